@@ -43,6 +43,24 @@ CONFIGS = {   # BASELINE.json configs[1..4]
 PEAK_MFMA_F32 = 157.3e12     # MI355X_MICROARCH.md: dense f32-input MFMA peak
 PEAK_MFMA_F16 = 2.5e15       # dense f16-input MFMA peak (never the 2:1-sparsity figure)
 PEAK_HBM = 8.0e12            # bytes / s
+# the device noise counter (DGP_VI._words()[1]) at the first timed evaluation: the timed region draws the same noise in every run, whatever
+# number of evaluations the adaptive warm-up ran, and no step number of the warm-up comes back (the counter is 64-bit)
+TIMED_NOISE_STEP = 1 << 32
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as ``out_dir/<name>.npy`` (float32 stays float32, anything else becomes float64).  An array beyond its
+    share of ``limit`` is replaced by a fixed, seeded sample of its flattened elements (sorted indices, the same in every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = limit // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def f_alg_layer(M, D, R, P):
@@ -99,6 +117,7 @@ class Step:
         self.B, self.K = spec["B"], spec["K"]
         self.K_total = K_total if K_total is not None else self.K * self.world
         self.out = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.logp = None
 
     def run(self, out=None, zs=None):
         """``out``: the exchange staging buffer this evaluation's result goes to ([B, 2] pairs / 1-element ELBO);
@@ -107,7 +126,8 @@ class Step:
         if self.shard == "k" and self.exchange:
             self.ms, self.glob = m.lse_partials(zs, K_total=self.K_total, out=out)
             return self.ms
-        self.out = m._build_likelihood(zs, out=out)
+        # _build_likelihood's own call, keeping the per-point log p [B] the same launch writes (E_log_p_Y; --dump-outputs)
+        self.out, self.logp, _ = m._elbo_parts(zs, elbo_out=out)
         return self.out
 
 
@@ -586,10 +606,18 @@ def main():
                     help="plumbing only: every rank joins the process group (gloo, CPU tensors), all-reduces its rank and rank 0 prints "
                          "{n_ranks_seen, rank_sum, env}; no GPU is touched -- checks the launcher and the rendezvous by themselves")
     ap.add_argument("--launch-timeout", type=float, default=1800.0, help="self-launched ranks are stopped after this many seconds")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed evaluation returned as DIR/<name>.npy: elbo (float64 [1]; the merged "
+                         "ELBO when sharded) and, single-rank, log_p (float32 [B], per-point log p of the same launch)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(launch_ranks(args, sys.argv[1:]))               # (this process never touches the GPU)
+        argv = sys.argv[1:]
+        if args.dump_outputs:                                    # (the ranks run in ROOT; the last --dump-outputs wins)
+            argv += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
+        sys.exit(launch_ranks(args, argv))                       # (this process never touches the GPU)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -704,6 +732,7 @@ def main():
                     graph.append(gph)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
+    graph_last = (step.out, step.logp)                           # what the replayed graph's last evaluation writes (eager calls replace step.out)
 
     def one_step():
         """spg evaluations (one graph replay), plus their exchange when sharded."""
@@ -758,6 +787,7 @@ def main():
         for _ in range(n_more):
             one_step()
         n_warm += 1 + n_more
+    model._words()[1].fill_(TIMED_NOISE_STEP)                    # (stream-ordered after the warm-up)
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps // spg):
@@ -771,8 +801,15 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
-    final_elbo = float((xch.finish()[-1] if xch is not None else step.out.reshape(1)).item())
+    # the last timed evaluation's results: a replay's buffers unless the timed region ended with evaluations launched singly
+    last_out, last_logp = (step.out, step.logp) if graph is None or args.steps % spg else graph_last
+    final_elbo = float((xch.finish()[-1] if xch is not None else last_out.reshape(1)).item())
     exchange_ms = xch.exchange_ms() if xch is not None else None
+    if args.dump_outputs and rank == 0:
+        outs = {"elbo": np.array([final_elbo], dtype=np.float64)}
+        if xch is None:
+            outs["log_p"] = last_logp.detach().cpu().numpy()
+        dump_outputs(args.dump_outputs, outs)
 
     # ---- --check: the sharded path against the unsharded job on injected noise (multi-rank correctness, no timing) ----------
     check = None

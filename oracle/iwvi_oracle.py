@@ -4,7 +4,7 @@ TEST INFRASTRUCTURE ONLY (see oracle/__init__.py).  **Parity unpinned**: the
 reference holds no golden vectors and cannot run here; this file follows the
 reference line by line in *algorithm*, not in code (it is NumPy with explicit
 noise arguments, the reference is a TensorFlow-1 graph with unseeded
-``tf.random_normal``).  Citations are relative to ``/root/reference``.
+``tf.random_normal``).  Citations are relative to the reference repository (hughsalimbeni/DGPs_with_IWVI).
 
 Every stochastic site of the reference takes its standard-normal draw as an
 argument here so that the HIP path and the oracle can be fed identical noise:

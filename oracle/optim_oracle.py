@@ -2,7 +2,7 @@
 applies per training step (experiments/build_models.py:284-304), restated in NumPy float64.
 
   * ``natgrad_step``: GPflow 1.x ``NatGradOptimizer(gamma)`` with the default natural parameterisation on a whitened
-    (q_mu [M, R], q_sqrt [R, M, M]).  GPflow is not vendored in /root/reference (unpinned,
+    (q_mu [M, R], q_sqrt [R, M, M]).  GPflow is not vendored in the reference repository (unpinned,
     1.3 <= v < 2.0); the algorithm restated here is the published one (Salimbeni, Eleftheriadis, Hensman 2018,
     "Natural gradients in practice", eq. 3-5 / GPflow ``training/natgrad_optimizer.py``):
         eta = (m, S + m m^T),  theta = (S^-1 m, -1/2 S^-1),  theta <- theta - gamma * dLoss/d eta,

@@ -2,7 +2,7 @@ import os
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 import ctypes, sys
 import numpy as np, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import CONFIGS
 from dgps_with_iwvi_amd import _abi, synthetic
 dev = torch.device("cuda:0")

@@ -1,4 +1,4 @@
-"""Child process of tests/test_gpu_multirank.py::test_trainer_n_shard_ranks_built_from_local_rows: one rank of a 2- or 8-rank (gloo,
+"""Child process of tests/test_gpu_multirank.py::test_trainer_n_shard_ranks_built_from_local_rows: one rank of a 2- or 4-rank (gloo,
 all on cuda:0) data-parallel job.  The rank builds its model from ITS OWN rows of the data set (so models.py:18 gives it a local
 num_data), wraps it in training.Trainer(group=...), evaluates one gradient on its slice of a job-wide injected noise draw and writes
 the merged gradient to an .npz."""

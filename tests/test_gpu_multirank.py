@@ -15,6 +15,9 @@ import torch
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# rank processes one test may start on the shared GPU: the pytest process holds it open too, and no more than six processes may
+# have one device open at a time
+MAX_RANKS = 4
 
 
 def _free_port():
@@ -24,6 +27,7 @@ def _free_port():
 
 
 def _run_bench(world, shard, extra=(), backend="gloo", timeout=600, train_leg=False):
+    assert world <= MAX_RANKS, world
     port = _free_port()
     procs = []
     for rank in range(world):
@@ -190,29 +194,29 @@ def test_overlapped_exchange_slot_reuse(gpu_device):
         dist.destroy_process_group()
 
 
-def test_bench_eight_ranks_split_k_at_the_configs3_stack(gpu_device):
-    """BASELINE.json configs[3] -- 3-layer DGP, M=256, K=50, 'K-sharded across 8' -- as the driver will start it on an 8-GPU node, here as 8
-    fresh rank processes over gloo on ONE GPU at a reduced batch: --split-k gives the ranks 7,7,6,6,6,6,6,6 of the job's 50 importance
-    samples; the merged ELBO of the job-wide injected draw equals the single-rank evaluation of the whole job."""
-    res = _run_bench(8, "k", extra=("--split-k", "--config", "3", "--batch", "64"), timeout=900)
-    assert res["n_gpus"] == 8 and res["n_ranks_seen"] == 8 and res["scaling"] == "strong"
-    assert res["config"]["K_total"] == 50 and res["config"]["K_per_rank"] == [7, 7, 6, 6, 6, 6, 6, 6]
+def test_bench_four_ranks_split_k_at_the_configs3_stack(gpu_device):
+    """BASELINE.json configs[3] -- 3-layer DGP, M=256, K=50, 'K-sharded across 8' -- through the code path an 8-GPU node runs, here as 4
+    fresh rank processes over gloo on ONE GPU (MAX_RANKS) at a reduced batch: --split-k gives the ranks an uneven 13,13,12,12 of the job's 50
+    importance samples; the merged ELBO of the job-wide injected draw equals the single-rank evaluation of the whole job."""
+    res = _run_bench(4, "k", extra=("--split-k", "--config", "3", "--batch", "64"), timeout=900)
+    assert res["n_gpus"] == 4 and res["n_ranks_seen"] == 4 and res["scaling"] == "strong"
+    assert res["config"]["K_total"] == 50 and res["config"]["K_per_rank"] == [13, 13, 12, 12]
     c = res["check"]
     assert c["K_total"] == 50 and c["B_total"] == 64 and c["all_steps_equal"]
     assert c["rel_diff"] <= 2e-6, c
     assert np.isfinite(res["value"]) and res["value"] > 0
 
 
-def test_bench_eight_ranks_n_shard_at_the_configs3_stack(gpu_device):
-    """The same stack N-sharded over 8 ranks (32 points each, all 50 samples): one scalar all-reduce per replay."""
-    res = _run_bench(8, "n", extra=("--config", "3", "--batch", "32"), timeout=900)
-    assert res["n_ranks_seen"] == 8 and res["scaling"] == "weak"
+def test_bench_four_ranks_n_shard_at_the_configs3_stack(gpu_device):
+    """The same stack N-sharded over 4 ranks (64 points each, all 50 samples): one scalar all-reduce per replay."""
+    res = _run_bench(4, "n", extra=("--config", "3", "--batch", "64"), timeout=900)
+    assert res["n_ranks_seen"] == 4 and res["scaling"] == "weak"
     c = res["check"]
     assert c["K_total"] == 50 and c["B_total"] == 256 and c["all_steps_equal"]
     assert c["rel_diff"] <= 2e-6, c
 
 
-@pytest.mark.parametrize("rows", [(30, 18), (9, 8, 7, 6, 6, 5, 4, 3)])
+@pytest.mark.parametrize("rows", [(30, 18), (17, 13, 11, 7)])
 def test_trainer_n_shard_ranks_built_from_local_rows(gpu_device, tmp_path, rows):
     """every rank constructs its model from its own rows (local num_data, models.py:18) and uneven minibatches
     (30 + 18 points).  Trainer(group=...) must scale the data term by the JOB's num_data and weigh the ranks by B_rank / B_job: the
@@ -222,7 +226,8 @@ def test_trainer_n_shard_ranks_built_from_local_rows(gpu_device, tmp_path, rows)
     out = str(tmp_path / "grad_rank%d.npz")
     worker = os.path.join(ROOT, "tests", "helpers", "nshard_trainer_worker.py")
     procs = []
-    world = len(rows)                                             # 2 ranks, and the 8 of a full node (the gradient bucket of sharding.allreduce_gradients)
+    world = len(rows)                                             # 2 ranks, and 4 with four different row counts (the gradient bucket of sharding.allreduce_gradients)
+    assert world <= MAX_RANKS, world
     for rank in range(world):
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    HSA_ENABLE_IPC_MODE_LEGACY="0")

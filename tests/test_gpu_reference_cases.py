@@ -105,7 +105,7 @@ def test_reference_test_dgp_zero_inner_layers(gpu_device, inner_noise):
     """A first layer with RBF(variance=1e-6), Identity mean function, q_sqrt * 1e-12, Z = X and jitter 1e-18
     (``temp_settings``) passes its input through, so the 2-layer DGP's ``predict_f_full_cov`` equals the 1-layer SVGP's.
     The reference asserts atol = rtol = 1e-5 in float64 with the inner layer's random draw left in
-    (/root/reference/tests/test_gp_layer.py:93-96).  Both layers are 1-D, so both take the float64 stage-1 route (asserted): the
+    (reference tests/test_gp_layer.py:93-96).  Both layers are 1-D, so both take the float64 stage-1 route (asserted): the
     inner layer's marginal variance sigma^2 - |a|^2 (true value ~1e-15: Xs lies between the inducing inputs of a kernel with
     lengthscale 1) is differenced in float64 -- measured <= 1.2e-18, i.e. the draw moves the outer layer's input by
     |z| sqrt(var) <= 2.5e-11 -- and the outer layer's K_uf, solve and variance are float64 too; what is left is the float32
