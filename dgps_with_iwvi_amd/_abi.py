@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libiwvi_hip.so")
 
 KERN_RBF, KERN_MATERN52 = 0, 1
 LAYER_GP, LAYER_LV = 0, 1
-ABI_VERSION = 17
+ABI_VERSION = 18
 GP_WANT_DENSE = 1
 GP_WANT_LM = 2
 GP_REUSE_FACTOR = 8
@@ -35,6 +35,7 @@ c_void_p, c_int, c_int64, c_float, c_double, c_size_t = (
 
 
 ERR_ARG, ERR_LAUNCH, ERR_UNSUPPORTED = -1, -2, -3      # enum iwvi_status (include/iwvi_hip.h)
+BW_ROUTE_CHAIN, BW_ROUTE_MID, BW_ROUTE_GEMM = 1, 2, 3   # iwvi_debug_last_backward_routes
 
 
 class IwviError(RuntimeError):
@@ -162,6 +163,7 @@ PROTOTYPES = {
     "iwvi_natgrad_ws_bytes_ex": (c_size_t, [c_int, c_int]),
     "iwvi_natgrad_step_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p, c_size_t, c_void_p]),
     "iwvi_debug_last_natgrad_route": (c_int, []),
+    "iwvi_debug_last_backward_routes": (c_int, [ctypes.POINTER(c_int), c_int]),
     "iwvi_adam_step": (c_int, [ctypes.POINTER(AdamTensor), c_int, c_double, c_double, c_double, c_double, c_int64,
                                c_int, c_int, c_void_p]),
     "iwvi_adam_step_dev": (c_int, [ctypes.POINTER(AdamTensor), c_int, c_double, c_double, c_double, c_double, c_void_p, c_int, c_void_p]),
@@ -221,6 +223,14 @@ DEBUG_OPTIONS = ("IWVI_BW_FUSED", "IWVI_CHAIN_EXIT", "IWVI_FW_SLOW_TAIL", "IWVI_
 def set_debug_option(name, value):
     """``iwvi_debug_set_option``: a development route switch of the library (process-wide; 0 = default route)."""
     check(lib().iwvi_debug_set_option(name.encode(), int(value)))
+
+
+def backward_routes():
+    """``iwvi_debug_last_backward_routes``: [(route, D bucket, samples per workgroup)] of the GP layer adjoints since the previous call,
+    in call order (the log is emptied)."""
+    buf = (c_int * (3 * MAX_STACK))()
+    n = lib().iwvi_debug_last_backward_routes(buf, MAX_STACK)
+    return [tuple(buf[3 * i:3 * i + 3]) for i in range(min(n, MAX_STACK))]
 
 
 _lib = None

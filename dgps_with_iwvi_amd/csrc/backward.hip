@@ -2700,6 +2700,22 @@ extern "C" int iwvi_gp_layers_backward_prepare(const iwvi_gp_bwd_desc* descs, in
     return check_launch("iwvi_gp_layers_backward_prepare");
 }
 
+// diagnostic (iwvi_debug_last_backward_routes): the route of every layer adjoint since the last read -- {route, D bucket of the
+// kernel-adjoint template, samples per workgroup}; the latest IWVI_MAX_STACK are kept
+static int g_bw_route[IWVI_MAX_STACK][3];
+static int g_bw_nroute = 0;
+static void note_bw_route(int route, int dbucket, int nsamp) {
+    int* r = g_bw_route[g_bw_nroute % IWVI_MAX_STACK];
+    r[0] = route; r[1] = dbucket; r[2] = nsamp;
+    ++g_bw_nroute;
+}
+extern "C" int iwvi_debug_last_backward_routes(int* out_host, int max) {
+    const int n = g_bw_nroute, kept = n < IWVI_MAX_STACK ? n : IWVI_MAX_STACK;
+    for (int i = 0; i < kept && i < max && out_host; ++i)
+        for (int j = 0; j < 3; ++j) out_host[3 * i + j] = g_bw_route[(n - kept + i) % IWVI_MAX_STACK][j];
+    g_bw_nroute = 0;
+    return n;
+}
 extern "C" int iwvi_gp_layer_backward(const iwvi_gp_bwd_desc* dp, int64_t T, void* ws_, void* stream_) {
     if (!dp || !ws_ || T <= 0) { set_error("iwvi_gp_layer_backward: bad argument"); return IWVI_ERR_ARG; }
     const iwvi_gp_bwd_desc& d = *dp;
@@ -2782,6 +2798,7 @@ extern "C" int iwvi_gp_layer_backward(const iwvi_gp_bwd_desc* dp, int64_t T, voi
             }
             ca.DK = nullptr;
         }
+        if (phase != 2) note_bw_route(IWVI_BW_ROUTE_CHAIN, D <= 8 ? 8 : (D <= 16 ? 16 : 32), 16 * chain_ns_shape(T, M, D, R, d.P));
         if (phase != 2 && (rc = launch_chain(st, ca)) != IWVI_OK) return rc;
         if (phase == 1) return IWVI_OK;
         if (q_only) {                                      // the two reductions (+ G_r by split-K GEMM where the chain does not form it), then dL_r
@@ -2804,6 +2821,7 @@ extern "C" int iwvi_gp_layer_backward(const iwvi_gp_bwd_desc* dp, int64_t T, voi
         // diag(2 dv_r) U_r) -- nothing of the kernel adjoint, the triangular solves or the adjoint of the factorisation
         HeadArgs h{d.A, d.U, d.noise, d.W, d.mf_A, d.d_sample, d.d_mean, d.d_var, w.DMU, w.DV2, w.SDV, nullptr, T, M, Mp, D, R, d.P, d.mf_type, d.variance, d.variance_dev,
                    d.q_mu, nullptr, d.GMV};
+        note_bw_route(IWVI_BW_ROUTE_GEMM, 0, 0);           // (no kernel adjoint on this route)
         hipLaunchKernelGGL(k_bw_heads, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, st, h);
         if ((rc = check_launch("k_bw_heads")) != IWVI_OK) return rc;
         if (d.dq_mu && (rc = thin(st, d.A, Mp, M, w.DMU, R, R, 0, T, w.part, w.part_floats, d.dq_mu, 0, &rqB, d.q_mu, -d.kl_weight)) != IWVI_OK) return rc;
@@ -2819,7 +2837,9 @@ extern "C" int iwvi_gp_layer_backward(const iwvi_gp_bwd_desc* dp, int64_t T, voi
                d.U, d.A, Mp, d.q_sqrt, d.q_mu, w.LinvF, w.DK, d.F, w.Zt, w.invls, w.DA, w.Qx, (long long)T, M, D, R, d.variance, d.kern_type, d.variance_dev};
     const int fused = chain ? 1 : launch_mid(st, ma);      // heads + DA + dK + kernel adjoint in one launch where the shapes allow
     if (fused < 0) return fused;
+    if (fused && !chain) note_bw_route(IWVI_BW_ROUTE_MID, D <= 8 ? 8 : (D <= 16 ? 16 : 32), 64);
     if (!fused) {
+        note_bw_route(IWVI_BW_ROUTE_GEMM, D <= 4 ? 4 : (D <= 8 ? 8 : (D <= 16 ? 16 : 32)), 16);
         HeadArgs h{d.A, d.U, d.noise, d.W, d.mf_A, d.d_sample, d.d_mean, d.d_var, w.DMU, w.DV2, w.SDV, d.dF, T, M, Mp, D, R, d.P, d.mf_type, d.variance, d.variance_dev,
                    d.q_mu, (d.dW && d.W && !d.GMV) ? w.GMV : nullptr, d.GMV};
         hipLaunchKernelGGL(k_bw_heads, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, st, h);

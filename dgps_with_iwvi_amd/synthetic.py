@@ -18,15 +18,26 @@ def _f32(a):
 
 
 def make_spec(L=2, M=128, B=1024, K=20, Dx=8, Dy=1, R=5, with_lv=False, seed=0, n_data=None,
-              parity=True, latent_dim=1):
+              parity=True, latent_dim=1, mixing="svd", distinct_y=False):
     """L = number of GP layers (L-1 inner ``G<R>`` + final).  parity=True randomises q_mu / q_sqrt
     (q_mu ~ N(0,1), q_sqrt = 0.1 tril(N(0,1)) + I scaled) so that every term of the conditional is
-    exercised; parity=False uses the reference's initial values (q_mu = 0, inner q_sqrt = 1e-5 I)."""
+    exercised; parity=False uses the reference's initial values (q_mu = 0, inner q_sqrt = 1e-5 I).
+
+    Opt-in knobs for wide shapes (the defaults leave every array as before, bit for bit): mixing="dense" gives every inner W [P, R]
+    Gaussian entries scaled by 1/sqrt(R) -- with "svd" (the reference's) the columns r >= Dx are zero, so latent GPs beyond Dx never reach
+    the output --, and distinct_y=True makes the Dy > 1 output columns different functions of X instead of copies of one column.
+    Both draw from a generator of their own, so they change nothing else of the spec."""
+    if mixing not in ("svd", "dense"):
+        raise ValueError("mixing must be 'svd' or 'dense', got %r" % (mixing,))
     rng = np.random.default_rng(seed)
+    rng_x = np.random.default_rng([seed, 0x6b6e6f62])              # the knobs' own stream
     n_data = max(B, M) if n_data is None else n_data
     X = _f32(rng.standard_normal((n_data, Dx)))
     Y = np.sin(X.sum(1, keepdims=True)) + 0.1 * rng.standard_normal((n_data, 1))
-    Y = np.tile(Y, [1, Dy]) if Dy > 1 else Y
+    if distinct_y and Dy > 1:
+        proj = rng_x.standard_normal((Dx, Dy))
+        Y = np.sin(X @ proj + rng_x.uniform(0, np.pi, Dy)) + 0.1 * rng_x.standard_normal((n_data, Dy))
+    Y = np.tile(Y, [1, Dy]) if Dy > 1 and Y.shape[1] == 1 else Y
     Y = _f32((Y - Y.mean(0)) / Y.std(0))
     Z0 = X[:M].copy()                                              # build_models.py:179-183 (no k-means)
     P = np.linalg.svd(X, full_matrices=False)[2]                   # :186
@@ -58,6 +69,8 @@ def make_spec(L=2, M=128, B=1024, K=20, Dx=8, Dy=1, R=5, with_lv=False, seed=0, 
         A[:min(D_in, D_out), :min(D_in, D_out)] = np.eye(min(D_in, D_out))   # :204-207
         W = np.zeros((D_out, R))
         W[:, :min(R, Dx)] = P[:, :min(R, Dx)]                       # :216-217
+        if mixing == "dense":
+            W = rng_x.standard_normal((D_out, R)) / np.sqrt(R)
         ZZ, q_mu, q_sqrt = gp_params(D_in, R, 0.3 if parity else 1e-5)
         layers.append(dict(type="gp", Z=ZZ, ls=_f32(np.full(D_in, float(D_in) ** 0.5)), var=1.0,
                            q_mu=q_mu, q_sqrt=q_sqrt, W=_f32(W), mf=("linear", _f32(A), np.zeros(D_out))))

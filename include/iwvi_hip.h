@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define IWVI_ABI_VERSION 17
+#define IWVI_ABI_VERSION 18
 
 enum {
     IWVI_OK = 0,
@@ -465,9 +465,10 @@ size_t iwvi_natgrad_ws_bytes(int M);
 int iwvi_natgrad_step(float* q_mu, float* q_sqrt, const float* dq_mu, const float* dq_sqrt,
                       int M, int R, double gamma, void* ws, void* stream);
 /* ABI 16: the same with the workspace sized for R latent GPs.  M <= 128: the step runs as five launches spread over the chip (their block
- * images take ~340 KB per latent GP at M = 128) when `ws_bytes` holds them for all R, else -- as iwvi_natgrad_step does beyond the R its
- * R-independent size happens to cover -- as one workgroup per latent GP: the same result, ~1.7x the time.  iwvi_natgrad_ws_bytes_ex(M, R)
- * is the size that always takes the spread route; iwvi_debug_last_natgrad_route(): 0 = multi-launch (M > 128), 1 = one workgroup per
+ * images take ~340 KB per latent GP at M = 128) when `ws_bytes` holds them for all R and R <= 8 (the spread route's inverse images hold 8
+ * latent GPs), else -- as iwvi_natgrad_step does beyond the R its R-independent size happens to cover -- as one workgroup per latent GP: the
+ * same result, ~1.7x the time.  iwvi_natgrad_ws_bytes_ex(M, R) is the size that takes the spread route whenever R <= 8; at R > 8 the step is
+ * one workgroup per latent GP whatever the workspace.  iwvi_debug_last_natgrad_route(): 0 = multi-launch (M > 128), 1 = one workgroup per
  * latent GP, 2 = spread. */
 size_t iwvi_natgrad_ws_bytes_ex(int M, int R);
 int iwvi_natgrad_step_ex(float* q_mu, float* q_sqrt, const float* dq_mu, const float* dq_sqrt,
@@ -601,6 +602,14 @@ int iwvi_debug_set_option(const char* name, int value);
 int iwvi_debug_last_forward_variant(void);
 /* In-kernel time stamps of the fused forward / of the precompute launch (128 64-bit words per workgroup; NULL switches them off) and an
  * early exit of the fused forward after phase N -- timing scripts only (scripts/stamp_*.py, bench.py's gemm_phase_mfma_util). */
+/* ABI 18: the route of every GP layer adjoint (iwvi_gp_layer_backward) since the previous call of this function, in call order (the latest
+ * IWVI_MAX_STACK are kept): 3 ints per layer in out_host -- the route (IWVI_BW_ROUTE_*), the input-dimension bucket of the kernel-adjoint
+ * template that ran (8 / 16 / 32 for the chain and the fused kernel, 4 / 8 / 16 / 32 for the GEMM route's k_bw_kernel, 0 where no kernel
+ * adjoint ran) and the samples per workgroup of that kernel.  Writes at most `max` layers, returns how many were recorded, empties the log. */
+#define IWVI_BW_ROUTE_CHAIN 1   /* k_bw_chain: the streaming per-sample chain             */
+#define IWVI_BW_ROUTE_MID 2     /* k_bw_mid: heads + dA + dK + kernel adjoint in one launch */
+#define IWVI_BW_ROUTE_GEMM 3    /* k_bw_heads, the GEMMs over u_out, k_bw_kernel          */
+int iwvi_debug_last_backward_routes(int* out_host, int max);
 void iwvi_debug_set_stamps(void* buf, int64_t max_workgroups);
 void iwvi_debug_set_pre_stamps(void* buf);
 void iwvi_debug_set_exit(int phase);

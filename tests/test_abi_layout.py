@@ -60,7 +60,8 @@ def test_flag_constants_match_the_header():
     pairs = {"GP_WANT_DENSE": "IWVI_GP_WANT_DENSE", "GP_WANT_LM": "IWVI_GP_WANT_LM", "GP_F64_STAGE1": "IWVI_GP_F64_STAGE1",
              "GP_REUSE_FACTOR": "IWVI_GP_REUSE_FACTOR", "GP_FACTOR_ONLY": "IWVI_GP_FACTOR_ONLY",
              "BW_F32_CHAIN": "IWVI_BW_F32_CHAIN", "BW_OWN_QSCALE": "IWVI_BW_OWN_QSCALE",
-             "MAX_STACK": "IWVI_MAX_STACK", "ERR_UNSUPPORTED": "IWVI_ERR_UNSUPPORTED"}
+             "MAX_STACK": "IWVI_MAX_STACK", "ERR_UNSUPPORTED": "IWVI_ERR_UNSUPPORTED",
+             "BW_ROUTE_CHAIN": "IWVI_BW_ROUTE_CHAIN", "BW_ROUTE_MID": "IWVI_BW_ROUTE_MID", "BW_ROUTE_GEMM": "IWVI_BW_ROUTE_GEMM"}
     checked = 0
     for py, c in pairs.items():
         if hasattr(_abi, py) and c in defs:

@@ -121,9 +121,6 @@ def test_gp_layer_backward_on_a_float64_route_layer(gpu_device, Dx, M, T, li):
         layer.fused_desc(tt(z), None)
 
 
-os.environ.setdefault("IWVI_BW_FUSED", "1")      # exercise the fused per-sample kernel wherever the shapes allow it (it is gated by size otherwise)
-
-
 def _model_grads(gpu_device, spec, zs):
     from dgps_with_iwvi_amd import synthetic, backward
     model = synthetic.build_model(spec, gpu_device)
@@ -183,7 +180,8 @@ def test_iw_elbo_gradients_match_golden(gpu_device, name):
 
 
 @pytest.mark.parametrize("L,M,K,B,lv", [(2, 64, 5, 16, True), (3, 32, 4, 12, True), (2, 128, 3, 40, False), (1, 48, 6, 10, False),
-                                        # T = B*K a multiple of 64 and M in {64, 128, 256}: the fused per-sample kernel (k_bw_mid)
+                                        # T = B*K a multiple of 64 and M in {64, 128, 256} (these take the streaming chain: the fused
+                                        # per-sample kernel k_bw_mid runs only where the chain's tiles overflow the LDS -- test_gpu_shape_envelope.py)
                                         (2, 64, 4, 16, True), (2, 128, 8, 16, True), (3, 128, 4, 32, False), (2, 256, 8, 8, True),
                                         # ragged: M not a multiple of 16 (padded states), odd B and K
                                         (2, 40, 3, 7, True), (3, 50, 5, 3, False)])

@@ -86,17 +86,99 @@ def test_fp32_route_has_its_compiled_in_shapes_variant_too(gpu_device):
     assert abs(e_lean - e_gen) <= 2e-7 * abs(e_gen), (e_lean, e_gen)
 
 
+def _read_back_vs_oracle(model, spec, lw_first):
+    """The same noise step once more through the variant that returns its draws: identical log-weights, and the bound, per-point terms
+    and log-weights against the float64 oracle on those draws (the tolerances of test_lean_variant_against_the_oracle_at_the_bench_shape)."""
+    from oracle.from_spec import build_oracle, oracle_noise
+    B, K = spec["B"], spec["K"]
+    model._words().zero_()
+    model.precompute(with_encoders=True)
+    lw_gen, outs, red = model._fused_forward(B * K, K, B, (B, K), zs=None, sampled_kl=True, want_layers=True, want_saved=True,
+                                             elbo=dict(B=B, K=K, stride_b=K, stride_k=1, mode_vi=False))
+    torch.cuda.synchronize()
+    assert not (_last_variant() & LEAN_BIT)
+    np.testing.assert_array_equal(lw_first, lw_gen.double().cpu().numpy().reshape(B, K))
+    zs = [o["noise_out"].double().cpu().numpy().reshape(B, K, -1) for o in outs]
+    om = build_oracle(spec)
+    L_NK = om.log_weights(oracle_noise(spec, zs))[0]
+    m_o = L_NK.max(1)
+    np.testing.assert_allclose(lw_first, L_NK, rtol=2e-4, atol=2e-2)
+    return om.build_likelihood(oracle_noise(spec, zs)), m_o + np.log(np.exp(L_NK - m_o[:, None]).sum(1)) - np.log(K)
+
+
+# Both sides of every condition the compiled-in-shape variants (SHP / LEAN) compile in: M = 128 (8 blocks), D <= 10 (3 MFMA steps of K_uf,
+# the mean function's loop), P <= 16 (one block of outputs), RBF, whole 80-sample chunks, 5 sub-tiles per workgroup with the operands staged
+# in LDS -- so a wide R or P that makes the LDS plan drop the staging (R = 17 or 32, P = 16 beside an LV layer) takes the general variant;
+# those shapes are below.  T = B K = 16 400 (a multiple of 80, every CU a workgroup).
+_INSIDE = [("Dx = 10, no LV (D = 10)", dict(L=2, B=820, K=20, Dx=10, R=5)),
+           ("Dx = 9 + LV (D = 10)", dict(L=2, B=820, K=20, Dx=9, R=5, with_lv=True)),
+           ("L = 1", dict(L=1, B=820, K=20, Dx=8, with_lv=True)),
+           ("L = 4", dict(L=4, B=820, K=20, Dx=8, R=5, with_lv=True)),
+           ("K = 8", dict(L=2, B=2050, K=8, Dx=8, R=5, with_lv=True))]
+
+
+@pytest.mark.parametrize("why,kw", _INSIDE + [("fp32 stage 2, D = 10", dict(L=2, B=820, K=20, Dx=10, R=5, f32=True))],
+                         ids=[w for w, _ in _INSIDE] + ["fp32 stage 2, D = 10"])
+def test_shapes_inside_the_variant_take_it_and_match_the_oracle(gpu_device, why, kw):
+    from dgps_with_iwvi_amd import settings, synthetic
+    kw = dict(kw)
+    f32 = kw.pop("f32", False)
+    spec = synthetic.make_spec(M=128, mixing="dense", seed=kw["B"] + kw["Dx"], n_data=65536, **kw)
+    settings.set_seed(kw["Dx"])
+    old, settings.fw_f32_stage2 = settings.fw_f32_stage2, f32
+    try:
+        model = synthetic.build_model(spec, gpu_device)
+        e_lean, lp_lean, lw_lean, v_lean = _evaluate(model, spec, force_general=False)
+        e_gen, lp_gen, lw_gen, v_gen = _evaluate(model, spec, force_general=True)
+        ref, lp_ref = _read_back_vs_oracle(model, spec, lw_lean)
+    finally:
+        settings.fw_f32_stage2 = old
+    assert v_lean & LEAN_BIT and (v_lean & 0xff) == 5 and bool(v_lean & S16_BIT) == (not f32), (why, hex(v_lean))
+    assert not (v_gen & (LEAN_BIT | SHAPES_BIT)), (why, hex(v_gen))
+    np.testing.assert_array_equal(lw_lean, lw_gen)
+    assert abs(e_lean - e_gen) <= 2e-7 * abs(e_gen), (e_lean, e_gen)
+    assert abs(e_lean - ref) <= 1e-4 * abs(ref), (why, e_lean, ref)
+    np.testing.assert_allclose(lp_lean, lp_ref, rtol=2e-4, atol=2e-2)
+
+
 @pytest.mark.parametrize("why,kw", [("M = 64", dict(L=2, M=64, B=1024, K=20, with_lv=True)),
                                     ("K = 40 (tail needs K <= 32)", dict(L=2, M=128, B=512, K=40, with_lv=True)),
-                                    ("a ragged last workgroup", dict(L=2, M=128, B=1023, K=20, with_lv=True))])
+                                    ("a ragged last workgroup", dict(L=2, M=128, B=1023, K=20, with_lv=True)),
+                                    ("R = 17, dense mixing: operands not staged", dict(L=2, M=128, B=820, K=20, Dx=8, R=17, with_lv=True, mixing="dense")),
+                                    ("R = 32, dense mixing: NS = 4", dict(L=2, M=128, B=820, K=20, Dx=8, R=32, with_lv=True, mixing="dense")),
+                                    ("Dx = 9 + LV, Dy = 16: operands not staged", dict(L=2, M=128, B=820, K=20, Dx=9, Dy=16, with_lv=True, distinct_y=True)),
+                                    ("Dx = 10 + LV (D = 11)", dict(L=2, M=128, B=820, K=20, Dx=10, with_lv=True)),
+                                    ("Dx = 11, no LV", dict(L=2, M=128, B=820, K=20, Dx=11)),
+                                    ("Dy = 17 (only P out of range)", dict(L=2, M=128, B=820, K=20, Dx=8, Dy=17, distinct_y=True)),
+                                    ("Matern52 at M = 128", dict(L=2, M=128, B=820, K=20, Dx=8, with_lv=True, matern=True)),
+                                    ("M = 127 (8 blocks, not 128)", dict(L=2, M=127, B=820, K=20, Dx=8, with_lv=True)),
+                                    ("M = 129", dict(L=2, M=129, B=820, K=20, Dx=8, with_lv=True))])
 def test_shapes_outside_the_variant_take_the_general_one(gpu_device, why, kw):
-    from dgps_with_iwvi_amd import settings, synthetic
+    from dgps_with_iwvi_amd import kernels, settings, synthetic
+    kw = dict(kw)
+    matern = kw.pop("matern", False)
     spec = synthetic.make_spec(seed=3, n_data=65536, **kw)
     settings.set_seed(5)
     model = synthetic.build_model(spec, gpu_device)
+    if matern:
+        for layer in model.layers[1:]:
+            old = layer._base_kern()
+            new = kernels.Matern52(old.input_dim, variance=old.variance, lengthscales=old.lengthscales, ARD=True).to(gpu_device)
+            if hasattr(layer.kern, "kernel"):
+                layer.kern.kernel = new
+            else:
+                layer.kern = new
     e, lp, lw, v = _evaluate(model, spec, force_general=False)
-    assert not (v & LEAN_BIT), why
+    # (K = 40 keeps the compiled-in shapes with the general tail, bit 11: only LEAN's tail needs K <= 32)
+    assert not (v & (LEAN_BIT | (0 if "K = 40" in why else SHAPES_BIT))), (why, hex(v))
     assert np.isfinite(e) and np.isfinite(lw).all()
+    e_gen, lp_gen, lw_gen, v_gen = _evaluate(model, spec, force_general=True)
+    np.testing.assert_array_equal(lw, lw_gen)                   # both runs took the general variant: the same bits
+    if "M = 64" in why or "K = 40" in why or "ragged" in why or matern:
+        return                                                  # (the oracle is RBF-only; the first three are covered elsewhere)
+    ref, lp_ref = _read_back_vs_oracle(model, spec, lw)
+    assert abs(e - ref) <= 1e-4 * abs(ref), (why, e, ref)
+    np.testing.assert_allclose(lp, lp_ref, rtol=2e-4, atol=2e-2)
 
 
 def test_requested_layer_outputs_take_the_variant_that_keeps_them(gpu_device):

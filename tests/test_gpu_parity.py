@@ -34,7 +34,9 @@ def _np(t):
 @pytest.mark.parametrize("M,D,R,kern", [(10, 1, 2, "matern"), (64, 8, 1, "rbf"), (100, 3, 2, "rbf"),
                                         (128, 9, 5, "rbf"), (200, 8, 2, "rbf"), (256, 8, 3, "rbf"),
                                         (128, 1, 1, "rbf"),      # dense 1-D cloud: K_uu is numerically rank-deficient, jitter decides
-                                        (512, 8, 1, "rbf")])     # the largest supported inducing set
+                                        (512, 8, 1, "rbf"),      # the largest supported inducing set
+                                        # the caps: kl[IWVI_MAX_R] filled, D = 30 (8 K_uf steps) / 32 (9 steps)
+                                        (128, 32, 32, "rbf"), (96, 30, 17, "rbf"), (512, 32, 32, "rbf")])
 def test_precompute_factorisation(gpu_device, M, D, R, kern):
     """Kuu + tf.cholesky (temp_workaround.py:39,48), Lm^-1 and gauss_kl (:186-188) vs NumPy fp64."""
     from dgps_with_iwvi_amd import kernels, settings
@@ -141,6 +143,12 @@ def _oracle_layer(c, D, R, mixing, mf, full_cov=False, z=None):
     (250, 8, 2, 2, False, "zero", 3, 40),       # super-block solve (M > 240) with padded inducing rows, split-f16 dense part
     (270, 5, 1, 1, False, "linear", 2, 30),     # 17 block rows: odd, so the fp32 variant; a one-row last super-block
     (384, 8, 3, 8, True, "linear", 2, 24),      # three super-blocks
+    # the caps: two 16-row q(u) and output blocks, 9 MFMA steps of K_uf (D = 31, 32), the M > 128 build at full width
+    (128, 32, 32, 32, True, "linear", 2, 40),
+    (64, 31, 17, 17, True, "linear", 3, 21),
+    (256, 24, 16, 32, True, "linear", 2, 33),
+    (127, 17, 20, 20, True, "zero", 2, 30),
+    (512, 32, 32, 32, True, "linear", 2, 24),
 ])
 def test_gp_layer_forward(gpu_device, M, D, R, P, mixing, mf, S, N):
     c = _layer_case(M + D + R, M, D, R, P, mixing, mf, S, N)

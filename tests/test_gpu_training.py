@@ -18,13 +18,15 @@ def _t(a, dev):
     return torch.as_tensor(np.asarray(a, dtype=np.float32), device=dev)
 
 
-@pytest.mark.parametrize("M,R", [(8, 1), (40, 2), (100, 3), (128, 1), (128, 5), (200, 1), (256, 1), (512, 1)])      # M <= 128: spread / one workgroup per latent GP; beyond: the multi-launch path (the final layers of configs[3] / [4])
+@pytest.mark.parametrize("M,R", [(8, 1), (40, 2), (100, 3), (128, 1), (128, 5), (200, 1), (256, 1), (512, 1),   # M <= 128: spread / one workgroup per latent GP; beyond: the multi-launch path (the final layers of configs[3] / [4])
+                                 (40, 9), (128, 17), (128, 32), (512, 9), (512, 32)])                            # R > 8: past the spread route's 8 latent GPs
 def test_natgrad_step_matches_oracle(gpu_device, M, R):
     import ctypes
     from dgps_with_iwvi_amd import _abi
     lib = _abi.lib()
-    # ABI 16: the workspace sized for R latent GPs always takes the spread route at M <= 128 (the R-independent size fell back
-    # to the one-workgroup kernel beyond R = 3 without saying so); the route that ran is readable
+    # ABI 16: the workspace sized for R latent GPs takes the spread route at M <= 128 while R <= 8 (the R-independent size fell
+    # back to the one-workgroup kernel beyond R = 3 without saying so); beyond 8 latent GPs it is one workgroup per latent GP; the route
+    # that ran is readable
     wsx = torch.empty(lib.iwvi_natgrad_ws_bytes_ex(M, R), dtype=torch.uint8, device=gpu_device)
     assert wsx.numel() >= lib.iwvi_natgrad_ws_bytes(M) > 0
     rng = np.random.default_rng(M)
@@ -43,7 +45,7 @@ def test_natgrad_step_matches_oracle(gpu_device, M, R):
     x_mu, x_sqrt = _t(q_mu, gpu_device), _t(q_sqrt, gpu_device)
     _abi.check(lib.iwvi_natgrad_step_ex(_abi.ptr(x_mu), _abi.ptr(x_sqrt), _abi.ptr(dg_mu), _abi.ptr(dg_sqrt), M, R, 0.05,
                                         wsx.data_ptr(), wsx.numel(), _abi.stream_ptr()))
-    assert lib.iwvi_debug_last_natgrad_route() == (2 if M <= 128 else 0)
+    assert lib.iwvi_debug_last_natgrad_route() == ((2 if R <= 8 else 1) if M <= 128 else 0)
     np.testing.assert_allclose(x_mu.cpu().numpy(), ref_mu, rtol=2e-5, atol=2e-6)
     np.testing.assert_allclose(x_sqrt.cpu().numpy(), ref_sqrt, rtol=2e-5, atol=2e-6)
     with pytest.raises(_abi.IwviError):                          # a workspace smaller than the R-independent minimum is refused, not overrun
