@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libiwvi_hip.so")
 
 KERN_RBF, KERN_MATERN52 = 0, 1
 LAYER_GP, LAYER_LV = 0, 1
-ABI_VERSION = 18
+ABI_VERSION = 19
 GP_WANT_DENSE = 1
 GP_WANT_LM = 2
 GP_REUSE_FACTOR = 8
@@ -211,6 +211,11 @@ PROTOTYPES = {
     "iwvi_gauss_kl": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "iwvi_gaussian_var_exp": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int64, c_int, c_int64, c_int64,
                                       c_void_p, c_void_p]),
+    "iwvi_gaussian_log_density": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_int64, c_int64,
+                                          c_void_p, c_void_p]),
+    "iwvi_dgp_predict_density_ws_bytes": (c_size_t, [c_int64, c_int64]),
+    "iwvi_dgp_predict_density": (c_int, [ctypes.POINTER(LayerDesc), c_int, c_void_p, c_int, c_void_p, c_int, c_int64, c_int64,
+                                         c_float, c_void_p, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "iwvi_unwhiten": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "iwvi_fill_normal": (c_int, [c_void_p, c_int64, ctypes.c_uint64, ctypes.c_uint64, c_void_p]),
     "iwvi_fill_normal_dev": (c_int, [c_void_p, c_int64, ctypes.c_uint64, c_void_p, c_void_p]),

@@ -1,5 +1,6 @@
 // Small boundary entry points that are NOT on the IW-ELBO hot path but belong to the reference's API surface:
 //   iwvi_gaussian_var_exp  gpflow Gaussian.variational_expectations as a callable (models.py:66,134)
+//   iwvi_gaussian_log_density  gpflow Gaussian.logp / predict_density (GPModel.predict_density)
 //   iwvi_unwhiten          the second back-substitution of the unwhitened case (temp_workaround.py:63-65),
 //                          applied once to the operands instead of per sample
 // Both are HBM/latency-bound elementwise or M^3-sized float64 work; no MFMA shaping.
@@ -18,6 +19,22 @@ __global__ __launch_bounds__(256) void k_gauss_var_exp(const float* __restrict__
         const float y = Y[((t / row_div) % row_mod) * Dy + d];
         const float e = y - Fmu[idx];
         out[idx] = cst - 0.5f * (e * e + Fvar[idx]) * inv_var;
+    }
+}
+
+// log N(y; Fmu, Fvar + variance) elementwise (Fvar == NULL: log N(y; Fmu, variance)); the variance from a device scalar when one is given
+__global__ __launch_bounds__(256) void k_gauss_log_density(const float* __restrict__ Fmu, const float* __restrict__ Fvar,
+                                                           const float* __restrict__ Y, float lik_variance, const float* __restrict__ lik_var_dev,
+                                                           long long n, int Dy, long long row_div, long long row_mod, float* __restrict__ out) {
+    const float lv = lik_var_dev ? *lik_var_dev : lik_variance;
+    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < n;
+         idx += (long long)gridDim.x * blockDim.x) {
+        const long long t = idx / Dy;
+        const int d = (int)(idx - t * Dy);
+        const float y = Y[((t / row_div) % row_mod) * Dy + d];
+        const float e = y - Fmu[idx];
+        const float s = Fvar ? Fvar[idx] + lv : lv;
+        out[idx] = -0.5f * 1.8378770664093453f - 0.5f * logf(s) - 0.5f * e * e / s;
     }
 }
 
@@ -78,6 +95,20 @@ extern "C" int iwvi_gaussian_var_exp(const float* Fmu, const float* Fvar, const 
     hipLaunchKernelGGL(k_gauss_var_exp, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, Fmu, Fvar, Y,
                        1.f / lik_variance, cst, n, Dy, (long long)row_div, (long long)row_mod, out);
     return check_launch("iwvi_gaussian_var_exp");
+}
+
+extern "C" int iwvi_gaussian_log_density(const float* Fmu, const float* Fvar, const float* Y, float lik_variance, const float* lik_variance_dev,
+                                         int64_t T, int Dy, int64_t row_div, int64_t row_mod, float* out, void* stream_) {
+    if (T < 0 || Dy <= 0 || row_div <= 0 || row_mod <= 0 || (!lik_variance_dev && !(lik_variance > 0.f))) {
+        set_error("iwvi_gaussian_log_density: bad size / variance"); return IWVI_ERR_ARG;
+    }
+    if (T == 0) return IWVI_OK;
+    if (!Fmu || !Y || !out) { set_error("iwvi_gaussian_log_density: null pointer"); return IWVI_ERR_ARG; }
+    const long long n = (long long)T * Dy;
+    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    hipLaunchKernelGGL(k_gauss_log_density, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, Fmu, Fvar, Y, lik_variance, lik_variance_dev,
+                       n, Dy, (long long)row_div, (long long)row_mod, out);
+    return check_launch("iwvi_gaussian_log_density");
 }
 
 extern "C" int iwvi_unwhiten(const void* state, int M, int R, const float* f, const float* q_sqrt,

@@ -861,11 +861,16 @@ __device__ __forceinline__ void f64_solve(const FwHot& G, const double* Linv, co
     }
 }
 
+// LEAN_MODE = FW_MODE_PREDICT: the general layer loop with the predictive tail (iwvi_dgp_predict_density) in place of the bound's: per sample
+// sum_d log N(y; m, v + sigma^2), per data point (max, sum exp) over the chunk's samples of that point -> the ws partials k_pred_lse_merge finishes
+constexpr int FW_MODE_PREDICT = 3;
+
 template <int NS, bool S16, bool BIG, int LEAN_MODE = 0, bool F64 = false>
 __global__ __launch_bounds__(FW_THREADS) void k_dgp_forward(const FwArgs gk) {
-    static_assert(!F64 || (!S16 && BIG && LEAN_MODE == 0), "the float64 stage-1 variants: fp32 stage 2, every solve form, no compiled-in shapes");
+    static_assert(!F64 || (!S16 && BIG && (LEAN_MODE == 0 || LEAN_MODE == FW_MODE_PREDICT)), "the float64 stage-1 variants: fp32 stage 2, every solve form, no compiled-in shapes");
     constexpr int NSAMP = 16 * NS;
-    constexpr bool SHP = LEAN_MODE != 0;     // the headline stack's shapes and sources compiled in (all RBF, M = 128, D <= 10, operands staged, encoders
+    constexpr bool PRED = LEAN_MODE == FW_MODE_PREDICT;
+    constexpr bool SHP = LEAN_MODE == 1 || LEAN_MODE == 2;     // the headline stack's shapes and sources compiled in (all RBF, M = 128, D <= 10, operands staged, encoders
                                              // precomputed, noise drawn here, whole chunks): mode 1 and mode 2
     constexpr bool LEAN = LEAN_MODE == 1;    // ... and the bound's own evaluation: no per-layer outputs, the packed arrival, the half-wave tail.
                                              // Mode 2 keeps the outputs and the general tail: the forward of a value + gradient evaluation
@@ -1076,7 +1081,7 @@ __global__ __launch_bounds__(FW_THREADS) void k_dgp_forward(const FwArgs gk) {
     if (dma_wave) fw_copy_load(CT, sm, 0, ncopy0, dwave, lane, ce0, ndma);
     }
     // the chunk's targets y (a gather by LDS-DMA: no register, nothing waits here)
-    if (g.out_logw && dma_wave) {
+    if ((PRED || g.out_logw) && dma_wave) {
         float* yrows = sm + g.lds.yrows;
         const int Dy_ = g.Dy;
         for (int i0 = dwave * 64; i0 < NSAMP * Dy_; i0 += dthreads) {
@@ -1247,10 +1252,12 @@ __global__ __launch_bounds__(FW_THREADS) void k_dgp_forward(const FwArgs gk) {
                         if (n_enc > 0 || pre_enc) { mu = in[pidx[j] * in_str + l]; sg = softplus_f(in[pidx[j] * in_str + Lw + l] - 3.f); }
                         const float z = (j < nvalid) ? zl[l * NSAMP + j] : 0.f;
                         const float w = fmaf(z, sg, mu);                                 // layers.py:86-87
-                        float kl;
-                        if (sampled_kl) kl = -0.5f * z * z - __logf(sg) + 0.5f * w * w;  // log q(W) - log p(W), :98-100
-                        else kl = 0.5f * (sg * sg + mu * mu - 1.f) - __logf(sg);         // KL(N(mu,sg)||N(0,1)), :101-103
-                        klsum += kl;
+                        float kl = 0.f;
+                        if constexpr (!PRED) {                                           // (prediction: no local regulariser)
+                            if (sampled_kl) kl = -0.5f * z * z - __logf(sg) + 0.5f * w * w;  // log q(W) - log p(W), :98-100
+                            else kl = 0.5f * (sg * sg + mu * mu - 1.f) - __logf(sg);         // KL(N(mu,sg)||N(0,1)), :101-103
+                            klsum += kl;
+                        }
                         xout[j * XSTR + D + l] = w;
                         xin[j * XSTR + D + l] = w;                                       // completes row j for x~ below
                         if (j < nvalid) {
@@ -2409,6 +2416,46 @@ __global__ __launch_bounds__(FW_THREADS) void k_dgp_forward(const FwArgs gk) {
     // (what this tail reads of the kernel arguments, requested together: read where they are used, each field was its own scalar-cache round
     //  trip on the one path every workgroup ends with -- fourteen of them, one after the other)
     FW_REBASE();
+    if constexpr (PRED) {
+        // ---- predictive tail (iwvi_dgp_predict_density): rows are point-major, t = n S + s (row_div = S).  Per sample
+        //      l = sum_d log N(y_d; m_d, v_d + sigma^2) -> LDS; then per data point of the chunk (max, sum exp(l - max)) over the chunk's samples
+        //      of that point, one half-wave per point: that pair goes to ws slot (point + chunk) -- the slots of one point are contiguous
+        //      over the chunks that hold its samples -- and k_pred_lse_merge combines them in chunk order.  No log-weight reaches HBM.
+        const int Dy = g.Dy;
+        if (tid < nvalid) {
+            const float likv = sm[g.lds.cnt + 8];                  // (prologue)
+            const float* yrows = sm + g.lds.yrows;
+            float acc = 0.f;
+            for (int d = 0; d < Dy; ++d) {
+                const float s2 = obuf[(Dy + d) * NSAMP + tid] + likv, df = yrows[d * NSAMP + tid] - obuf[d * NSAMP + tid];
+                acc += -0.5f * 1.8378770664093453f - 0.5f * __logf(s2) - 0.5f * df * df / s2;
+            }
+            lw[tid] = acc;
+        }
+        __syncthreads();
+        constexpr int NV = (NSAMP + 31) / 32;                     // terms per lane: a point holds at most NSAMP samples of a chunk
+        float2* part = reinterpret_cast<float2*>(g.e.ws);
+        const int e = tid & 31;
+        for (int seg = tid >> 5; seg < npts; seg += FW_THREADS / 32) {     // (uniform per half-wave: the reductions stay inside it)
+            const long long n = (long long)p_first + seg;
+            const long long a0 = n * g.row_div, a1 = a0 + g.row_div;
+            const int lo = (int)((a0 > t0 ? a0 : t0) - t0), hi = (int)((a1 < t0 + nvalid ? a1 : t0 + nvalid) - t0);
+            float v[NV];
+#pragma unroll
+            for (int k = 0; k < NV; ++k) { const int i = lo + e + 32 * k; v[k] = i < hi ? lw[i] : -INFINITY; }
+            float m = v[0];
+#pragma unroll
+            for (int k = 1; k < NV; ++k) m = fmaxf(m, v[k]);
+            m = halfwave_all_max(m);
+            float ssum = 0.f;
+#pragma unroll
+            for (int k = 0; k < NV; ++k) ssum += (lo + e + 32 * k < hi) ? __expf(v[k] - m) : 0.f;
+            ssum = halfwave_all_sum(ssum);
+            if (e == 0) part[n + chunk_id] = make_float2(m, ssum);
+        }
+        fw_arrive<NS>(gk, sm, tid, chunk_id);                     // (the bound is off: only the noise counter advances)
+        return;
+    }
     const FwElboHot Eh = opaque_block(static_cast<const FwElboHot&>(g.e));
     struct TailHot { float* out_logw; unsigned long long* rng; int Dy, yrows, cnt, nchunks; };
     const TailHot th = opaque_block(TailHot{g.out_logw, g.rng_state, g.Dy, g.lds.yrows, g.lds.cnt, g.nchunks});
@@ -2827,9 +2874,26 @@ static size_t fw_plan_lds(FwArgs& a, int nsamp, int maxR, int maxP, bool stage_z
     return (size_t)o * sizeof(float);
 }
 
-int dgp_forward_impl(const iwvi_layer_desc* layers, int n_layers, const float* X, int Dx, const float* XY, int XYdim,
-                          const float* Y, int Dy, int64_t T, int64_t row_div, int64_t row_mod, float lik_variance,
-                          uint64_t seed, uint64_t* rng_state, float* out_logw, const iwvi_elbo_desc* elbo, hipStream_t stream) {
+// per data point n: combine the (max, sum exp) pairs the chunks holding its samples left in ws slots n + c, c = first .. last chunk of
+// the point, in chunk order (deterministic): log (1/S) sum_s exp(l_s)
+__global__ __launch_bounds__(256) void k_pred_lse_merge(const float2* __restrict__ part, long long N, long long S, int nsamp,
+                                                        float* __restrict__ out) {
+    const long long n = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const long long c0 = n * S / nsamp, c1 = (n * S + S - 1) / nsamp;
+    float m = -INFINITY;
+    for (long long c = c0; c <= c1; ++c) m = fmaxf(m, part[n + c].x);
+    float ssum = 0.f;
+    for (long long c = c0; c <= c1; ++c) { const float2 q = part[n + c]; ssum += q.y * expf(q.x - m); }
+    out[n] = (m == -INFINITY) ? -INFINITY : m + logf(ssum) - logf((float)S);
+}
+
+struct FwPredict { int64_t N, S; float* out_logp; void* ws; };
+
+static int dgp_forward_core(const iwvi_layer_desc* layers, int n_layers, const float* X, int Dx, const float* XY, int XYdim,
+                            const float* Y, int Dy, int64_t T, int64_t row_div, int64_t row_mod, float lik_variance,
+                            uint64_t seed, uint64_t* rng_state, float* out_logw, const iwvi_elbo_desc* elbo, hipStream_t stream,
+                            const FwPredict* pred, const float* lik_variance_dev) {
     if (T <= 0) return IWVI_OK;                         // empty batch: nothing to do
     if (!layers || n_layers <= 0 || n_layers > IWVI_MAX_STACK) { set_error("iwvi_dgp_forward: %d layers (1..%d supported)", n_layers, IWVI_MAX_STACK); return IWVI_ERR_ARG; }
     if (!X || Dx <= 0 || Dx > IWVI_MAX_D) { set_error("iwvi_dgp_forward: null X or Dx=%d out of range (1..%d)", Dx, IWVI_MAX_D); return IWVI_ERR_ARG; }
@@ -2914,7 +2978,7 @@ int dgp_forward_impl(const iwvi_layer_desc* layers, int n_layers, const float* X
             D += d.latent_dim;
         } else { set_error("iwvi_dgp_forward: unknown layer type %d", d.type); return IWVI_ERR_ARG; }
     }
-    if (out_logw) {
+    if (out_logw || pred) {
         if (layers[n_layers - 1].type != IWVI_LAYER_GP || D != Dy) { set_error("iwvi_dgp_forward: the last layer must be a GP layer with P == Dy (%d vs %d)", D, Dy); return IWVI_ERR_ARG; }
     }
     if (need_rng && !rng_state) { set_error("iwvi_dgp_forward: a layer draws its own noise but rng_state is NULL"); return IWVI_ERR_ARG; }
@@ -2963,8 +3027,9 @@ int dgp_forward_impl(const iwvi_layer_desc* layers, int n_layers, const float* X
     if (ns > FW_MAXNS) ns = FW_MAXNS;
     { const int cap = dbg_opt("IWVI_FW_MAX_NS"); if (cap > 0 && ns > cap) ns = cap; }   // development: fewer samples per workgroup than would fit
     if (ns < 1) ns = 1;
+    if (pred && !(ns & 1)) --ns;                         // the predictive variants exist for 1, 3 and 5 sub-tiles per workgroup
     size_t lds_bytes = 0;
-    for (; ns >= 1; --ns) {
+    for (; ns >= 1; ns -= pred ? 2 : 1) {
         lds_bytes = fw_plan_lds(a, 16 * ns, maxR, maxP, true, true);
         if (lds_bytes <= LDS_MAX) break;
         lds_bytes = fw_plan_lds(a, 16 * ns, maxR, maxP, true, false);
@@ -3009,6 +3074,31 @@ int dgp_forward_impl(const iwvi_layer_desc* layers, int n_layers, const float* X
     a.h.stamps = (g_stamp_buf && chunks + IWVI_MAX_STACK <= g_stamp_wgs) ? g_stamp_buf : nullptr;
     a.h.dbg_exit = g_dbg_exit;
     fw_decide_fast(a, (unsigned)chunks, 16 * ns, T);
+    if (pred) {                                          // the predictive tail (FW_MODE_PREDICT), then the per-point merge of its partials
+        a.h.lik_var_dev = lik_variance_dev;
+        a.h.e.ws = (double*)pred->ws;
+        int rc;
+        if (f64_any) {
+            g_last_variant = ns | 1 << 9 | 1 << 12;
+            rc = ns == 1 ? launch_forward<1, false, true, FW_MODE_PREDICT, true>(a, (unsigned)chunks, lds_bytes, stream)
+               : ns == 3 ? launch_forward<3, false, true, FW_MODE_PREDICT, true>(a, (unsigned)chunks, lds_bytes, stream)
+                         : launch_forward<5, false, true, FW_MODE_PREDICT, true>(a, (unsigned)chunks, lds_bytes, stream);
+        } else {
+            bool bg = false;
+            for (int i = 0; i < n_layers; ++i) if (a.L[i].type == IWVI_LAYER_GP && a.L[i].gp.nbk > 8) bg = true;
+            g_last_variant = ns | (s16_all ? 1 << 8 : 0) | (bg ? 1 << 9 : 0);
+#define FW_PRED(NS_) (s16_all ? (bg ? launch_forward<NS_, true, true, FW_MODE_PREDICT>(a, (unsigned)chunks, lds_bytes, stream)      \
+                                    : launch_forward<NS_, true, false, FW_MODE_PREDICT>(a, (unsigned)chunks, lds_bytes, stream))     \
+                              : (bg ? launch_forward<NS_, false, true, FW_MODE_PREDICT>(a, (unsigned)chunks, lds_bytes, stream)     \
+                                    : launch_forward<NS_, false, false, FW_MODE_PREDICT>(a, (unsigned)chunks, lds_bytes, stream)))
+            rc = ns == 1 ? FW_PRED(1) : ns == 3 ? FW_PRED(3) : FW_PRED(5);
+#undef FW_PRED
+        }
+        if (rc != IWVI_OK) return rc;
+        hipLaunchKernelGGL(k_pred_lse_merge, dim3((unsigned)((pred->N + 255) / 256)), dim3(256), 0, stream,
+                           (const float2*)pred->ws, (long long)pred->N, (long long)pred->S, 16 * ns, pred->out_logp);
+        return check_launch("k_pred_lse_merge");
+    }
     if (a.h.e.adj_w) {                                   // every point's K samples inside one chunk, two doubles of ws per chunk; the sums travel through ws
         if ((16 * ns) % a.h.e.K != 0 || 2 * chunks > (T + 15) / 16) {
             set_error("iwvi_dgp_forward: the fused adjoint heads need K (%d) to divide the chunk of %d samples", a.h.e.K, 16 * ns);
@@ -3080,6 +3170,13 @@ int dgp_forward_impl(const iwvi_layer_desc* layers, int n_layers, const float* X
 #undef FW_LAUNCH
 }
 
+int dgp_forward_impl(const iwvi_layer_desc* layers, int n_layers, const float* X, int Dx, const float* XY, int XYdim,
+                          const float* Y, int Dy, int64_t T, int64_t row_div, int64_t row_mod, float lik_variance,
+                          uint64_t seed, uint64_t* rng_state, float* out_logw, const iwvi_elbo_desc* elbo, hipStream_t stream) {
+    return dgp_forward_core(layers, n_layers, X, Dx, XY, XYdim, Y, Dy, T, row_div, row_mod, lik_variance, seed, rng_state, out_logw, elbo,
+                            stream, nullptr, nullptr);
+}
+
 }  // namespace iwvi
 
 using namespace iwvi;
@@ -3090,6 +3187,29 @@ extern "C" int iwvi_dgp_forward(const iwvi_layer_desc* layers, int n_layers, con
                                 float* out_logw, const iwvi_elbo_desc* elbo, void* stream) {
     return dgp_forward_impl(layers, n_layers, X, Dx, XY, XYdim, Y, Dy, T, row_div, row_mod, lik_variance, seed,
                             rng_state, out_logw, elbo, (hipStream_t)stream);
+}
+
+extern "C" size_t iwvi_dgp_predict_density_ws_bytes(int64_t N, int64_t S) {
+    if (N <= 0 || S <= 0) return 0;
+    return (size_t)(N + (N * S + 15) / 16) * 2 * sizeof(float);
+}
+
+extern "C" int iwvi_dgp_predict_density(const iwvi_layer_desc* layers, int n_layers, const float* X, int Dx, const float* Y, int Dy,
+                                        int64_t N, int64_t S, float lik_variance, const float* lik_variance_dev, uint64_t seed,
+                                        uint64_t* rng_state, float* out_logp, void* ws, void* stream) {
+    if (N < 0 || S < 1) { set_error("iwvi_dgp_predict_density: N=%lld, S=%lld (N >= 0, S >= 1)", (long long)N, (long long)S); return IWVI_ERR_ARG; }
+    if (N == 0) return IWVI_OK;
+    if (N > 0x7fffffffLL || S > 0x7fffffffLL || N * S > 0x7fffffffLL - 4096) { set_error("iwvi_dgp_predict_density: N x S = %lld x %lld rows (< 2^31)", (long long)N, (long long)S); return IWVI_ERR_ARG; }
+    if (!Y || !out_logp || !ws) { set_error("iwvi_dgp_predict_density: null Y / out_logp / ws"); return IWVI_ERR_ARG; }
+    if (Dy <= 0 || Dy > IWVI_MAX_P) { set_error("iwvi_dgp_predict_density: Dy=%d out of range (1..%d)", Dy, IWVI_MAX_P); return IWVI_ERR_ARG; }
+    if (!lik_variance_dev && !(lik_variance > 0.f)) { set_error("iwvi_dgp_predict_density: the likelihood variance must be positive"); return IWVI_ERR_ARG; }
+    for (int i = 0; i < n_layers && layers; ++i)
+        if (layers[i].type == IWVI_LAYER_LV && (layers[i].enc_W || layers[i].enc_out)) {
+            set_error("iwvi_dgp_predict_density: latent-variable layer %d has an encoder (prediction runs them in prior mode)", i); return IWVI_ERR_ARG;
+        }
+    const FwPredict p{N, S, out_logp, ws};
+    return dgp_forward_core(layers, n_layers, X, Dx, nullptr, 0, Y, Dy, N * S, S, N, lik_variance_dev ? 1.f : lik_variance, seed, rng_state,
+                            nullptr, nullptr, (hipStream_t)stream, &p, lik_variance_dev);
 }
 
 /* diagnostic (not part of the drop-in surface): register a device buffer of 128 * max_workgroups 64-bit words;

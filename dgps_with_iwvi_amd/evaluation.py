@@ -26,8 +26,10 @@ def kde_log_density(samples, y):
     return logp, sq, ms
 
 
-def evaluate(model, X_test, Y_test, num_predict_samples=2000, predict_batch_size=1000, shapiro=False):
-    """-> dict(test_loglik, test_rmse[, test_shapiro_W_median]) as the reference's ``res`` (:167-169); Y one column."""
+def evaluate(model, X_test, Y_test, num_predict_samples=2000, predict_batch_size=1000, shapiro=False, mc_loglik=False):
+    """-> dict(test_loglik, test_rmse[, test_shapiro_W_median]) as the reference's ``res`` (:167-169); Y one column.
+    ``mc_loglik``: also ``test_loglik_mc``, the mean Monte Carlo log predictive density (``model.predict_log_density`` with
+    ``num_predict_samples`` draws per point), the usual DGP test metric beside the reference's KDE estimate."""
     dev = model.X.device
     X_test = torch.as_tensor(np.asarray(X_test, dtype=np.float32), device=dev) if not isinstance(X_test, torch.Tensor) else X_test.to(dev, settings.float_type)
     Y_test = torch.as_tensor(np.asarray(Y_test, dtype=np.float32), device=dev) if not isinstance(Y_test, torch.Tensor) else Y_test.to(dev, settings.float_type)
@@ -50,4 +52,7 @@ def evaluate(model, X_test, Y_test, num_predict_samples=2000, predict_batch_size
     res = {"test_loglik": float(torch.cat(logps).double().mean()), "test_rmse": float(torch.cat(sqs).double().mean()) ** 0.5}
     if shapiro:
         res["test_shapiro_W_median"] = float(np.median(Ws))
+    if mc_loglik:
+        lp = model.predict_log_density(X_test, Y_test.reshape(N, -1), num_predict_samples, batch_size=predict_batch_size)
+        res["test_loglik_mc"] = float(lp.double().mean())
     return res

@@ -185,7 +185,8 @@ class DGP_VI:
 
     # -- fused forward ------------------------------------------------------------------------
     def _fused_forward(self, T, row_div, row_mod, lead, zs=None, sampled_kl=True, want_layers=False,
-                       want_logw=True, use_encoder=True, elbo=None, stack_from=0, want_saved=False, outputs_for=None, moments=True):
+                       want_logw=True, use_encoder=True, elbo=None, stack_from=0, want_saved=False, outputs_for=None, moments=True,
+                       X=None, Y=None, predict=None):
         """``iwvi_dgp_forward`` over the current minibatch: every layer + log-weights in one launch.
         Row t of the flattened batch reads data row (t // row_div) % row_mod.  ``elbo`` = dict(B, K, stride_b,
         stride_k, mode_vi, want_ms, K_total): also run the reduction of models.py:138-150 in the tail of the
@@ -194,7 +195,10 @@ class DGP_VI:
         starts from its samples [T, Dx+Lw] and its per-sample regulariser.
         ``outputs_for`` (with ``want_layers``): only these layers (indices into the stack) get output buffers, the others write
         nothing; ``moments=False``: no sample / mean / var rows either (only what ``want_saved`` adds) -- the natural-gradient op needs
-        the final layer's a, noise and latent moments alone."""
+        the final layer's a, noise and latent moments alone.
+        ``X`` / ``Y``: explicit inputs and targets in place of the current minibatch.  ``predict`` = dict(S, out): run
+        ``iwvi_dgp_predict_density`` instead (rows t = n S + s, latent-variable layers in prior mode: ``use_encoder=False``),
+        writing the per-point Monte Carlo log predictive density into ``out`` [N]."""
         dev = self.X.device
         layers = self.layers[stack_from:]
         n = len(layers)
@@ -209,8 +213,8 @@ class DGP_VI:
                 raise ValueError("stack_from=1 needs elbo and precompute(sample_first=...) on this minibatch")
             X = first._smp_X
         else:
-            X = _abi.dev_tensor(self.X.contiguous(), "X")
-        Y = _abi.dev_tensor(self.Y.contiguous(), "Y")
+            X = _abi.dev_tensor((self.X if X is None else X).contiguous(), "X")
+        Y = _abi.dev_tensor((self.Y if Y is None else Y).contiguous(), "Y")
         XY = self._xy_minibatch() if use_encoder and any(isinstance(l, LatentVariableLayer) for l in layers) else None
         descs = (_abi.LayerDesc * n)()
         keep, outs = [], []
@@ -257,8 +261,16 @@ class DGP_VI:
             descs[i] = d
             keep.append(k)
             outs.append(o)
-        logw = torch.empty(T, dtype=settings.float_type, device=dev) if want_logw else None
         words = self._words()
+        if predict is not None:
+            N, S, out = X.shape[0], predict["S"], predict["out"]
+            ws = torch.empty((_abi.lib().iwvi_dgp_predict_density_ws_bytes(N, S) + 3) // 4, dtype=torch.float32, device=dev)
+            lik_host, lik_dev = self.likelihood.desc_variance()
+            _abi.check(_abi.lib().iwvi_dgp_predict_density(descs, n, _abi.ptr(X), X.shape[1], _abi.ptr(Y), Y.shape[1], N, S,
+                                                           lik_host, lik_dev, settings.seed, ctypes.c_void_p(words.data_ptr() + 8),
+                                                           _abi.ptr(out), _abi.ptr(ws), _abi.stream_ptr()))
+            return None, outs, None
+        logw = torch.empty(T, dtype=settings.float_type, device=dev) if want_logw else None
         ed, red = None, None
         if elbo is not None:
             B, K = elbo["B"], elbo["K"]
@@ -397,6 +409,73 @@ class DGP_VI:
         X_tiled = X[None, :, :].expand(S, *X.shape).contiguous()       # :97
         _, means, covs, _, _ = self.propagate(X_tiled, zs=zs)
         return means[-1], covs[-1]
+
+    def predict_y(self, X, zs=None):
+        """gpflow ``GPModel.predict_y``: the likelihood's predictive mean and variance at one draw through the inner layers."""
+        return self.likelihood.predict_mean_and_var(*self._build_predict(_data(X), False, zs))
+
+    def predict_density(self, X, Y, zs=None):
+        """gpflow ``GPModel.predict_density``: log N(Y; m, v + variance) [N, Dy] at one draw through the inner layers."""
+        X = _data(X)
+        Y = _data(Y)
+        return self.likelihood.predict_density(*self._build_predict(X, False, zs), Y)
+
+    def _input_dim(self):
+        """Columns of X the stack expects: the first GP layer's input width less the latent dimensions added in front of it."""
+        lat = 0
+        for l in self.layers:
+            if isinstance(l, GPLayer):
+                return l._Z().shape[1] - lat
+            lat += l.latent_dim
+        return None
+
+    def _output_dim(self):
+        last = self.layers[-1]
+        if not isinstance(last, GPLayer):
+            return None
+        return last.kern.W.shape[0] if hasattr(last.kern, "W") else last.num_outputs
+
+    _PREDICT_ROWS = 1 << 24                          # default cap on N x S rows per launch (the forward takes < 2^31)
+
+    def predict_log_density(self, X, Y, S, zs=None, batch_size=None):
+        """Monte Carlo log predictive density [N]: log (1/S) sum_s prod_d N(y_nd; m_snd, v_snd + variance), the final layer's moments of
+        S draws through the inner layers (drawn as in ``predict_f_multisample``; ``zs``: one [S, N, dim] array or None per layer).  One
+        precompute, then per batch of ``batch_size`` points one ``iwvi_dgp_predict_density`` call (the fused forward with a predictive
+        tail, and the merge of its per-point partials): no per-layer sample, moment or log-weight reaches memory."""
+        X, Y = _data(X), _data(Y)
+        S = int(S)
+        if S < 1:
+            raise ValueError("S must be >= 1, got %d" % S)
+        if X.dim() != 2 or X.shape[1] != self._input_dim():
+            raise ValueError("X must be [N, %s], got %s" % (self._input_dim(), tuple(X.shape)))
+        Dy = self._output_dim()
+        if Y.dim() != 2 or Y.shape[0] != X.shape[0] or Y.shape[1] != Dy:
+            raise ValueError("Y must be [%d, %s], got %s" % (X.shape[0], Dy, tuple(Y.shape)))
+        N = X.shape[0]
+        zs = [None] * len(self.layers) if zs is None else list(zs)
+        if len(zs) != len(self.layers):
+            raise ValueError("zs needs one entry per layer")
+        for i, (l, z) in enumerate(zip(self.layers, zs)):
+            if isinstance(l, LatentVariableLayer) and (l.q_mu_placeholder is not None or l.q_sqrt_placeholder is not None):
+                raise ValueError("layer %d: fed latent-variable placeholders are not supported by predict_log_density" % i)
+            if z is not None:
+                w = l.latent_dim if isinstance(l, LatentVariableLayer) else l.num_outputs
+                if tuple(z.shape) != (S, N, w):
+                    raise ValueError("zs[%d] must be [S, N, %d] = %s, got %s" % (i, w, (S, N, w), tuple(z.shape)))
+        bs = batch_size or max(1, self._PREDICT_ROWS // S)
+        if bs < 1:
+            raise ValueError("batch_size must be >= 1")
+        out = torch.empty(N, dtype=settings.float_type, device=X.device)
+        if N == 0:
+            return out
+        self.precompute()
+        for lo in range(0, N, bs):
+            hi = min(N, lo + bs)
+            nb = hi - lo
+            zb = [None if z is None else _data(z)[:, lo:hi].transpose(0, 1).reshape(nb * S, -1) for z in zs]   # point-major rows n S + s
+            self._fused_forward(nb * S, S, nb, (nb * S,), zs=zb, want_logw=False, use_encoder=False,
+                                X=X[lo:hi], Y=Y[lo:hi], predict=dict(S=S, out=out[lo:hi]))
+        return out
 
     def predict_y_samples(self, X, S, zs=None, z_y=None):
         X = _data(X)

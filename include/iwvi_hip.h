@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define IWVI_ABI_VERSION 18
+#define IWVI_ABI_VERSION 19
 
 enum {
     IWVI_OK = 0,
@@ -574,6 +574,26 @@ int iwvi_gauss_kl(const float* q_mu, const float* q_sqrt, int M, int R, double* 
  * Fmu, Fvar, out [T, Dy].  (The hot path never calls this: the expectation is fused into iwvi_dgp_forward's tail.) */
 int iwvi_gaussian_var_exp(const float* Fmu, const float* Fvar, const float* Y, float lik_variance,
                           int64_t T, int Dy, int64_t row_div, int64_t row_mod, float* out, void* stream);
+
+/* gpflow 1.x Gaussian.predict_density / Gaussian.logp as one callable:
+ *   out[t, d] = -1/2 log 2pi - 1/2 log s - 1/2 (Y[row(t), d] - Fmu[t, d])^2 / s,  s = Fvar[t, d] + variance  (Fvar == NULL: s = variance, logp)
+ * with row(t) as in iwvi_gaussian_var_exp; variance = *lik_variance_dev when that device scalar is given, else lik_variance.  Fmu, Fvar, out [T, Dy]. */
+int iwvi_gaussian_log_density(const float* Fmu, const float* Fvar, const float* Y, float lik_variance, const float* lik_variance_dev,
+                              int64_t T, int Dy, int64_t row_div, int64_t row_mod, float* out, void* stream);
+
+/* Monte Carlo log predictive density of the layer stack (ABI 19), the doubly-stochastic DGP's predict_density(X, Y, S):
+ *   out_logp[n] = log (1/S) sum_s prod_d N(Y[n, d]; m_snd, v_snd + variance)
+ * where (m_snd, v_snd) are the final layer's marginal moments of draw s through the inner layers (marginal samples, latent-variable
+ * layers in prior mode: their enc_W / enc_out must be NULL).  One iwvi_dgp_forward launch over the N x S rows t = n S + s (row_div = S:
+ * layer noise, injected or drawn, is indexed by that row) with a predictive tail -- no per-layer output, no per-sample log-weight reaches
+ * memory -- and one small launch that merges each point's per-workgroup (max, sum exp) partials in a fixed order (deterministic).
+ * X [N, Dx], Y [N, Dy] (Dy = the final layer's P), ws: iwvi_dgp_predict_density_ws_bytes(N, S) bytes of device memory, no initial
+ * contents.  variance = *lik_variance_dev when given.  rng_state as in iwvi_dgp_forward (its step word advances once per call).
+ * N x S < 2^31 - 4096. */
+size_t iwvi_dgp_predict_density_ws_bytes(int64_t N, int64_t S);
+int iwvi_dgp_predict_density(const iwvi_layer_desc* layers_host, int n_layers, const float* X, int Dx, const float* Y, int Dy,
+                             int64_t N, int64_t S, float lik_variance, const float* lik_variance_dev, uint64_t seed,
+                             uint64_t* rng_state, float* out_logp, void* ws, void* stream);
 
 /* white=False (temp_workaround.py:63-65: "another backsubstitution in the unwhitened case").  The unwhitened
  * q(u) = N(f, q_sqrt q_sqrt^T) gives the same conditional as the whitened one with f_w = Lm^-1 f and
