@@ -7,7 +7,10 @@ all GP layers, Gaussian variational expectations, log-sum-exp over K, scaled sum
 one minibatch already resident in HBM.  Default workload = BASELINE.json configs[2] (the config the
 metric is quoted on): 2-layer DGP + LatentVariableLayer, M=128, K=20, batch=1024, Dx=8, Dy=1, R=5.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config 1..4] [--shard k|n]
+  python bench.py [--gpus N --steps K --warmup W] [--config 1..4] [--shard k|n] [--full]
+      a plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line; --full adds everything else it
+      measures after the timed region (the SURVEY.md section 8(d) median, the dominant kernel's roofline, the fp32 stage-2 path, two
+      evaluations in flight, the CPU baselines, the training leg) and, before it, the HIP_FORCE_DEV_KERNARG=0 child run
       --gpus N > 1 with no WORLD_SIZE in the environment: this process starts the N rank processes itself (launch_ranks:
       before anything touches the GPU), relays rank 0's JSON line and exits with the first non-zero rank's code
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...      (the same ranks from a launcher)
@@ -449,7 +452,7 @@ def no_dev_kernarg_leg(args):
     default when the package has not been imported before HIP initialises), started before this process touches the GPU."""
     env = dict(os.environ, HIP_FORCE_DEV_KERNARG="0", IWVI_BENCH_CHILD="1")
     cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--config", str(args.config),
-           "--no-cpu-baseline", "--no-train-leg", "--median-iters", "0", "--no-kernarg-leg"]
+           "--full", "--no-cpu-baseline", "--no-train-leg", "--median-iters", "0", "--no-kernarg-leg"]
     try:
         p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
         line = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -584,6 +587,11 @@ def main():
                          "instead of every rank drawing K of its own (weak scaling, the default)")
     ap.add_argument("--batch", type=int, default=None, help="override the config's minibatch size (plumbing tests; not a BASELINE workload)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a hipGraph")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the HIP_FORCE_DEV_KERNARG=0 child run, the hipEvent median protocol, the dominant kernel's roofline "
+                         "(GEMM-phase MFMA utilisation, L2 operand stream), the fp32 stage-2 path, two evaluations in flight, the CPU baselines and "
+                         "the training leg, each switched off by its own --no-* / --median-iters 0 as before.  Without it the run does only "
+                         "what the headline needs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-train-leg", action="store_true", help="skip the (informational) training-step timing")
@@ -637,7 +645,7 @@ def main():
         dist.destroy_process_group()
         return
     kernarg_leg = None
-    if world == 1 and not args.no_kernarg_leg and not args.no_train_leg and os.environ.get("IWVI_BENCH_CHILD") != "1" \
+    if args.full and world == 1 and not args.no_kernarg_leg and not args.no_train_leg and os.environ.get("IWVI_BENCH_CHILD") != "1" \
             and os.environ.get("HIP_FORCE_DEV_KERNARG") == "1":
         kernarg_leg = no_dev_kernarg_leg(args)                   # (before this process's first GPU call)
     if not torch.cuda.is_available():
@@ -844,7 +852,7 @@ def main():
     # ---- SURVEY.md section 8(d) protocol: median of >= 50 hipEvent-timed iterations, one complete evaluation per iteration
     #      (own graph of 1 evaluation: precompute + fused forward; fresh device-drawn noise every replay) ------------------
     med = None
-    if world == 1 and args.median_iters > 0:
+    if args.full and world == 1 and args.median_iters > 0:
         s3 = torch.cuda.Stream(device=dev)
         s3.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s3):
@@ -882,48 +890,49 @@ def main():
     # ---- dominant kernel: the fused forward (all layers), HIP events around a graph of back-to-back launches
     tot_flops, _ = f_alg_model(spec)
     dom_flops = tot_flops * B * K
-    model.precompute(with_encoders=True)
-    NREP = 20
-    fwd = lambda: model._fused_forward(B * K, K, B, (B, K), elbo=dict(B=B, K=K, stride_b=K, stride_k=1, mode_vi=False))
-    fwd()
-    torch.cuda.synchronize()
-    s2 = torch.cuda.Stream(device=dev)
-    s2.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s2):
-        fwd()
-        g2 = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g2, stream=s2, capture_error_mode="thread_local"):
-            for _ in range(NREP):
-                keep_logw = fwd()
-    torch.cuda.current_stream().wait_stream(s2)
-    torch.cuda.synchronize()
-    for _ in range(3):
-        g2.replay()
-    torch.cuda.synchronize()
-    reps = max(5, args.steps // NREP)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
-    for a, b in evs:
-        a.record()
-        g2.replay()
-        b.record()
-    torch.cuda.synchronize()
-    dom_ms = float(np.median([a.elapsed_time(b) for a, b in evs])) / NREP
-    achieved = dom_flops / (dom_ms * 1e-3)
-    try:                                                     # (read now: the variant the timed launches took)
-        l2_stream = l2_operand_stream(spec, B * K, dom_ms)
-    except Exception as e:                                   # informational
-        l2_stream = {"error": "%s: %s" % (type(e).__name__, e)}
     gemm_util = None
-    if world == 1:
-        try:
-            gemm_util = gemm_phase_mfma_util(model, spec, B, K)
-        except Exception as e:                                   # (diagnostic stamps: must not take the headline line down)
-            gemm_util = {"error": "%s: %s" % (type(e).__name__, e)}
+    if args.full:
+        model.precompute(with_encoders=True)
+        NREP = 20
+        fwd = lambda: model._fused_forward(B * K, K, B, (B, K), elbo=dict(B=B, K=K, stride_b=K, stride_k=1, mode_vi=False))
+        fwd()
+        torch.cuda.synchronize()
+        s2 = torch.cuda.Stream(device=dev)
+        s2.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s2):
+            fwd()
+            g2 = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g2, stream=s2, capture_error_mode="thread_local"):
+                for _ in range(NREP):
+                    keep_logw = fwd()
+        torch.cuda.current_stream().wait_stream(s2)
+        torch.cuda.synchronize()
+        for _ in range(3):
+            g2.replay()
+        torch.cuda.synchronize()
+        reps = max(5, args.steps // NREP)
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+        for a, b in evs:
+            a.record()
+            g2.replay()
+            b.record()
+        torch.cuda.synchronize()
+        dom_ms = float(np.median([a.elapsed_time(b) for a, b in evs])) / NREP
+        achieved = dom_flops / (dom_ms * 1e-3)
+        try:                                                     # (read now: the variant the timed launches took)
+            l2_stream = l2_operand_stream(spec, B * K, dom_ms)
+        except Exception as e:                                   # informational
+            l2_stream = {"error": "%s: %s" % (type(e).__name__, e)}
+        if world == 1:
+            try:
+                gemm_util = gemm_phase_mfma_util(model, spec, B, K)
+            except Exception as e:                               # (diagnostic stamps: must not take the headline line down)
+                gemm_util = {"error": "%s: %s" % (type(e).__name__, e)}
 
     # ---- the same evaluation with the fp32-MFMA stage 2 (iwvi_layer_desc.flags & IWVI_LAYER_F32_STAGE2: a per-call flag), so that the
     #      pure-fp32 figure is observed in the same run, next to the split-f16 default
     fp32_path = None
-    if world == 1 and not settings.fw_f32_stage2:
+    if args.full and world == 1 and not settings.fw_f32_stage2:
         settings.fw_f32_stage2 = True
         try:
             s4 = torch.cuda.Stream(device=dev)
@@ -955,7 +964,7 @@ def main():
     # independent minibatches gets, and the head-room an overlapped single evaluation is after.  A training
     # step cannot do this (its next parameters depend on this step's gradient), which is why the headline stays one evaluation at a time.
     two_in_flight = None
-    if world == 1 and os.environ.get("IWVI_BENCH_TWO_IN_FLIGHT", "1") != "0" and not args.no_train_leg:
+    if args.full and world == 1 and os.environ.get("IWVI_BENCH_TWO_IN_FLIGHT", "1") != "0" and not args.no_train_leg:
         try:
             models2 = [model, synthetic.build_model(spec, dev, num_samples=K_local)]
             streams2 = [torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)]
@@ -1000,8 +1009,8 @@ def main():
     # need their own rocprofv3 passes and cannot be read live); null for any other workload
     traffic, traffic_src, pmc = None, None, {}
     try:
-        tj = json.load(open(os.path.join(ROOT, "profiles", "traffic_latest.json")))
-        if args.config == 2 and world == 1:
+        if args.full and args.config == 2 and world == 1:
+            tj = json.load(open(os.path.join(ROOT, "profiles", "traffic_latest.json")))
             traffic, traffic_src = tj["hbm_bytes"], tj["source"]
             pmc = {k: tj[k] for k in ("mfma_busy_frac", "mfma_issued_f32_tflops", "mfma_issued_f16_tflops", "mfma_pipe_frac",
                                       "kernel_avg_us_rocprof", "pmc_profile_of_commit") if k in tj}
@@ -1025,7 +1034,7 @@ def main():
             # stage 2 (u_r = L_r^T a, mean = q_mu^T a) enter the matrix cores as x = h1 + h2, two f16 planes = 22 mantissa bits, with
             # power-of-two scales -- as accurate as the fp32 MFMA it replaces (tests/test_gpu_split16.py; IWVI_FW_F32_STAGE2=1 switches back)
             "dtype_note": ("fp32 data and accumulate, fp64 factorisation; stage-2 matrix operands as split f16 (h1 + h2, 22 mantissa bits) "
-                           "unless IWVI_LAYER_F32_STAGE2 is set on a layer (see fp32_path)" if not settings.fw_f32_stage2 else "fp32 MFMA stage 2 (IWVI_LAYER_F32_STAGE2)"),
+                           "unless IWVI_LAYER_F32_STAGE2 is set on a layer (see fp32_path of a --full line)" if not settings.fw_f32_stage2 else "fp32 MFMA stage 2 (IWVI_LAYER_F32_STAGE2)"),
             "config": {"workload": "BASELINE.json configs[%d]: %s; Dx=8, Dy=1, inner layers G5 (R=5, P=8), RBF-ARD, "
                                    "per-step Gram+Cholesky included, noise drawn on device%s" % (
                                        args.config, spec["name"], "" if not args.batch else " -- batch overridden (--batch %d): a plumbing run, not the BASELINE workload" % args.batch),
@@ -1039,15 +1048,17 @@ def main():
             # evaluations it carries
             "exchange_ms": exchange_ms, "evaluations_per_exchange": (spg if xch is not None else None),
             "host_enqueue_ms_per_step": t_enqueued / args.steps * 1e3,
+            "full": bool(args.full),
+        }
+        if args.full:
             # achieved = algorithmic FLOP / s of the dominant kernel.  peak = the ceiling of THIS instruction mix: the fp32-MFMA part of the
             # algorithm at the fp32-MFMA peak, the split-f16 part (three f16 MFMA FLOPs per algorithmic FLOP) at a third of the f16 peak --
             # so frac <= 1 whatever the shape.  frac_fp32_equivalent (algorithmic / fp32-MFMA peak) is last round's number; it passes 1
             # where stage 2 dominates (M >= 256) and is kept only for comparison.  bound: from the counters of the committed profile.
-            "roofline": roofline_object(achieved, dom_flops, dom_ms, spec, traffic, traffic_src, pmc),
-        }
-        if gemm_util is not None:
-            res["roofline"]["gemm_phase_mfma_util"] = gemm_util
-        res["roofline"]["l2_operand_stream"] = l2_stream
+            res["roofline"] = roofline_object(achieved, dom_flops, dom_ms, spec, traffic, traffic_src, pmc)
+            if gemm_util is not None:
+                res["roofline"]["gemm_phase_mfma_util"] = gemm_util
+            res["roofline"]["l2_operand_stream"] = l2_stream
         f32p, f16p = f_alg_split(spec, settings.fw_f32_stage2)
         mix_peak = (f32p + f16p) / (f32p / PEAK_MFMA_F32 + f16p / (PEAK_MFMA_F16 / 3.0))
         res["model_frac_of_mfma_peak"] = res["value"] / world * tot_flops / mix_peak          # the WHOLE step (both launches) against the mix ceiling
@@ -1066,14 +1077,14 @@ def main():
             res.update({"ms_per_step_median": med["ms_per_step_median"], "median_protocol": med})
         if check is not None:
             res["check"] = check
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(spec, args.cpu_seconds)
             try:                                                 # float32 on the CPU: the precision the device path computes in
                 res["cpu_baseline_fp32"] = cpu_baseline(spec, args.cpu_seconds * 0.5, torch.float32)
             except Exception as e:                               # (a float32 Cholesky of K_uu + 1e-6 I may fail on the host)
                 res["cpu_baseline_fp32"] = {"error": "%s: %s" % (type(e).__name__, e)}
             res["gpu_over_cpu"] = res["value"] / res["cpu_baseline"]["value"]
-        if world == 1 and not args.no_train_leg:
+        if args.full and world == 1 and not args.no_train_leg:
             res["training_step"] = training_leg(model, B * K, flops_forward=tot_flops * B * K)
         if sharded_train is not None:
             res["training_step"] = sharded_train

@@ -6,7 +6,7 @@ cp $D/libiwvi_hip.so /tmp/lib_keep.so
 for r in $(seq 1 $R); do
   for v in "$@"; do
     cp $D/$v $D/libiwvi_hip.so
-    python bench.py --config $C --steps 20 --warmup 5 --no-cpu-baseline --no-train-leg --median-iters 0 2>/dev/null | python -c "
+    python bench.py --config $C --steps 20 --warmup 5 --full --no-cpu-baseline --no-train-leg --median-iters 0 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.read().strip().splitlines()[-1])
 g=r['roofline'].get('gemm_phase_mfma_util') or {}

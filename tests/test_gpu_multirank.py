@@ -75,7 +75,7 @@ def test_bench_two_ranks_one_exchange_per_evaluation(gpu_device):
 
 
 def test_bench_single_rank_line_has_the_contract_fields(gpu_device):
-    res = _run_bench(1, "k", extra=("--median-iters", "50"))
+    res = _run_bench(1, "k", extra=("--full", "--median-iters", "50"))
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "ms_per_step_median", "n_ranks_seen"):
         assert k in res, k
@@ -93,6 +93,25 @@ def test_bench_single_rank_line_has_the_contract_fields(gpu_device):
     l2 = r["l2_operand_stream"]
     assert l2["workgroups"] * l2["bytes_per_workgroup"] == l2["bytes_per_launch"] and 0.0 < l2["TB_per_s"] < 20.0 and l2["samples_per_workgroup"] % 16 == 0
     # (the `no_dev_kernarg` leg -- the same loop in a fresh process without device-resident kernel arguments -- belongs to the full line only)
+
+
+def test_bench_plain_line_is_the_headline_only(gpu_device):
+    """``bench.py --gpus 1 --steps N --warmup W`` without --full sets up, warms up, times the N steps and prints the line: the contract fields,
+    and none of what --full measures in runs of its own (the device kernel-argument child, the median protocol, the roofline, the fp32 path,
+    two evaluations in flight, the CPU baselines, the training leg)."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+                       env=_bare_env(), capture_output=True, text=True, cwd=ROOT, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    res = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config", "elbo"):
+        assert k in res, k
+    assert res["full"] is False and res["n_gpus"] == 1 and res["steps"] == 20 and res["warmup"] == 5
+    assert res["value"] > 0 and res["ms_per_step"] > 0 and np.isfinite(res["elbo"])
+    for k in ("no_dev_kernarg", "ms_per_step_median", "median_protocol", "roofline", "fp32_path", "two_in_flight", "cpu_baseline",
+              "cpu_baseline_fp32", "gpu_over_cpu", "training_step"):
+        assert k not in res, k
 
 
 @pytest.mark.parametrize("shard", ["k", "n"])
