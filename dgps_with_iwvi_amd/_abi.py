@@ -216,6 +216,10 @@ PROTOTYPES = {
     "iwvi_dgp_predict_density_ws_bytes": (c_size_t, [c_int64, c_int64]),
     "iwvi_dgp_predict_density": (c_int, [ctypes.POINTER(LayerDesc), c_int, c_void_p, c_int, c_void_p, c_int, c_int64, c_int64,
                                          c_float, c_void_p, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "iwvi_dgp_predict_samples": (c_int, [ctypes.POINTER(LayerDesc), c_int, c_void_p, c_int, c_int, c_int64, c_int64,
+                                         c_float, c_void_p, c_void_p, ctypes.c_uint64, c_void_p, c_void_p, c_void_p]),
+    "iwvi_sample_stats": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "iwvi_unwhiten": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "iwvi_fill_normal": (c_int, [c_void_p, c_int64, ctypes.c_uint64, ctypes.c_uint64, c_void_p]),
     "iwvi_fill_normal_dev": (c_int, [c_void_p, c_int64, ctypes.c_uint64, c_void_p, c_void_p]),

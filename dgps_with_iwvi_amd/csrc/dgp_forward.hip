@@ -864,12 +864,19 @@ __device__ __forceinline__ void f64_solve(const FwHot& G, const double* Linv, co
 // LEAN_MODE = FW_MODE_PREDICT: the general layer loop with the predictive tail (iwvi_dgp_predict_density) in place of the bound's: per sample
 // sum_d log N(y; m, v + sigma^2), per data point (max, sum exp) over the chunk's samples of that point -> the ws partials k_pred_lse_merge finishes
 constexpr int FW_MODE_PREDICT = 3;
+// LEAN_MODE = FW_MODE_SAMPLE: the same launch shape with a sampling tail (iwvi_dgp_predict_samples): y = m + sqrt(v + sigma^2) eps per row and
+// output column, eps read from the caller's z_y or drawn from noise stream FW_STREAM_Y -- no layer uses that index (layer_base + layer <
+// 2 IWVI_MAX_STACK), so the layers' draws are those of the same launch without the tail
+constexpr int FW_MODE_SAMPLE = 4;
+constexpr int FW_STREAM_Y = 255;
+static_assert(FW_STREAM_Y >= 2 * IWVI_MAX_STACK, "the sampling tail's noise stream must not be a layer's");
 
 template <int NS, bool S16, bool BIG, int LEAN_MODE = 0, bool F64 = false>
 __global__ __launch_bounds__(FW_THREADS) void k_dgp_forward(const FwArgs gk) {
-    static_assert(!F64 || (!S16 && BIG && (LEAN_MODE == 0 || LEAN_MODE == FW_MODE_PREDICT)), "the float64 stage-1 variants: fp32 stage 2, every solve form, no compiled-in shapes");
+    static_assert(!F64 || (!S16 && BIG && (LEAN_MODE == 0 || LEAN_MODE == FW_MODE_PREDICT || LEAN_MODE == FW_MODE_SAMPLE)), "the float64 stage-1 variants: fp32 stage 2, every solve form, no compiled-in shapes");
     constexpr int NSAMP = 16 * NS;
     constexpr bool PRED = LEAN_MODE == FW_MODE_PREDICT;
+    constexpr bool SAMP = LEAN_MODE == FW_MODE_SAMPLE;
     constexpr bool SHP = LEAN_MODE == 1 || LEAN_MODE == 2;     // the headline stack's shapes and sources compiled in (all RBF, M = 128, D <= 10, operands staged, encoders
                                              // precomputed, noise drawn here, whole chunks): mode 1 and mode 2
     constexpr bool LEAN = LEAN_MODE == 1;    // ... and the bound's own evaluation: no per-layer outputs, the packed arrival, the half-wave tail.
@@ -1253,7 +1260,7 @@ __global__ __launch_bounds__(FW_THREADS) void k_dgp_forward(const FwArgs gk) {
                         const float z = (j < nvalid) ? zl[l * NSAMP + j] : 0.f;
                         const float w = fmaf(z, sg, mu);                                 // layers.py:86-87
                         float kl = 0.f;
-                        if constexpr (!PRED) {                                           // (prediction: no local regulariser)
+                        if constexpr (!PRED && !SAMP) {                                  // (prediction: no local regulariser)
                             if (sampled_kl) kl = -0.5f * z * z - __logf(sg) + 0.5f * w * w;  // log q(W) - log p(W), :98-100
                             else kl = 0.5f * (sg * sg + mu * mu - 1.f) - __logf(sg);         // KL(N(mu,sg)||N(0,1)), :101-103
                             klsum += kl;
@@ -2416,6 +2423,29 @@ __global__ __launch_bounds__(FW_THREADS) void k_dgp_forward(const FwArgs gk) {
     // (what this tail reads of the kernel arguments, requested together: read where they are used, each field was its own scalar-cache round
     //  trip on the one path every workgroup ends with -- fourteen of them, one after the other)
     FW_REBASE();
+    if constexpr (SAMP) {
+        // ---- sampling tail (iwvi_dgp_predict_samples): rows are point-major as below, so out[t Dy + d] is [N, S, Dy] with a point's S samples
+        //      contiguous; consecutive threads write consecutive words.  The output and z_y ride in the bound's unused slots (e.ms, e.logp).
+        const int Dy = g.Dy;
+        const float likv = sm[g.lds.cnt + 8];                      // (prologue)
+        float* out = g.e.ms;
+        const float* zy = g.e.logp;
+        const float rcp = 1.0f / (float)Dy;
+        for (int idx = tid; idx < nvalid * Dy; idx += FW_THREADS) {
+            const int j = div_small(idx, rcp), d = idx - j * Dy;
+            float eps;
+            if (zy) eps = zy[(size_t)t0 * Dy + idx];
+            else {
+                float v4[4];
+                draw_normal4(g.seed, step, FW_STREAM_Y, t0 + j, d >> 2, v4);
+                const int e = d & 3;
+                eps = e == 0 ? v4[0] : e == 1 ? v4[1] : e == 2 ? v4[2] : v4[3];
+            }
+            out[(size_t)t0 * Dy + idx] = obuf[d * NSAMP + j] + sqrtf(obuf[(Dy + d) * NSAMP + j] + likv) * eps;
+        }
+        fw_arrive<NS>(gk, sm, tid, chunk_id);                     // (the bound is off: only the noise counter advances)
+        return;
+    }
     if constexpr (PRED) {
         // ---- predictive tail (iwvi_dgp_predict_density): rows are point-major, t = n S + s (row_div = S).  Per sample
         //      l = sum_d log N(y_d; m_d, v_d + sigma^2) -> LDS; then per data point of the chunk (max, sum exp(l - max)) over the chunk's samples
@@ -2888,7 +2918,7 @@ __global__ __launch_bounds__(256) void k_pred_lse_merge(const float2* __restrict
     out[n] = (m == -INFINITY) ? -INFINITY : m + logf(ssum) - logf((float)S);
 }
 
-struct FwPredict { int64_t N, S; float* out_logp; void* ws; };
+struct FwPredict { int64_t N, S; float* out_logp; void* ws; float* out_y; const float* z_y; };   // out_y: the sampling tail (FW_MODE_SAMPLE) instead
 
 static int dgp_forward_core(const iwvi_layer_desc* layers, int n_layers, const float* X, int Dx, const float* XY, int XYdim,
                             const float* Y, int Dy, int64_t T, int64_t row_div, int64_t row_mod, float lik_variance,
@@ -3074,6 +3104,26 @@ static int dgp_forward_core(const iwvi_layer_desc* layers, int n_layers, const f
     a.h.stamps = (g_stamp_buf && chunks + IWVI_MAX_STACK <= g_stamp_wgs) ? g_stamp_buf : nullptr;
     a.h.dbg_exit = g_dbg_exit;
     fw_decide_fast(a, (unsigned)chunks, 16 * ns, T);
+    if (pred && pred->out_y) {                           // the sampling tail (FW_MODE_SAMPLE): one launch, nothing to merge
+        a.h.lik_var_dev = lik_variance_dev;
+        a.h.e.ms = pred->out_y;
+        a.h.e.logp = const_cast<float*>(pred->z_y);
+        if (f64_any) {
+            g_last_variant = ns | 1 << 9 | 1 << 12;
+            return ns == 1 ? launch_forward<1, false, true, FW_MODE_SAMPLE, true>(a, (unsigned)chunks, lds_bytes, stream)
+                 : ns == 3 ? launch_forward<3, false, true, FW_MODE_SAMPLE, true>(a, (unsigned)chunks, lds_bytes, stream)
+                           : launch_forward<5, false, true, FW_MODE_SAMPLE, true>(a, (unsigned)chunks, lds_bytes, stream);
+        }
+        bool bg = false;
+        for (int i = 0; i < n_layers; ++i) if (a.L[i].type == IWVI_LAYER_GP && a.L[i].gp.nbk > 8) bg = true;
+        g_last_variant = ns | (s16_all ? 1 << 8 : 0) | (bg ? 1 << 9 : 0);
+#define FW_SAMP(NS_) (s16_all ? (bg ? launch_forward<NS_, true, true, FW_MODE_SAMPLE>(a, (unsigned)chunks, lds_bytes, stream)      \
+                                    : launch_forward<NS_, true, false, FW_MODE_SAMPLE>(a, (unsigned)chunks, lds_bytes, stream))     \
+                              : (bg ? launch_forward<NS_, false, true, FW_MODE_SAMPLE>(a, (unsigned)chunks, lds_bytes, stream)     \
+                                    : launch_forward<NS_, false, false, FW_MODE_SAMPLE>(a, (unsigned)chunks, lds_bytes, stream)))
+        return ns == 1 ? FW_SAMP(1) : ns == 3 ? FW_SAMP(3) : FW_SAMP(5);
+#undef FW_SAMP
+    }
     if (pred) {                                          // the predictive tail (FW_MODE_PREDICT), then the per-point merge of its partials
         a.h.lik_var_dev = lik_variance_dev;
         a.h.e.ws = (double*)pred->ws;
@@ -3207,8 +3257,27 @@ extern "C" int iwvi_dgp_predict_density(const iwvi_layer_desc* layers, int n_lay
         if (layers[i].type == IWVI_LAYER_LV && (layers[i].enc_W || layers[i].enc_out)) {
             set_error("iwvi_dgp_predict_density: latent-variable layer %d has an encoder (prediction runs them in prior mode)", i); return IWVI_ERR_ARG;
         }
-    const FwPredict p{N, S, out_logp, ws};
+    const FwPredict p{N, S, out_logp, ws, nullptr, nullptr};
     return dgp_forward_core(layers, n_layers, X, Dx, nullptr, 0, Y, Dy, N * S, S, N, lik_variance_dev ? 1.f : lik_variance, seed, rng_state,
+                            nullptr, nullptr, (hipStream_t)stream, &p, lik_variance_dev);
+}
+
+extern "C" int iwvi_dgp_predict_samples(const iwvi_layer_desc* layers, int n_layers, const float* X, int Dx, int Dy, int64_t N, int64_t S,
+                                        float lik_variance, const float* lik_variance_dev, const float* z_y, uint64_t seed,
+                                        uint64_t* rng_state, float* out_y, void* stream) {
+    if (N < 0 || S < 1) { set_error("iwvi_dgp_predict_samples: N=%lld, S=%lld (N >= 0, S >= 1)", (long long)N, (long long)S); return IWVI_ERR_ARG; }
+    if (N == 0) return IWVI_OK;
+    if (N > 0x7fffffffLL || S > 0x7fffffffLL || N * S > 0x7fffffffLL - 4096) { set_error("iwvi_dgp_predict_samples: N x S = %lld x %lld rows (< 2^31)", (long long)N, (long long)S); return IWVI_ERR_ARG; }
+    if (!out_y) { set_error("iwvi_dgp_predict_samples: null out_y"); return IWVI_ERR_ARG; }
+    if (Dy <= 0 || Dy > IWVI_MAX_P) { set_error("iwvi_dgp_predict_samples: Dy=%d out of range (1..%d)", Dy, IWVI_MAX_P); return IWVI_ERR_ARG; }
+    if (!lik_variance_dev && !(lik_variance > 0.f)) { set_error("iwvi_dgp_predict_samples: the likelihood variance must be positive"); return IWVI_ERR_ARG; }
+    if (!z_y && !rng_state) { set_error("iwvi_dgp_predict_samples: without z_y the tail draws its own noise but rng_state is NULL"); return IWVI_ERR_ARG; }
+    for (int i = 0; i < n_layers && layers; ++i)
+        if (layers[i].type == IWVI_LAYER_LV && (layers[i].enc_W || layers[i].enc_out)) {
+            set_error("iwvi_dgp_predict_samples: latent-variable layer %d has an encoder (prediction runs them in prior mode)", i); return IWVI_ERR_ARG;
+        }
+    const FwPredict p{N, S, nullptr, nullptr, out_y, z_y};
+    return dgp_forward_core(layers, n_layers, X, Dx, nullptr, 0, nullptr, Dy, N * S, S, N, lik_variance_dev ? 1.f : lik_variance, seed, rng_state,
                             nullptr, nullptr, (hipStream_t)stream, &p, lik_variance_dev);
 }
 

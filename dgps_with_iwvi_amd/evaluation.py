@@ -4,7 +4,13 @@ The reference walks the test set one point at a time: ``predict_y_samples(x, num
 ``sklearn.neighbors.KernelDensity`` with Silverman's bandwidth fitted to the samples, its log density at y, the squared
 error of the sample mean (and a Shapiro-Wilk statistic of the samples, a diagnostic).  Here ``predict_y_samples`` runs on
 batches of test points (the layer kernels; prior-mode latent-variable layers, layers.py:73-81) and
-``iwvi_kde_loglik`` evaluates every point's estimate in one launch."""
+``iwvi_kde_loglik`` evaluates every point's estimate in one launch.
+
+``evaluate(on_device=True)`` keeps the whole loop on the device: ``predict_y_samples_fused`` (the fused forward with a sampling tail)
+and per batch one ``iwvi_sample_stats`` launch -- a sort of each point's samples in LDS, then the KDE, the squared error, the
+Shapiro-Wilk W and any quantiles from it -- with one read-back at the end."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -26,10 +32,127 @@ def kde_log_density(samples, y):
     return logp, sq, ms
 
 
-def evaluate(model, X_test, Y_test, num_predict_samples=2000, predict_batch_size=1000, shapiro=False, mc_loglik=False):
+_SW_C1 = (0.0, 0.221157, -0.147981, -2.071190, 4.434685, -2.706056)      # Royston (1992), the polynomials of the two leading coefficients
+_SW_C2 = (0.0, 0.042981, -0.293762, -1.752461, 5.682633, -3.582633)
+MAX_SAMPLES = 16384                                                      # iwvi_sample_stats: one point's samples sorted in 64 KiB of LDS
+
+
+def shapiro_coefficients(S):
+    """The S // 2 coefficients a_i of the Shapiro-Wilk statistic W = (sum_i a_i (x_(S+1-i) - x_(i)))^2 / sum_i (x_i - mean)^2 by
+    Royston's approximation (Applied Statistics algorithm AS R94), float64, host side: normal scores m_i = Phi^-1((i - 3/8) / (S + 1/4)),
+    the two leading coefficients corrected by polynomials in S^-1/2 (only the first for S = 4, 5), the rest m_i rescaled so that the
+    squares sum to one; S = 3 (and the degenerate S = 2) has the single exact coefficient sqrt(1/2)."""
+    S = int(S)
+    if S < 2 or S > MAX_SAMPLES:
+        raise ValueError("S=%d out of range (2..%d)" % (S, MAX_SAMPLES))
+    if S <= 3:
+        return np.array([np.sqrt(0.5)])
+    from statistics import NormalDist
+    nd = NormalDist()
+    h = S // 2
+    m = np.array([nd.inv_cdf((i - 0.375) / (S + 0.25)) for i in range(1, h + 1)], dtype=np.float64)   # (negative: the lower half)
+    summ2 = 2.0 * float(np.dot(m, m))
+    ssumm2, rsn = np.sqrt(summ2), 1.0 / np.sqrt(S)
+    a = np.empty(h, dtype=np.float64)
+    a1 = np.polyval(_SW_C1[::-1], rsn) - m[0] / ssumm2
+    if S > 5:
+        a2 = np.polyval(_SW_C2[::-1], rsn) - m[1] / ssumm2
+        fac = np.sqrt((summ2 - 2.0 * m[0] ** 2 - 2.0 * m[1] ** 2) / (1.0 - 2.0 * a1 ** 2 - 2.0 * a2 ** 2))
+        a[:] = -m / fac
+        a[0], a[1] = a1, a2
+    else:
+        fac = np.sqrt((summ2 - 2.0 * m[0] ** 2) / (1.0 - 2.0 * a1 ** 2))
+        a[:] = -m / fac
+        a[0] = a1
+    return a
+
+
+_sw_cache = {}
+
+
+def _shapiro_coefficients_dev(S, dev):
+    key = (int(S), str(dev))
+    if key not in _sw_cache:
+        _sw_cache[key] = torch.as_tensor(shapiro_coefficients(S), dtype=torch.float64, device=dev)
+    return _sw_cache[key]
+
+
+def _check_probs(quantiles):
+    q = np.asarray(quantiles, dtype=np.float64).reshape(-1)
+    if not np.all((q >= 0.0) & (q <= 1.0)):                               # (NaN fails both comparisons)
+        raise ValueError("quantiles must lie in [0, 1], got %s" % (q.tolist(),))
+    return q
+
+
+def sample_stats(samples, y=None, shapiro=True, quantiles=None):
+    """samples [S, N] (device, any strides), y [N] or None -> dict of device tensors through one ``iwvi_sample_stats`` launch:
+    ``mean_std`` [N, 2] always; ``logp`` and ``sqerr`` [N] (as ``kde_log_density``) when ``y`` is given; ``W`` [N] (Shapiro-Wilk) when
+    ``shapiro``; ``quantiles`` [N, len(quantiles)] (NumPy's default linear rule) when asked for.  2 <= S <= 16384."""
+    probs = None if quantiles is None else _check_probs(quantiles)
+    if not isinstance(samples, torch.Tensor) or samples.dim() != 2:
+        raise ValueError("samples must be a [S, N] tensor")
+    S, N = samples.shape
+    if S < 2 or S > MAX_SAMPLES:
+        raise ValueError("S=%d out of range (2..%d)" % (S, MAX_SAMPLES))
+    if N > 0 and min(samples.stride()) <= 0:                             # (an expanded view: the kernel takes positive strides)
+        samples = samples.contiguous()
+    if not samples.is_cuda or samples.dtype != settings.float_type:
+        _abi.dev_tensor(samples.contiguous(), "samples")                 # (raises: no CPU fallback, float32 only)
+    dev = samples.device
+    if y is not None:
+        y = _abi.dev_tensor(y.reshape(-1).contiguous(), "y")
+        if y.numel() != N:
+            raise ValueError("y has %d entries, samples cover %d points" % (y.numel(), N))
+    out = {"mean_std": torch.empty(N, 2, dtype=settings.float_type, device=dev)}
+    if y is not None:
+        out["logp"], out["sqerr"] = (torch.empty(N, dtype=settings.float_type, device=dev) for _ in range(2))
+    coef = None
+    if shapiro:
+        coef = _shapiro_coefficients_dev(S, dev)
+        out["W"] = torch.empty(N, dtype=settings.float_type, device=dev)
+    pr = None
+    if probs is not None:
+        pr = torch.as_tensor(probs, dtype=torch.float64, device=dev)
+        out["quantiles"] = torch.empty(N, len(probs), dtype=settings.float_type, device=dev)
+    if N == 0:
+        return out
+    ss, sn = samples.stride()
+    _abi.check(_abi.lib().iwvi_sample_stats(ctypes.c_void_p(samples.data_ptr()), ss, sn, _abi.ptr(y), N, S, _abi.ptr(coef), _abi.ptr(pr),
+                                           0 if probs is None else len(probs), _abi.ptr(out.get("logp")), _abi.ptr(out.get("sqerr")),
+                                           _abi.ptr(out["mean_std"]), _abi.ptr(out.get("W")), _abi.ptr(out.get("quantiles")),
+                                           _abi.stream_ptr()))
+    return out
+
+
+def _evaluate_on_device(model, X_test, Y_test, num_predict_samples, predict_batch_size, quantiles):
+    parts = []
+    for lo in range(0, X_test.shape[0], predict_batch_size):
+        x, y = X_test[lo:lo + predict_batch_size], Y_test[lo:lo + predict_batch_size]
+        smp = model.predict_y_samples_fused(x, num_predict_samples)[:, :, 0]       # [S, n], a point's samples contiguous
+        parts.append(sample_stats(smp, y, shapiro=True, quantiles=quantiles))
+    cat = {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+    # one read-back: the three scalars in one tensor (NumPy's median: the mean of the two middle values for an even count)
+    W = cat["W"].double().sort().values
+    med = 0.5 * (W[(W.numel() - 1) // 2] + W[W.numel() // 2])
+    vals = torch.stack([cat["logp"].double().mean(), cat["sqerr"].double().mean().sqrt(), med]).cpu().numpy()
+    res = {"test_loglik": float(vals[0]), "test_rmse": float(vals[1]), "test_shapiro_W_median": float(vals[2])}
+    if quantiles is not None:
+        res["test_quantiles"] = cat["quantiles"].cpu().numpy()
+    return res
+
+
+def evaluate(model, X_test, Y_test, num_predict_samples=2000, predict_batch_size=1000, shapiro=False, mc_loglik=False,
+             on_device=False, quantiles=None):
     """-> dict(test_loglik, test_rmse[, test_shapiro_W_median]) as the reference's ``res`` (:167-169); Y one column.
     ``mc_loglik``: also ``test_loglik_mc``, the mean Monte Carlo log predictive density (``model.predict_log_density`` with
-    ``num_predict_samples`` draws per point), the usual DGP test metric beside the reference's KDE estimate."""
+    ``num_predict_samples`` draws per point), the usual DGP test metric beside the reference's KDE estimate.
+    ``on_device``: per batch ``predict_y_samples_fused`` and one ``iwvi_sample_stats`` launch, one read-back at the end;
+    ``test_shapiro_W_median`` is then always in the result (the reference's row), and ``quantiles=[...]`` (on-device only) adds
+    ``test_quantiles`` [N, len(quantiles)], the predictive quantiles per test point."""
+    if quantiles is not None:
+        if not on_device:
+            raise ValueError("quantiles need on_device=True")
+        _check_probs(quantiles)
     dev = model.X.device
     X_test = torch.as_tensor(np.asarray(X_test, dtype=np.float32), device=dev) if not isinstance(X_test, torch.Tensor) else X_test.to(dev, settings.float_type)
     Y_test = torch.as_tensor(np.asarray(Y_test, dtype=np.float32), device=dev) if not isinstance(Y_test, torch.Tensor) else Y_test.to(dev, settings.float_type)
@@ -38,6 +161,12 @@ def evaluate(model, X_test, Y_test, num_predict_samples=2000, predict_batch_size
     N = X_test.shape[0]
     if N == 0 or Y_test.shape[0] != N:
         raise ValueError("X_test has %d rows, Y_test %d" % (N, Y_test.shape[0]))
+    if on_device:
+        res = _evaluate_on_device(model, X_test, Y_test, num_predict_samples, predict_batch_size, quantiles)
+        if mc_loglik:
+            lp = model.predict_log_density(X_test, Y_test.reshape(N, -1), num_predict_samples, batch_size=predict_batch_size)
+            res["test_loglik_mc"] = float(lp.double().mean())
+        return res
     logps, sqs, Ws = [], [], []
     for lo in range(0, N, predict_batch_size):
         x, y = X_test[lo:lo + predict_batch_size], Y_test[lo:lo + predict_batch_size]

@@ -3,7 +3,8 @@
 The layer kernel's hot variants sit at the 256-VGPR limit: a source change anywhere in the layer loop can push one of them into
 scratch, and a variant that only the large configs take then regresses unnoticed (round 4: the five-sub-tile large-M variant went
 216 B into scratch, configs[3] 1.27 -> 1.43 ms, for four commits).  ``check()`` is run by ``__graft_entry__.build()`` and by
-tests/test_kernel_resources.py: it fails when a ``k_dgp_forward`` or ``k_bw_chain`` instantiation uses scratch memory
+tests/test_kernel_resources.py: it fails when a ``k_dgp_forward`` or ``k_bw_chain`` instantiation (the predictive and sampling variants of the
+forward included) or ``k_sample_stats`` uses scratch memory
 (``.private_segment_fixed_size`` > 0) beyond what ``ALLOWED_SCRATCH`` lists, or when a listed spill count grows.
 
   python -m dgps_with_iwvi_amd.kernel_resources [--write profiles/<tag>_kernel_resources.txt]
@@ -24,7 +25,7 @@ FIELDS = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_sp
           "group_segment_fixed_size", "max_flat_workgroup_size")
 
 # kernels whose instantiations must not touch scratch memory at all ...
-NO_SCRATCH = ("k_dgp_forward", "k_bw_chain")
+NO_SCRATCH = ("k_dgp_forward", "k_bw_chain", "k_sample_stats")
 # ... except these (demangled-name substring -> bytes of scratch it is known to use; lower it when a kernel improves)
 ALLOWED_SCRATCH = {
     # round 6 (profiles/r06_kernel_resources.txt): every BIG variant (some layer with M > 128: configs[3] / [4]) and every float64-route

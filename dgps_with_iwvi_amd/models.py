@@ -198,7 +198,8 @@ class DGP_VI:
         the final layer's a, noise and latent moments alone.
         ``X`` / ``Y``: explicit inputs and targets in place of the current minibatch.  ``predict`` = dict(S, out): run
         ``iwvi_dgp_predict_density`` instead (rows t = n S + s, latent-variable layers in prior mode: ``use_encoder=False``),
-        writing the per-point Monte Carlo log predictive density into ``out`` [N]."""
+        writing the per-point Monte Carlo log predictive density into ``out`` [N]; ``predict`` = dict(S, out_y[, z_y]): run
+        ``iwvi_dgp_predict_samples`` -- the same rows, y samples into ``out_y`` [N, S, Dy] (``z_y`` [N S, Dy]: the likelihood's noise)."""
         dev = self.X.device
         layers = self.layers[stack_from:]
         n = len(layers)
@@ -262,6 +263,13 @@ class DGP_VI:
             keep.append(k)
             outs.append(o)
         words = self._words()
+        if predict is not None and "out_y" in predict:
+            N, S, out_y, z_y = X.shape[0], predict["S"], predict["out_y"], predict.get("z_y")
+            lik_host, lik_dev = self.likelihood.desc_variance()
+            _abi.check(_abi.lib().iwvi_dgp_predict_samples(descs, n, _abi.ptr(X), X.shape[1], out_y.shape[-1], N, S, lik_host, lik_dev,
+                                                           _abi.ptr(z_y), settings.seed, ctypes.c_void_p(words.data_ptr() + 8),
+                                                           _abi.ptr(out_y), _abi.stream_ptr()))
+            return None, outs, None
         if predict is not None:
             N, S, out = X.shape[0], predict["S"], predict["out"]
             ws = torch.empty((_abi.lib().iwvi_dgp_predict_density_ws_bytes(N, S) + 3) // 4, dtype=torch.float32, device=dev)
@@ -452,16 +460,7 @@ class DGP_VI:
         if Y.dim() != 2 or Y.shape[0] != X.shape[0] or Y.shape[1] != Dy:
             raise ValueError("Y must be [%d, %s], got %s" % (X.shape[0], Dy, tuple(Y.shape)))
         N = X.shape[0]
-        zs = [None] * len(self.layers) if zs is None else list(zs)
-        if len(zs) != len(self.layers):
-            raise ValueError("zs needs one entry per layer")
-        for i, (l, z) in enumerate(zip(self.layers, zs)):
-            if isinstance(l, LatentVariableLayer) and (l.q_mu_placeholder is not None or l.q_sqrt_placeholder is not None):
-                raise ValueError("layer %d: fed latent-variable placeholders are not supported by predict_log_density" % i)
-            if z is not None:
-                w = l.latent_dim if isinstance(l, LatentVariableLayer) else l.num_outputs
-                if tuple(z.shape) != (S, N, w):
-                    raise ValueError("zs[%d] must be [S, N, %d] = %s, got %s" % (i, w, (S, N, w), tuple(z.shape)))
+        zs = self._check_predict_noise("predict_log_density", S, N, zs)
         bs = batch_size or max(1, self._PREDICT_ROWS // S)
         if bs < 1:
             raise ValueError("batch_size must be >= 1")
@@ -476,6 +475,55 @@ class DGP_VI:
             self._fused_forward(nb * S, S, nb, (nb * S,), zs=zb, want_logw=False, use_encoder=False,
                                 X=X[lo:hi], Y=Y[lo:hi], predict=dict(S=S, out=out[lo:hi]))
         return out
+
+    def _check_predict_noise(self, what, S, N, zs):
+        """``zs`` of the fused predictive routes: one [S, N, dim] array or None per layer; no fed latent-variable placeholders."""
+        zs = [None] * len(self.layers) if zs is None else list(zs)
+        if len(zs) != len(self.layers):
+            raise ValueError("zs needs one entry per layer")
+        for i, (l, z) in enumerate(zip(self.layers, zs)):
+            if isinstance(l, LatentVariableLayer) and (l.q_mu_placeholder is not None or l.q_sqrt_placeholder is not None):
+                raise ValueError("layer %d: fed latent-variable placeholders are not supported by %s" % (i, what))
+            if z is not None:
+                w = l.latent_dim if isinstance(l, LatentVariableLayer) else l.num_outputs
+                if tuple(z.shape) != (S, N, w):
+                    raise ValueError("zs[%d] must be [S, N, %d] = %s, got %s" % (i, w, (S, N, w), tuple(z.shape)))
+        return zs
+
+    def predict_y_samples_fused(self, X, S, zs=None, z_y=None, batch_size=None):
+        """``predict_y_samples`` [S, N, Dy] in one launch per batch of points: one precompute, then per ``batch_size`` points one
+        ``iwvi_dgp_predict_samples`` call (the fused forward with a sampling tail; no per-layer sample, mean or variance reaches memory).
+        ``zs``: one [S, N, dim] array or None per layer, ``z_y`` [S, N, Dy] the likelihood's noise -- with both given the result is
+        ``predict_y_samples(X, S, zs, z_y)``; what is not given is drawn in the kernel.  The result is a transposed view of the kernel's
+        [N, S, Dy], in which a point's S samples are contiguous (what ``evaluation.sample_stats`` reads fastest)."""
+        X = _data(X)
+        S = int(S)
+        if S < 1:
+            raise ValueError("S must be >= 1, got %d" % S)
+        if X.dim() != 2 or X.shape[1] != self._input_dim():
+            raise ValueError("X must be [N, %s], got %s" % (self._input_dim(), tuple(X.shape)))
+        Dy = self._output_dim()
+        if Dy is None:
+            raise ValueError("predict_y_samples_fused needs a GP layer as the last layer")
+        N = X.shape[0]
+        zs = self._check_predict_noise("predict_y_samples_fused", S, N, zs)
+        if z_y is not None and tuple(z_y.shape) != (S, N, Dy):
+            raise ValueError("z_y must be [S, N, %d] = %s, got %s" % (Dy, (S, N, Dy), tuple(z_y.shape)))
+        bs = max(1, self._PREDICT_ROWS // S) if batch_size is None else int(batch_size)
+        if bs < 1:
+            raise ValueError("batch_size must be >= 1")
+        out = torch.empty(N, S, Dy, dtype=settings.float_type, device=X.device)
+        if N == 0:
+            return out.transpose(0, 1)
+        self.precompute()
+        for lo in range(0, N, bs):
+            hi = min(N, lo + bs)
+            nb = hi - lo
+            zb = [None if z is None else _data(z)[:, lo:hi].transpose(0, 1).reshape(nb * S, -1) for z in zs]   # point-major rows n S + s
+            zyb = None if z_y is None else _abi.dev_tensor(_data(z_y)[:, lo:hi].transpose(0, 1).reshape(nb * S, Dy).contiguous(), "z_y")
+            self._fused_forward(nb * S, S, nb, (nb * S,), zs=zb, want_logw=False, use_encoder=False,
+                                X=X[lo:hi], predict=dict(S=S, out_y=out[lo:hi], z_y=zyb))
+        return out.transpose(0, 1)
 
     def predict_y_samples(self, X, S, zs=None, z_y=None):
         X = _data(X)

@@ -27,6 +27,9 @@
 extern "C" {
 #endif
 
+/* 19, with an additive extension: iwvi_dgp_predict_samples and iwvi_sample_stats were added without a change to any existing entry point
+ * or struct, so the number did not move and a caller built against 19 keeps working.  A C caller that wants the two symbols looks them up
+ * (dlsym), Python asks hasattr(lib, ...). */
 #define IWVI_ABI_VERSION 19
 
 enum {
@@ -594,6 +597,34 @@ size_t iwvi_dgp_predict_density_ws_bytes(int64_t N, int64_t S);
 int iwvi_dgp_predict_density(const iwvi_layer_desc* layers_host, int n_layers, const float* X, int Dx, const float* Y, int Dy,
                              int64_t N, int64_t S, float lik_variance, const float* lik_variance_dev, uint64_t seed,
                              uint64_t* rng_state, float* out_logp, void* ws, void* stream);
+
+/* Predictive samples of y from the layer stack (additive extension of ABI 19), the doubly-stochastic DGP's predict_y_samples(X, S)
+ * (reference models.py:104-107):
+ *   out_y[n, s, d] = m_snd + sqrt(v_snd + variance) eps_snd
+ * with (m_snd, v_snd) and the rows t = n S + s exactly as in iwvi_dgp_predict_density: ONE iwvi_dgp_forward launch whose tail writes the
+ * samples -- no per-layer output reaches memory.  eps = z_y[t, d] ([N S, Dy]) when z_y is given; otherwise drawn from the launch's
+ * counter-based stream under an index no layer uses, so the layers' own draws are those of the same call without the tail.
+ * X [N, Dx]; out_y [N, S, Dy] (a point's S samples are contiguous: what iwvi_sample_stats reads fastest); Dy = the final layer's P;
+ * variance = *lik_variance_dev when given.  rng_state as in iwvi_dgp_forward (its step word advances once per call); it may be NULL
+ * only when z_y and every layer's noise are given.  N x S < 2^31 - 4096. */
+int iwvi_dgp_predict_samples(const iwvi_layer_desc* layers_host, int n_layers, const float* X, int Dx, int Dy, int64_t N, int64_t S,
+                             float lik_variance, const float* lik_variance_dev, const float* z_y, uint64_t seed,
+                             uint64_t* rng_state, float* out_y, void* stream);
+
+/* Per-point statistics of S samples in one launch (additive extension of ABI 19): the rest of the reference's evaluation loop
+ * (experiments/run_conditional_density_estimation.py:148-169) and quantiles, from ONE ascending sort of each point's samples in LDS.
+ * samples: element (s, n) at samples[s*sample_stride + n*point_stride] (positive strides), 2 <= S <= 16384; y [N].
+ *   out_logp, out_sqerr, out_mean_std [N, 2]: as iwvi_kde_loglik (float64 sums); y may be NULL when neither out_logp nor out_sqerr is asked for
+ *   out_W [N]: the Shapiro-Wilk statistic W = (sum_i a_i (x_(S+1-i) - x_(i)))^2 / sum_i (x_i - mean)^2 with Royston's coefficients
+ *     (algorithm AS R94) a = sw_coef [S/2], float64 on the device; they depend on S alone and are computed by the caller (Python:
+ *     evaluation.shapiro_coefficients).  All samples equal: W = 1.
+ *   out_quantiles [N, n_probs]: at probs [n_probs] (device, float64 like NumPy's -- a float32 0.975 would move the position p (S - 1) by 4e-5 at
+ *     S = 2000 --, each in [0, 1]; values outside are clamped), NumPy's default rule: position
+ *     p (S - 1), linear interpolation between the two neighbouring sorted values.  n_probs = 0: none.
+ * Every output may be NULL.  A point with a NaN sample gets NaN in all of its outputs; other points are not affected. */
+int iwvi_sample_stats(const float* samples, int64_t sample_stride, int64_t point_stride, const float* y, int64_t N, int S,
+                      const double* sw_coef, const double* probs, int n_probs, float* out_logp, float* out_sqerr,
+                      float* out_mean_std, float* out_W, float* out_quantiles, void* stream);
 
 /* white=False (temp_workaround.py:63-65: "another backsubstitution in the unwhitened case").  The unwhitened
  * q(u) = N(f, q_sqrt q_sqrt^T) gives the same conditional as the whitened one with f_w = Lm^-1 f and

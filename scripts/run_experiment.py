@@ -44,6 +44,7 @@ def main(argv=None):
     p.add_argument("--n_train", type=int, default=2000)
     p.add_argument("--n_test", type=int, default=500)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--device_eval", action="store_true", help="evaluate on the device: fused y-samples + iwvi_sample_stats (evaluate(on_device=True))")
     ARGS = p.parse_args(argv)
     ARGS.fix_linear = bool(ARGS.fix_linear)
     rng = np.random.default_rng(ARGS.seed)
@@ -62,7 +63,7 @@ def main(argv=None):
             print("iteration %5d  ELBO %.2f" % (it, float(elbo)), flush=True)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    res = evaluation.evaluate(model, Xs, Ys, ARGS.num_predict_samples, ARGS.predict_batch_size, shapiro=True)
+    res = evaluation.evaluate(model, Xs, Ys, ARGS.num_predict_samples, ARGS.predict_batch_size, shapiro=True, on_device=ARGS.device_eval)
     res.update(test_loglik_before_training=before["test_loglik"], train_seconds=dt, ms_per_iteration=dt / max(ARGS.iterations, 1) * 1e3)
     res.update(ARGS.__dict__)
     print(res)
