@@ -35,6 +35,7 @@ c_void_p, c_int, c_int64, c_float, c_double, c_size_t = (
 
 
 ERR_ARG, ERR_LAUNCH, ERR_UNSUPPORTED = -1, -2, -3      # enum iwvi_status (include/iwvi_hip.h)
+LIK_GAUSSIAN, LIK_BERNOULLI_PROBIT, LIK_STUDENT_T = 0, 1, 2   # iwvi_lik_desc.type
 BW_ROUTE_CHAIN, BW_ROUTE_MID, BW_ROUTE_GEMM = 1, 2, 3   # iwvi_debug_last_backward_routes
 
 
@@ -104,6 +105,11 @@ class GpBwdDesc(ctypes.Structure):
                 ("dq_mu", c_void_p), ("dq_sqrt", c_void_p), ("dW", c_void_p), ("dmf_A", c_void_p),
                 ("side_stream", c_void_p), ("side_stream2", c_void_p), ("prepared", ctypes.c_int32),
                 ("variance_dev", c_void_p), ("phase", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+class LikDesc(ctypes.Structure):
+    """struct iwvi_lik_desc (include/iwvi_hip.h): a likelihood for the iwvi_lik_* entry points."""
+    _fields_ = [("type", ctypes.c_int32), ("param", c_float * 2), ("lgc", c_float), ("param0_dev", c_void_p)]
 
 
 class AdamTensor(ctypes.Structure):
@@ -220,6 +226,19 @@ PROTOTYPES = {
                                          c_float, c_void_p, c_void_p, ctypes.c_uint64, c_void_p, c_void_p, c_void_p]),
     "iwvi_sample_stats": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "iwvi_lik_elbo_reduce": (c_int, [ctypes.POINTER(LikDesc), c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_int64,
+                                     ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_int32), c_int,
+                                     ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_int32), c_int, c_double,
+                                     c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "iwvi_lik_elbo_backward": (c_int, [ctypes.POINTER(LikDesc), c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(c_void_p),
+                                       ctypes.POINTER(ctypes.c_int32), c_int, c_int64, c_int, c_double, c_int,
+                                       c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_int32), c_int,
+                                       c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "iwvi_lik_var_exp": (c_int, [ctypes.POINTER(LikDesc), c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64,
+                                 c_void_p, c_void_p]),
+    "iwvi_lik_predict_density": (c_int, [ctypes.POINTER(LikDesc), c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64,
+                                         c_void_p, c_void_p]),
+    "iwvi_lik_predict_mean_and_var": (c_int, [ctypes.POINTER(LikDesc), c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "iwvi_unwhiten": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "iwvi_fill_normal": (c_int, [c_void_p, c_int64, ctypes.c_uint64, ctypes.c_uint64, c_void_p]),
     "iwvi_fill_normal_dev": (c_int, [c_void_p, c_int64, ctypes.c_uint64, c_void_p, c_void_p]),

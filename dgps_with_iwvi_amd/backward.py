@@ -371,8 +371,13 @@ def iw_elbo_and_gradients(model, zs=None, mode_vi=None, exchange=None, K_total=N
     The IW-ELBO of the current minibatch (models.py:112-150) and its gradient w.r.t. every parameter the
     reference trains (build_models.py:284-304): -> (elbo [0-dim float64 tensor], dict) with the names of
     oracle/grad_oracle.py: 'l<i>.Z', 'l<i>.ls', 'l<i>.var', 'l<i>.q_mu', 'l<i>.q_sqrt', 'l<i>.W', 'l<i>.mfA' (layers with
-    a mixing matrix / linear mean function), 'l<i>.encW<j>', 'l<i>.encb<j>', 'lik_var'.  ``zs``: one noise tensor per layer ([B, K, dim]) or None -> drawn."""
+    a mixing matrix / linear mean function), 'l<i>.encW<j>', 'l<i>.encb<j>', 'lik_var'.  ``zs``: one noise tensor per layer ([B, K, dim]) or None -> drawn.
+
+    A likelihood other than the Gaussian (``likelihoods.Bernoulli`` / ``StudentT``): the heads never come out of the layer launch
+    (``fuse_heads`` is off) but from ``iwvi_lik_elbo_backward`` on the final layer's moments; the layer adjoints are the same.  The
+    likelihood's gradient is named by its ``grad_name`` ('lik_scale' for the Student-t; the Bernoulli has none)."""
     from .layers import LatentVariableLayer
+    from .likelihoods import is_gaussian
     from .models import DGP_IWVI
     from .temp_workaround import draw_normal
     dev = model.X.device
@@ -400,6 +405,12 @@ def iw_elbo_and_gradients(model, zs=None, mode_vi=None, exchange=None, K_total=N
                                   "2 latent-variable layers (%d in this model)" % n_lv)
     has_lv = any(isinstance(l, LatentVariableLayer) for l in layers)
     XY = model._xy_minibatch() if has_lv else None
+    gauss = is_gaussian(model.likelihood)
+    if not gauss:
+        if exchange is not None:
+            raise NotImplementedError("K-sharded training exchanges the Gaussian tail's per-point pairs; a %s model trains on one rank "
+                                      "or N-sharded" % type(model.likelihood).__name__)
+        fuse_heads = False
     # beside the forward, on its own stream: dense float64 factors + the parameter-only part of every layer's adjoint
     cur = torch.cuda.current_stream()
     import os
@@ -508,14 +519,21 @@ def iw_elbo_and_gradients(model, zs=None, mode_vi=None, exchange=None, K_total=N
         if sharding._RECORDER is not None and prep_stream != cur:
             cur.wait_stream(prep_stream)                         # a segmented capture cuts the graph at the exchange: no forked work may be left open across the cut
         lse_g = _abi.dev_tensor(exchange(ms).to(ft).contiguous(), "lse_global")
-    lik_host, lik_dev = model.likelihood.desc_variance()
-    if not fused_heads:
+    if not gauss:
+        _abi.check(_abi.lib().iwvi_lik_elbo_backward(
+            model.likelihood.lik_desc(), _abi.ptr(fin.mean), _abi.ptr(fin.var), _abi.ptr(Y), Dy, klp, kld, len(kls), B, K,
+            scale, 1 if mode_vi else 0, _abi.ptr(w), _abi.ptr(d_mean), _abi.ptr(d_var),
+            glob_p, glob_n, len(glob), _abi.ptr(lse_g), int(K_total or K),
+            ctypes.c_void_p(sums.data_ptr()), ctypes.c_void_p(ws.data_ptr()), _abi.stream_ptr()))
+    lik_host, lik_dev = model.likelihood.desc_variance() if gauss else (1.0, None)
+    if gauss and not fused_heads:
         _abi.check(_abi.lib().iwvi_iw_elbo_backward_dev(
             _abi.ptr(fin.mean), _abi.ptr(fin.var), _abi.ptr(Y), Dy, klp, kld, len(kls), B, K,
             lik_host, lik_dev, scale, 1 if mode_vi else 0, _abi.ptr(w), _abi.ptr(d_mean), _abi.ptr(d_var),
             glob_p, glob_n, len(glob), _abi.ptr(lse_g), int(K_total or K),
             ctypes.c_void_p(sums.data_ptr()), ctypes.c_void_p(ws.data_ptr()), _abi.stream_ptr()))
-    grads = {"lik_var": sums[1]}
+    lik_name = getattr(model.likelihood, "grad_name", "lik_var")    # (a class attribute: no read of the value, which may live on the device)
+    grads = {} if lik_name is None else {lik_name: sums[1]}
     elbo = sums[2]                                               # scale * sum_n(...) - sum of the global KLs, formed on the device
     if final_q:
         i = len(layers) - 1

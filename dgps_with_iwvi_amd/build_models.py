@@ -117,9 +117,35 @@ def attach_train_op(model, ARGS):
 
 
 # ---- checkpoint / resume of the parameters (reference: gpflow Saver, run_conditional_density_estimation.py:95-125) ----
+def likelihood_state(lik):
+    """A Gaussian is stored as ever ('likelihood.variance'); any other likelihood under 'likelihood.type' (its class name) and
+    'likelihood.params' (its parameters in the order of the constructor)."""
+    from .likelihoods import Bernoulli, StudentT
+    if isinstance(lik, StudentT):
+        return {"likelihood.type": np.str_("StudentT"), "likelihood.params": np.array([lik.scale, lik.df], dtype=np.float64)}
+    if isinstance(lik, Bernoulli):
+        return {"likelihood.type": np.str_("Bernoulli"), "likelihood.params": np.zeros(0, dtype=np.float64)}
+    return {"likelihood.variance": np.float64(lik.variance)}
+
+
+def load_likelihood_state(lik, state):
+    """Into the model's own likelihood object (a trainer's device master is bound to it).  A file without 'likelihood.type' was written
+    for a Gaussian -- every file from before the other likelihoods existed."""
+    from .likelihoods import Bernoulli, StudentT
+    kind = str(state["likelihood.type"]) if "likelihood.type" in state else "Gaussian"
+    have = "StudentT" if isinstance(lik, StudentT) else "Bernoulli" if isinstance(lik, Bernoulli) else "Gaussian"   # (as likelihood_state: subclasses count)
+    if kind != have:
+        raise ValueError("the checkpoint holds a %s likelihood, the model a %s" % (kind, type(lik).__name__))
+    if kind == "StudentT":
+        scale, df = (float(v) for v in np.asarray(state["likelihood.params"]).reshape(-1))
+        lik.scale, lik.df = scale, df
+    elif kind == "Gaussian":
+        lik.variance = float(state["likelihood.variance"])
+
+
 def state_dict(model):
     """Every parameter tensor of the stack, as CPU float arrays keyed 'layers.<i>.<name>'."""
-    out = {"likelihood.variance": np.float64(model.likelihood.variance)}
+    out = likelihood_state(model.likelihood)
     for i, layer in enumerate(model.layers):
         p = "layers.%d." % i
         if isinstance(layer, GPLayer):
@@ -168,7 +194,7 @@ def load_state_dict(model, state):
         else:
             getattr(obj, name)[index] = new
 
-    model.likelihood.variance = float(state["likelihood.variance"])
+    load_likelihood_state(model.likelihood, state)
     for i, layer in enumerate(model.layers):
         p = "layers.%d." % i
         if isinstance(layer, GPLayer):

@@ -1,0 +1,476 @@
+// The bound's tail and the heads of its adjoint for likelihoods other than the Gaussian (include/iwvi_hip.h: iwvi_lik_*), and the
+// likelihood's methods as elementwise callables.  The reference passes any GPflow-1.x likelihood to its models (models.py:66,105,134);
+// the non-conjugate ones -- Bernoulli with the probit link, Student-t -- integrate by GPflow's ndiagquad: Gauss-Hermite, 20 points.
+// The layer stack is untouched: these kernels read the final layer's moments (and the local regularisers) the layer launch left in HBM.
+#include "iwvi_common.h"
+
+namespace iwvi {
+
+// numpy.polynomial.hermite.hermgauss(20): the rule is symmetric, x_(19-i) = -x_i with equal weights -- the ten positive nodes, their
+// weights w_i / sqrt(pi) and the logarithms of those (log-space sums).  Rounded to float32 the twenty weights sum to 1 - 5e-9.
+__device__ __constant__ const float GH_X[10] = {2.453407083e-01f, 7.374737285e-01f, 1.234076215e+00f, 1.738537712e+00f, 2.254974002e+00f,
+                                                2.788806058e+00f, 3.347854567e+00f, 3.944764040e+00f, 4.603682450e+00f, 5.387480890e+00f};
+__device__ __constant__ const float GH_W[10] = {2.607930634e-01f, 1.617393340e-01f, 6.150637206e-02f, 1.399783745e-02f, 1.830103131e-03f,
+                                                1.288262800e-04f, 4.402121090e-06f, 6.127490260e-08f, 2.482062362e-10f, 1.257800672e-13f};
+__device__ __constant__ const float GH_LOGW[10] = {-1.344028046e+00f, -1.821769289e+00f, -2.788614499e+00f, -4.268852429e+00f, -6.303382958e+00f,
+                                                   -8.957045728e+00f, -1.233342407e+01f, -1.660789550e+01f, -2.211676112e+01f, -2.970424151e+01f};
+
+// dE/dv = sum_i w_i g'(f_i) x_i / sqrt(2 v) is 0/0 at v = 0 (the forward clamps a float32 variance that undershot at exactly 0); its limit is
+// g''(mu) / 2.  The variance is floored here, for the value and the heads alike (the heads stay the gradient of the value that is
+// computed): sqrt(2 v) >= 1.4e-4, which moves E by g'' 5e-9 -- below float32 resolution -- and leaves the quotient finite.
+constexpr float LIK_V_FLOOR = 1e-8f;
+constexpr float LIK_JIT = 1e-3f;                  // GPflow's inv_probit jitter: p = Phi(f) (1 - 2 jit) + jit
+
+struct Lik { int type; float p0, p1, lgc; const float* p0_dev; };
+
+// g(f) = logp(f, y);  GRAD: also g'(f) and d g / d param[0]
+template <bool GRAD>
+__device__ __forceinline__ float lik_eval(const Lik& L, float p0, float f, float y, float& gp, float& gpar) {
+    if (L.type == IWVI_LIK_BERNOULLI_PROBIT) {
+        // Phi(f) = erfc(-f / sqrt 2) / 2 and 1 - Phi(f) = erfc(f / sqrt 2) / 2: neither tail cancels; 1 - p = (1 - Phi)(1 - 2 jit) + jit
+        const float u = f * 0.70710678118654752f;
+        const float p = 0.5f * erfcf(-u) * (1.f - 2.f * LIK_JIT) + LIK_JIT;
+        const float q = 0.5f * erfcf(u) * (1.f - 2.f * LIK_JIT) + LIK_JIT;
+        const bool one = (y == 1.f);
+        if (GRAD) {
+            const float dp = (1.f - 2.f * LIK_JIT) * 0.3989422804014327f * __expf(-0.5f * f * f);
+            gp = one ? dp / p : -dp / q;
+            gpar = 0.f;
+        }
+        return logf(one ? p : q);
+    }
+    const float e = y - f;
+    if (L.type == IWVI_LIK_STUDENT_T) {
+        const float s = p0, nu = L.p1, s2nu = s * s * nu;
+        if (GRAD) {
+            const float den = s2nu + e * e;
+            gp = (nu + 1.f) * e / den;
+            gpar = -1.f / s + (nu + 1.f) * e * e / (s * den);
+        }
+        return L.lgc - logf(s) - 0.5f * logf(nu * 3.14159265358979324f) - 0.5f * (nu + 1.f) * log1pf(e * e / s2nu);
+    }
+    if (GRAD) {
+        gp = e / p0;
+        gpar = -0.5f / p0 + 0.5f * e * e / (p0 * p0);
+    }
+    return -0.5f * logf(6.283185307179586f * p0) - 0.5f * e * e / p0;
+}
+
+// E_{N(f; mu, v)} g(f) by the rule; GRAD: dE/dmu, dE/dv, dE/dparam[0] by its reparameterised form (first derivatives only)
+template <bool GRAD>
+__device__ __forceinline__ float lik_quad(const Lik& L, float p0, float mu, float v, float y, float& dmu, float& dv, float& dpar) {
+    const float a = sqrtf(2.f * fmaxf(v, LIK_V_FLOOR));
+    float E = 0.f, s1 = 0.f, s2 = 0.f, sp = 0.f;
+#pragma unroll
+    for (int j = 0; j < 10; ++j) {
+        const float xa = a * GH_X[j];
+        float gpa = 0.f, gpb = 0.f, qa = 0.f, qb = 0.f;
+        const float ga = lik_eval<GRAD>(L, p0, mu + xa, y, gpa, qa);
+        const float gb = lik_eval<GRAD>(L, p0, mu - xa, y, gpb, qb);
+        E = fmaf(GH_W[j], ga + gb, E);
+        if (GRAD) {
+            s1 = fmaf(GH_W[j], gpa + gpb, s1);
+            s2 = fmaf(GH_W[j] * GH_X[j], gpa - gpb, s2);
+            sp = fmaf(GH_W[j], qa + qb, sp);
+        }
+    }
+    if (GRAD) { dmu = s1; dv = s2 / a; dpar = sp; }
+    return E;
+}
+
+// ------------------------------------------------------------------------------------------
+// The reduction (csrc/lv_elbo.hip: k_elbo with the quadrature in place of the Gaussian closed form): SEG lanes per data point, one lane
+// per sample walking its Dy outputs; float32 inside a sample, the log-sum-exp over K and the sum over the points in float64; the last
+// workgroup to arrive (agent-scope release / ticket / acquire) adds the points up in a fixed order.
+// ------------------------------------------------------------------------------------------
+constexpr int LIK_MAX_GLOB = 16;
+struct LikReduceArgs {
+    Lik lik;
+    const float* fmean; const float* fvar; const float* Y;
+    const float* kl[IWVI_MAX_KL]; int kl_dims[IWVI_MAX_KL]; int n_kl;
+    long long B, stride_b, stride_k; int K, Dy, K_total, mode_vi;
+    float* ms; float* logp;
+    double* elbo; unsigned long long* ticket; double scale;
+    const double* klg[LIK_MAX_GLOB]; int klg_n[LIK_MAX_GLOB]; int n_glob;
+};
+
+template <int SEG>
+__device__ __forceinline__ float lseg_max(float v) {
+#pragma unroll
+    for (int o = SEG / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+template <int SEG>
+__device__ __forceinline__ double lseg_sum(double v) {
+#pragma unroll
+    for (int o = SEG / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// A workgroup takes ONE pass of LIK_THREADS / SEG points (k_elbo takes 64 points in several passes: its per-sample work is a handful of
+// FMAs; here a sample costs 20 x Dy evaluations of erfc / log, and 64 points per workgroup left configs[2] -- B = 1024 -- on 16 of the
+// chip's 256 CUs: a Bernoulli evaluation took 101.6 us against 66.0 with the points spread -- profiles/likelihood_tail_time.json)
+constexpr int LIK_THREADS = 256;
+
+template <int SEG>
+__global__ __launch_bounds__(LIK_THREADS) void k_lik_elbo(LikReduceArgs g) {
+    __shared__ double red[LIK_THREADS];
+    __shared__ int is_last;
+    const int tid = threadIdx.x, sl = tid % SEG, sg = tid / SEG;
+    constexpr int PPP = LIK_THREADS / SEG;
+    const int K = g.K, Dy = g.Dy;
+    const float p0 = g.lik.p0_dev ? *g.lik.p0_dev : g.lik.p0;
+    {
+        const long long b = (long long)blockIdx.x * PPP + sg;
+        const bool live = b < g.B;                    // uniform within a segment
+        float m = -INFINITY;
+        double ssum = 0.0, lsum = 0.0;
+        for (int k0 = 0; k0 < K; k0 += SEG) {
+            const int k = k0 + sl;
+            const bool on = live && k < K;
+            float L = -INFINITY;
+            if (on) {
+                const long long t = b * g.stride_b + k * g.stride_k;
+                float acc = 0.f, d0, d1, d2;
+                for (int d = 0; d < Dy; ++d)
+                    acc += lik_quad<false>(g.lik, p0, g.fmean[t * Dy + d], g.fvar[t * Dy + d], g.Y[b * Dy + d], d0, d1, d2);
+                for (int i = 0; i < g.n_kl; ++i)
+                    for (int d = 0; d < g.kl_dims[i]; ++d) acc -= g.kl[i][t * g.kl_dims[i] + d];
+                L = acc;
+            }
+            if (g.mode_vi) { lsum += lseg_sum<SEG>(on ? (double)L : 0.0); continue; }
+            const float nm = fmaxf(m, lseg_max<SEG>(L));
+            const double cs = lseg_sum<SEG>(on ? (double)__expf(L - nm) : 0.0);
+            ssum = (m == -INFINITY ? 0.0 : ssum * (double)__expf(m - nm)) + cs;
+            m = nm;
+        }
+        if (live && sl == 0) {
+            if (g.mode_vi) {
+                if (g.logp) g.logp[b] = (float)(lsum / (double)K);                                   // models.py:84
+            } else {
+                if (g.ms) { g.ms[2 * b] = m; g.ms[2 * b + 1] = (float)ssum; }
+                if (g.logp) g.logp[b] = (float)((double)m + log(ssum) - log((double)g.K_total));     // models.py:148
+            }
+        }
+    }
+    if (!g.elbo) return;
+    // ---- publish this workgroup's logp, draw a ticket, the last arriver sums everything ----
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned long long t = __hip_atomic_fetch_add(g.ticket, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = (t == (unsigned long long)gridDim.x - 1);
+        if (last) {
+            __hip_atomic_store(g.ticket, 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next call
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        is_last = last;
+    }
+    __syncthreads();
+    if (!is_last) return;
+    double acc = 0.0;
+    for (long long b = tid; b < g.B; b += LIK_THREADS) acc += (double)g.logp[b];
+    red[tid] = acc;
+    __syncthreads();
+    for (int s2 = LIK_THREADS / 2; s2 > 0; s2 >>= 1) {
+        if (tid < s2) red[tid] += red[tid + s2];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double kl = 0.0;
+        for (int i = 0; i < g.n_glob; ++i)
+            for (int c = 0; c < g.klg_n[i]; ++c) kl += g.klg[i][c];
+        *g.elbo = red[0] * g.scale - kl;                                                              // models.py:150
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Heads of the bound's adjoint (csrc/backward.hip: k_elbo_bwd with the quadrature): one wave per data point, lanes over its K samples.
+// Pass 1: L_nk and the running (max, sum exp); pass 2: the weights and, per output, the heads.
+// ------------------------------------------------------------------------------------------
+struct LikBwdArgs {
+    Lik lik;
+    const float* fmean; const float* fvar; const float* Y; int Dy;
+    const float* kl[IWVI_MAX_KL]; int kl_dims[IWVI_MAX_KL]; int n_kl;
+    long long B; int K; double scale; int mode_vi;
+    const float* lse_global; int K_total;
+    float* w; float* d_mean; float* d_var; double* part;   // part[0..B) = lse - log K, part[B..2B) = d param[0] share
+};
+__global__ __launch_bounds__(256) void k_lik_elbo_bwd(LikBwdArgs a) {
+    const int lane = threadIdx.x & 63;
+    const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= a.B) return;
+    const float p0 = a.lik.p0_dev ? *a.lik.p0_dev : a.lik.p0;
+    auto logw = [&](long long t) {
+        float l = 0.f, d0, d1, d2;
+        for (int j = 0; j < a.Dy; ++j)
+            l += lik_quad<false>(a.lik, p0, a.fmean[t * a.Dy + j], a.fvar[t * a.Dy + j], a.Y[b * a.Dy + j], d0, d1, d2);
+        for (int i = 0; i < a.n_kl; ++i)
+            for (int q = 0; q < a.kl_dims[i]; ++q) l -= a.kl[i][t * a.kl_dims[i] + q];
+        return l;
+    };
+    const bool one = a.K <= 64;                          // every lane holds its only sample's L_nk: no second evaluation
+    float Lc = -INFINITY, mx = -INFINITY;
+    double se = 0.0;
+    if (a.mode_vi) {                                    // models.py:84: mean over the samples -> uniform weights
+        for (int k = lane; k < a.K; k += 64) se += (double)logw(b * a.K + k);
+        for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
+    } else {
+        for (int k = lane; k < a.K; k += 64) { Lc = logw(b * a.K + k); mx = fmaxf(mx, Lc); }
+        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+        if (a.lse_global) {                             // weights against the whole job's normaliser: exp(L - LSE)
+            mx = a.lse_global[b]; se = 1.0;
+        } else {
+            for (int k = lane; k < a.K; k += 64) se += (double)__expf((one ? Lc : logw(b * a.K + k)) - mx);
+            for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
+        }
+    }
+    double ds = 0.0;
+    for (int k = lane; k < a.K; k += 64) {
+        const long long t = b * a.K + k;
+        float wt;
+        if (a.mode_vi) wt = (float)(a.scale / (double)a.K);
+        else wt = (float)(a.scale * (double)__expf((one ? Lc : logw(t)) - mx) / se);
+        if (a.w) a.w[t] = wt;
+        for (int j = 0; j < a.Dy; ++j) {
+            float dmu, dv, dp;
+            lik_quad<true>(a.lik, p0, a.fmean[t * a.Dy + j], a.fvar[t * a.Dy + j], a.Y[b * a.Dy + j], dmu, dv, dp);
+            if (a.d_mean) a.d_mean[t * a.Dy + j] = wt * dmu;
+            if (a.d_var) a.d_var[t * a.Dy + j] = wt * dv;
+            ds += (double)wt * (double)dp;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) ds += __shfl_xor(ds, o, 64);
+    if (lane == 0) {
+        a.part[b] = a.mode_vi ? se / (double)a.K : (double)mx + log(se) - log((double)(a.lse_global ? a.K_total : a.K));
+        a.part[a.B + b] = ds;
+    }
+}
+// out[0] = sum part[0..n), out[1] = sum part[n..2n), out[2] = scale * out[0] - sum of the global KL shares (the bound)
+struct LikFinishArgs { const double* part; long long n; double scale; const double* klg[IWVI_MAX_LAYERS]; int kln[IWVI_MAX_LAYERS]; int n_glob; double* out; };
+__global__ __launch_bounds__(256) void k_lik_finish(LikFinishArgs a) {
+    __shared__ double red[256];
+    double tot[2];
+    for (int i = 0; i < 2; ++i) {
+        const double* p = a.part + (size_t)i * a.n;
+        double s = 0.0;
+        for (long long k = threadIdx.x; k < a.n; k += 256) s += p[k];
+        red[threadIdx.x] = s;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+        tot[i] = red[0];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        double kl = 0.0;
+        for (int i = 0; i < a.n_glob; ++i) for (int q = 0; q < a.kln[i]; ++q) kl += a.klg[i][q];
+        a.out[0] = tot[0]; a.out[1] = tot[1]; a.out[2] = a.scale * tot[0] - kl;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Elementwise callables.  MODE 0: variational_expectations; 1: predict_density (Fvar == NULL: logp); 2: predict_mean_and_var
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ float inv_probit(float x) { return 0.5f * erfcf(-x * 0.70710678118654752f) * (1.f - 2.f * LIK_JIT) + LIK_JIT; }
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_lik_elem(Lik L, const float* __restrict__ Fmu, const float* __restrict__ Fvar,
+                                                  const float* __restrict__ Y, long long n, int Dy, long long row_div, long long row_mod,
+                                                  float* __restrict__ out, float* __restrict__ out2) {
+    const float p0 = L.p0_dev ? *L.p0_dev : L.p0;
+    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < n; idx += (long long)gridDim.x * blockDim.x) {
+        const float mu = Fmu[idx];
+        float d0, d1, d2;
+        if (MODE == 2) {
+            const float v = Fvar[idx];
+            if (L.type == IWVI_LIK_BERNOULLI_PROBIT) {
+                const float p = inv_probit(mu * rsqrtf(1.f + v));
+                out[idx] = p; out2[idx] = p - p * p;
+            } else if (L.type == IWVI_LIK_STUDENT_T) {
+                // m = E[F] = mu (the nodes are symmetric); E[s^2 nu / (nu - 2) + F^2] - m^2 by the rule in its centred form: f_i^2 - mu^2 =
+                // (a x_i)(2 mu + a x_i), and the node pair +-x_i adds 2 (a x_i)^2 -- mu^2 never enters, so nothing cancels
+                const float a = sqrtf(2.f * fmaxf(v, 0.f)), c = p0 * p0 * L.p1 / (L.p1 - 2.f);
+                float m2 = 0.f;
+#pragma unroll
+                for (int j = 0; j < 10; ++j) {
+                    const float xa = a * GH_X[j];
+                    m2 = fmaf(GH_W[j], 2.f * xa * xa, m2);
+                }
+                out[idx] = mu; out2[idx] = c + m2;
+            } else {
+                out[idx] = mu; out2[idx] = v + p0;
+            }
+            continue;
+        }
+        const long long t = idx / Dy;
+        const int d = (int)(idx - t * Dy);
+        const float y = Y[((t / row_div) % row_mod) * Dy + d];
+        if (MODE == 0) { out[idx] = lik_quad<false>(L, p0, mu, Fvar[idx], y, d0, d1, d2); continue; }
+        if (!Fvar) { out[idx] = lik_eval<false>(L, p0, mu, y, d0, d1); continue; }
+        const float v = Fvar[idx];
+        if (L.type == IWVI_LIK_BERNOULLI_PROBIT) {
+            const float x = mu * rsqrtf(1.f + v);
+            out[idx] = logf(y == 1.f ? inv_probit(x) : 0.5f * erfcf(x * 0.70710678118654752f) * (1.f - 2.f * LIK_JIT) + LIK_JIT);
+        } else if (L.type == IWVI_LIK_STUDENT_T) {
+            // log sum_i exp(g(f_i) + log w_i): the largest term first, then the sum (g is evaluated twice; nothing is kept in scratch)
+            const float a = sqrtf(2.f * fmaxf(v, 0.f));
+            float mx = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < 10; ++j) {
+                const float xa = a * GH_X[j];
+                mx = fmaxf(mx, GH_LOGW[j] + fmaxf(lik_eval<false>(L, p0, mu + xa, y, d0, d1), lik_eval<false>(L, p0, mu - xa, y, d0, d1)));
+            }
+            float s = 0.f;
+#pragma unroll
+            for (int j = 0; j < 10; ++j) {
+                const float xa = a * GH_X[j];
+                s += __expf(GH_LOGW[j] + lik_eval<false>(L, p0, mu + xa, y, d0, d1) - mx) + __expf(GH_LOGW[j] + lik_eval<false>(L, p0, mu - xa, y, d0, d1) - mx);
+            }
+            out[idx] = mx + logf(s);
+        } else {
+            const float e = y - mu, s = v + p0;
+            out[idx] = -0.5f * logf(6.283185307179586f * s) - 0.5f * e * e / s;
+        }
+    }
+}
+
+// descriptor -> kernel argument; what: the entry point's name for the error text; need_df2: predict_mean_and_var of the Student-t
+static int take_lik(const iwvi_lik_desc* d, Lik& L, const char* what, bool need_df2 = false) {
+    if (!d) { set_error("%s: null likelihood descriptor", what); return IWVI_ERR_ARG; }
+    L.type = d->type; L.p0 = d->param[0]; L.p1 = d->param[1]; L.lgc = d->lgc; L.p0_dev = d->param0_dev;
+    switch (d->type) {
+        case IWVI_LIK_GAUSSIAN:
+            if (!(d->param[0] > 0.f)) { set_error("%s: Gaussian variance must be positive", what); return IWVI_ERR_ARG; }
+            return IWVI_OK;
+        case IWVI_LIK_BERNOULLI_PROBIT:
+            L.p0 = 1.f; L.p0_dev = nullptr;
+            return IWVI_OK;
+        case IWVI_LIK_STUDENT_T:
+            if (!(d->param[0] > 0.f)) { set_error("%s: Student-t scale must be positive", what); return IWVI_ERR_ARG; }
+            if (!(d->param[1] > 0.f)) { set_error("%s: Student-t df must be positive", what); return IWVI_ERR_ARG; }
+            if (need_df2 && !(d->param[1] > 2.f)) { set_error("%s: the Student-t variance needs df > 2 (got %g)", what, (double)d->param[1]); return IWVI_ERR_ARG; }
+            return IWVI_OK;
+        default:
+            set_error("%s: unknown likelihood type %d", what, d->type); return IWVI_ERR_ARG;
+    }
+}
+
+template <int SEG>
+static int launch_lik_elbo(const LikReduceArgs& g, hipStream_t stream) {
+    constexpr int PPP = LIK_THREADS / SEG;
+    const long long blocks = (g.B + PPP - 1) / PPP;
+    hipLaunchKernelGGL(k_lik_elbo<SEG>, dim3((unsigned)blocks), dim3(LIK_THREADS), 0, stream, g);
+    return check_launch("k_lik_elbo");
+}
+
+}  // namespace iwvi
+
+using namespace iwvi;
+
+extern "C" int iwvi_lik_elbo_reduce(const iwvi_lik_desc* lik, const float* fmean, const float* fvar, const float* Y,
+                                    int64_t B, int K, int Dy, int64_t stride_b, int64_t stride_k,
+                                    const float* const* kl_local, const int32_t* kl_dims, int n_kl,
+                                    const double* const* kl_global, const int32_t* kl_global_counts, int n_glob,
+                                    double scale, int K_total, int mode_vi,
+                                    float* out_ms, float* out_logp, double* out_elbo, uint64_t* ticket, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    LikReduceArgs g{};
+    int rc;
+    if ((rc = take_lik(lik, g.lik, "iwvi_lik_elbo_reduce")) != IWVI_OK) return rc;
+    if (!fmean || !fvar || !Y) { set_error("iwvi_lik_elbo_reduce: null input"); return IWVI_ERR_ARG; }
+    if (B <= 0) { set_error("iwvi_lik_elbo_reduce: empty minibatch"); return IWVI_ERR_ARG; }
+    if (K <= 0 || Dy <= 0) { set_error("iwvi_lik_elbo_reduce: bad K=%d or Dy=%d", K, Dy); return IWVI_ERR_ARG; }
+    if (n_kl < 0 || n_kl > IWVI_MAX_KL) { set_error("iwvi_lik_elbo_reduce: %d local regularisers (max %d)", n_kl, IWVI_MAX_KL); return IWVI_ERR_ARG; }
+    if (!out_ms && !out_logp && !out_elbo) { set_error("iwvi_lik_elbo_reduce: no output asked for"); return IWVI_ERR_ARG; }
+    if (out_elbo && (!out_logp || !ticket)) { set_error("iwvi_lik_elbo_reduce: out_elbo needs out_logp (scratch) and a zero-initialised ticket word"); return IWVI_ERR_ARG; }
+    g.fmean = fmean; g.fvar = fvar; g.Y = Y; g.n_kl = n_kl;
+    for (int i = 0; i < n_kl; ++i) {
+        if (!kl_local || !kl_local[i] || !kl_dims || kl_dims[i] <= 0) { set_error("iwvi_lik_elbo_reduce: bad local regulariser %d", i); return IWVI_ERR_ARG; }
+        g.kl[i] = kl_local[i]; g.kl_dims[i] = kl_dims[i];
+    }
+    g.stride_b = stride_b; g.stride_k = stride_k;
+    g.B = B; g.K = K; g.Dy = Dy; g.K_total = K_total > 0 ? K_total : K; g.mode_vi = mode_vi;
+    g.ms = out_ms; g.logp = out_logp; g.elbo = out_elbo; g.ticket = (unsigned long long*)ticket; g.scale = scale;
+    if (out_elbo) {
+        if (n_glob < 0 || n_glob > LIK_MAX_GLOB) { set_error("iwvi_lik_elbo_reduce: too many global KL terms (%d > %d)", n_glob, LIK_MAX_GLOB); return IWVI_ERR_ARG; }
+        for (int i = 0; i < n_glob; ++i) {
+            if (!kl_global || !kl_global[i]) { set_error("iwvi_lik_elbo_reduce: null global KL pointer %d", i); return IWVI_ERR_ARG; }
+            g.klg[i] = kl_global[i];
+            g.klg_n[i] = kl_global_counts ? kl_global_counts[i] : 1;
+            if (g.klg_n[i] <= 0 || g.klg_n[i] > IWVI_MAX_R) { set_error("iwvi_lik_elbo_reduce: bad global KL count %d", g.klg_n[i]); return IWVI_ERR_ARG; }
+        }
+        g.n_glob = n_glob;
+    }
+    if (K <= 4) return launch_lik_elbo<4>(g, stream);
+    if (K <= 8) return launch_lik_elbo<8>(g, stream);
+    if (K <= 16) return launch_lik_elbo<16>(g, stream);
+    if (K <= 32) return launch_lik_elbo<32>(g, stream);
+    return launch_lik_elbo<64>(g, stream);
+}
+
+extern "C" int iwvi_lik_elbo_backward(const iwvi_lik_desc* lik, const float* fmean, const float* fvar, const float* Y, int Dy,
+                                      const float* const* kl_local, const int32_t* kl_dims, int n_local,
+                                      int64_t B, int K, double scale, int mode_vi,
+                                      float* out_w, float* d_mean, float* d_var,
+                                      const double* const* kl_global, const int32_t* kl_global_counts, int n_glob,
+                                      const float* lse_global, int K_total, double* out_sums, double* ws, void* stream_) {
+    LikBwdArgs a{};
+    int rc;
+    if ((rc = take_lik(lik, a.lik, "iwvi_lik_elbo_backward")) != IWVI_OK) return rc;
+    if (!fmean || !fvar || !Y || !out_sums || !ws || Dy <= 0 || B <= 0 || K <= 0 || n_local < 0 || n_local > IWVI_MAX_KL ||
+        n_glob < 0 || n_glob > IWVI_MAX_LAYERS) {
+        set_error("iwvi_lik_elbo_backward: bad argument"); return IWVI_ERR_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream_;
+    a.fmean = fmean; a.fvar = fvar; a.Y = Y; a.Dy = Dy; a.n_kl = n_local;
+    for (int i = 0; i < n_local; ++i) {
+        if (!kl_local || !kl_local[i] || !kl_dims || kl_dims[i] <= 0) { set_error("iwvi_lik_elbo_backward: bad local regulariser %d", i); return IWVI_ERR_ARG; }
+        a.kl[i] = kl_local[i]; a.kl_dims[i] = kl_dims[i];
+    }
+    if (lse_global && (mode_vi || K_total < K)) { set_error("iwvi_lik_elbo_backward: lse_global needs the IW bound and K_total >= K"); return IWVI_ERR_ARG; }
+    LikFinishArgs fa{};
+    fa.part = ws; fa.n = B; fa.scale = scale; fa.n_glob = n_glob; fa.out = out_sums;
+    for (int i = 0; i < n_glob; ++i) {
+        if (!kl_global || !kl_global[i] || !kl_global_counts || kl_global_counts[i] <= 0) { set_error("iwvi_lik_elbo_backward: bad global KL %d", i); return IWVI_ERR_ARG; }
+        fa.klg[i] = kl_global[i]; fa.kln[i] = kl_global_counts[i];
+    }
+    a.B = B; a.K = K; a.scale = scale; a.mode_vi = mode_vi; a.lse_global = lse_global; a.K_total = K_total;
+    a.w = out_w; a.d_mean = d_mean; a.d_var = d_var; a.part = ws;
+    hipLaunchKernelGGL(k_lik_elbo_bwd, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_lik_finish, dim3(1), dim3(256), 0, st, fa);
+    return check_launch("k_lik_elbo_bwd");
+}
+
+template <int MODE>
+static int lik_elementwise(const char* what, const iwvi_lik_desc* lik, const float* Fmu, const float* Fvar, const float* Y, int64_t T, int Dy,
+                           int64_t row_div, int64_t row_mod, float* out, float* out2, void* stream_) {
+    Lik L{};
+    int rc;
+    if ((rc = take_lik(lik, L, what, MODE == 2)) != IWVI_OK) return rc;
+    if (T < 0 || Dy <= 0 || row_div <= 0 || row_mod <= 0) { set_error("%s: bad size", what); return IWVI_ERR_ARG; }
+    if (T == 0) return IWVI_OK;
+    if (!Fmu || !out || (MODE != 1 && !Fvar) || (MODE != 2 && !Y) || (MODE == 2 && !out2)) { set_error("%s: null pointer", what); return IWVI_ERR_ARG; }
+    const long long n = (long long)T * Dy;
+    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    hipLaunchKernelGGL(k_lik_elem<MODE>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, L, Fmu, Fvar, Y, n, Dy,
+                       (long long)row_div, (long long)row_mod, out, out2);
+    return check_launch(what);
+}
+
+extern "C" int iwvi_lik_var_exp(const iwvi_lik_desc* lik, const float* Fmu, const float* Fvar, const float* Y,
+                                int64_t T, int Dy, int64_t row_div, int64_t row_mod, float* out, void* stream_) {
+    return lik_elementwise<0>("iwvi_lik_var_exp", lik, Fmu, Fvar, Y, T, Dy, row_div, row_mod, out, nullptr, stream_);
+}
+
+extern "C" int iwvi_lik_predict_density(const iwvi_lik_desc* lik, const float* Fmu, const float* Fvar, const float* Y,
+                                        int64_t T, int Dy, int64_t row_div, int64_t row_mod, float* out, void* stream_) {
+    return lik_elementwise<1>("iwvi_lik_predict_density", lik, Fmu, Fvar, Y, T, Dy, row_div, row_mod, out, nullptr, stream_);
+}
+
+extern "C" int iwvi_lik_predict_mean_and_var(const iwvi_lik_desc* lik, const float* Fmu, const float* Fvar, int64_t n,
+                                             float* out_mean, float* out_var, void* stream_) {
+    return lik_elementwise<2>("iwvi_lik_predict_mean_and_var", lik, Fmu, Fvar, nullptr, n, 1, 1, 1, out_mean, out_var, stream_);
+}

@@ -4,8 +4,8 @@ The layer kernel's hot variants sit at the 256-VGPR limit: a source change anywh
 scratch, and a variant that only the large configs take then regresses unnoticed (round 4: the five-sub-tile large-M variant went
 216 B into scratch, configs[3] 1.27 -> 1.43 ms, for four commits).  ``check()`` is run by ``__graft_entry__.build()`` and by
 tests/test_kernel_resources.py: it fails when a ``k_dgp_forward`` or ``k_bw_chain`` instantiation (the predictive and sampling variants of the
-forward included) or ``k_sample_stats`` uses scratch memory
-(``.private_segment_fixed_size`` > 0) beyond what ``ALLOWED_SCRATCH`` lists, or when a listed spill count grows.
+forward included), ``k_sample_stats`` or a likelihood-tail kernel (every ``k_lik_*``) uses scratch memory
+(``.private_segment_fixed_size`` > 0) beyond what ``ALLOWED_SCRATCH`` lists, when a listed spill count grows, or when a kernel listed in ``MAX_VGPRS`` exceeds its VGPR ceiling.
 
   python -m dgps_with_iwvi_amd.kernel_resources [--write profiles/<tag>_kernel_resources.txt]
 """
@@ -25,7 +25,8 @@ FIELDS = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_sp
           "group_segment_fixed_size", "max_flat_workgroup_size")
 
 # kernels whose instantiations must not touch scratch memory at all ...
-NO_SCRATCH = ("k_dgp_forward", "k_bw_chain", "k_sample_stats")
+# (k_lik_*: csrc/likelihood_tail.hip -- twenty quadrature nodes unrolled per element: no scratch, and a VGPR ceiling each, MAX_VGPRS below)
+NO_SCRATCH = ("k_dgp_forward", "k_bw_chain", "k_sample_stats", "k_lik_elbo", "k_lik_elbo_bwd", "k_lik_elem", "k_lik_finish")
 # ... except these (demangled-name substring -> bytes of scratch it is known to use; lower it when a kernel improves)
 ALLOWED_SCRATCH = {
     # round 6 (profiles/r06_kernel_resources.txt): every BIG variant (some layer with M > 128: configs[3] / [4]) and every float64-route
@@ -43,6 +44,12 @@ ALLOWED_SCRATCH = {
 MAX_SPILLS = {
     "k_precompute": (0, 760),
 }
+
+
+# VGPR ceilings (kernel name before its template arguments -> most VGPRs any instantiation may use).  The likelihood-tail kernels are latency
+# chains of transcendental evaluations: 128 VGPRs keep four waves on a SIMD (512 per lane) to hide them.  Today: k_lik_elbo 80, k_lik_elbo_bwd 115,
+# k_lik_elem 19-65, k_lik_finish 12.
+MAX_VGPRS = {"k_lik_elbo": 128, "k_lik_elbo_bwd": 128, "k_lik_elem": 128, "k_lik_finish": 32}
 
 
 def csrc_hash():
@@ -128,6 +135,9 @@ def check(rows=None):
                 if r.get("private_segment_fixed_size", 0) > allowed:
                     bad.append("%s: %d B of scratch per lane (allowed %d; %d VGPR / %d SGPR spills)" % (
                         d, r["private_segment_fixed_size"], allowed, r.get("vgpr_spill_count", 0), r.get("sgpr_spill_count", 0)))
+        cap = MAX_VGPRS.get(d.split("<")[0])
+        if cap is not None and r.get("vgpr_count", 0) > cap:
+            bad.append("%s: %d VGPRs (budget %d)" % (d, r.get("vgpr_count", 0), cap))
         for s, (mv, ms) in MAX_SPILLS.items():
             if s == d and (r.get("vgpr_spill_count", 0) > mv or r.get("sgpr_spill_count", 0) > ms):
                 bad.append("%s: %d VGPR / %d SGPR spills (budget %d / %d)" % (d, r.get("vgpr_spill_count", 0), r.get("sgpr_spill_count", 0), mv, ms))

@@ -26,12 +26,16 @@ class DeviceScalarVariance:
     _var_dev = None
     _var_stale = False
 
-    @property
-    def variance(self):
+    def host_value(self):
+        """The host copy, refreshed from the device master when that has moved since the last read."""
         if self._var_dev is not None and self._var_stale:
             self._var_host = float(self._var_dev.item())
             self._var_stale = False
         return self._var_host
+
+    @property
+    def variance(self):
+        return self.host_value()
 
     @variance.setter
     def variance(self, v):

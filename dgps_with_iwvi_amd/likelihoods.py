@@ -1,17 +1,84 @@
-"""Gaussian likelihood (reference: experiments/build_models.py:198-199; models.py:66,105,134).
-On the hot path ``variational_expectations`` is fused into the tail of ``iwvi_dgp_forward``; the method here is the
+"""Likelihoods (GPflow-1.x ``gpflow.likelihoods`` counterparts; reference: experiments/build_models.py:198-199; models.py:66,105,134).
+
+``Gaussian``: on the hot path ``variational_expectations`` is fused into the tail of ``iwvi_dgp_forward``; the method here is the
 reference's callable form on explicit moments (``iwvi_gaussian_var_exp``); ``logp`` / ``predict_density`` run
-``iwvi_gaussian_log_density``."""
+``iwvi_gaussian_log_density``.
+
+``Bernoulli`` (probit link) and ``StudentT`` are the non-conjugate ones: their expectations are GPflow's 20-point Gauss-Hermite rule,
+evaluated by the kernels of ``csrc/likelihood_tail.hip`` (``iwvi_lik_*``).  A model with one of them runs the layer launch without its
+Gaussian tail and ``iwvi_lik_elbo_reduce`` / ``iwvi_lik_elbo_backward`` on the final layer's moments (models.py, backward.py).
+
+Every likelihood answers ``lik_desc()`` (the ``iwvi_lik_desc`` of its current parameters), ``grad_name`` (the key of its trained scalar's
+gradient in ``backward.iw_elbo_and_gradients``, or None) and ``trained_scalar()`` (what a ``training.Trainer`` puts among its Adam
+scalars: (gradient name, value), or None)."""
+import math
+
 import torch
 
 from . import _abi, settings
 from .kernels import DeviceScalarVariance
 
 
+def _moments(Fmu, Fvar, Y):
+    """(Fmu, Fvar or None, Y or None, T, Dy) as contiguous device tensors of Fmu's shape."""
+    Fmu = _abi.dev_tensor(torch.as_tensor(Fmu).contiguous(), "Fmu")
+    if Fvar is not None:
+        Fvar = _abi.dev_tensor(torch.as_tensor(Fvar, device=Fmu.device).expand_as(Fmu).contiguous(), "Fvar")
+    if Y is not None:
+        Y = _abi.dev_tensor(torch.as_tensor(Y, dtype=settings.float_type, device=Fmu.device).expand_as(Fmu).contiguous(), "Y")
+    Dy = Fmu.shape[-1] if Fmu.dim() else 1
+    return Fmu, Fvar, Y, Fmu.numel() // max(Dy, 1), Dy
+
+
+class _QuadratureLikelihood:
+    """The methods of a likelihood whose arithmetic lives in ``csrc/likelihood_tail.hip``."""
+
+    def variational_expectations(self, Fmu, Fvar, Y):
+        """E_{N(f; Fmu, Fvar)} logp(f, Y), elementwise, by the 20-point Gauss-Hermite rule (GPflow 1.x ``ndiagquad``; models.py:66,134)."""
+        Fmu, Fvar, Y, T, Dy = _moments(Fmu, Fvar, Y)
+        out = torch.empty_like(Fmu)
+        d = self.lik_desc()
+        _abi.check(_abi.lib().iwvi_lik_var_exp(d, _abi.ptr(Fmu), _abi.ptr(Fvar), _abi.ptr(Y), T, Dy, 1, max(T, 1), _abi.ptr(out), _abi.stream_ptr()))
+        return out
+
+    def _density(self, Fmu, Fvar, Y):
+        Fmu, Fvar, Y, T, Dy = _moments(Fmu, Fvar, Y)
+        out = torch.empty_like(Fmu)
+        d = self.lik_desc()
+        _abi.check(_abi.lib().iwvi_lik_predict_density(d, _abi.ptr(Fmu), _abi.ptr(Fvar), _abi.ptr(Y), T, Dy, 1, max(T, 1), _abi.ptr(out),
+                                                       _abi.stream_ptr()))
+        return out
+
+    def logp(self, F, Y):
+        return self._density(F, None, Y)
+
+    def predict_density(self, Fmu, Fvar, Y):
+        return self._density(Fmu, Fvar, Y)
+
+    def predict_mean_and_var(self, Fmu, Fvar):
+        Fmu, Fvar, _, _, _ = _moments(Fmu, Fvar, None)
+        m, v = torch.empty_like(Fmu), torch.empty_like(Fmu)
+        d = self.lik_desc()
+        _abi.check(_abi.lib().iwvi_lik_predict_mean_and_var(d, _abi.ptr(Fmu), _abi.ptr(Fvar), Fmu.numel(), _abi.ptr(m), _abi.ptr(v),
+                                                            _abi.stream_ptr()))
+        return m, v
+
+
 class Gaussian(DeviceScalarVariance):
     def __init__(self, variance=1.0, name=None):
         self.variance = float(variance)
         self.name = name
+
+    def lik_desc(self):
+        d = _abi.LikDesc()
+        d.type = _abi.LIK_GAUSSIAN
+        d.param[0], d.param0_dev = self.desc_variance()
+        return d
+
+    grad_name = "lik_var"
+
+    def trained_scalar(self):
+        return self.grad_name, self.variance
 
     def variational_expectations(self, Fmu, Fvar, Y):
         """E_{N(f; Fmu, Fvar)} log N(Y; f, variance), elementwise (gpflow 1.x Gaussian; called at models.py:66,134)."""
@@ -47,3 +114,82 @@ class Gaussian(DeviceScalarVariance):
     def predict_density(self, Fmu, Fvar, Y):
         """log N(Y; Fmu, Fvar + variance), elementwise (gpflow 1.x Gaussian.predict_density)."""
         return self._log_density(Fmu, Fvar, Y)
+
+
+class Bernoulli(_QuadratureLikelihood):
+    """gpflow 1.x ``Bernoulli(invlink=inv_probit)``: p = Phi(F) (1 - 2e-3) + 1e-3, logp = log p if Y == 1 else log(1 - p).
+    ``predict_mean_and_var`` and ``predict_density`` are the probit link's closed forms at p = inv_probit(Fmu / sqrt(1 + Fvar))."""
+
+    def __init__(self, invlink=None, name=None):
+        if invlink is not None and getattr(invlink, "__name__", invlink) != "inv_probit":
+            raise NotImplementedError("Bernoulli(invlink=%r): only the probit link (GPflow's default, inv_probit) is implemented"
+                                      % (getattr(invlink, "__name__", invlink),))
+        self.name = name
+
+    def lik_desc(self):
+        d = _abi.LikDesc()
+        d.type = _abi.LIK_BERNOULLI_PROBIT
+        return d
+
+    grad_name = None
+
+    def trained_scalar(self):
+        return None
+
+    def check_targets(self, Y):
+        """Labels must be exactly 0 or 1: ``logp`` takes ``Y == 1`` for class 1 and EVERYTHING else (0.999, -1, 2) for class 0, as GPflow
+        does, silently.  The models call this once on the host when they are built."""
+        import numpy as np
+        Yh = Y.detach().cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
+        bad = ~((Yh == 0) | (Yh == 1))
+        if bad.any():
+            raise ValueError("Bernoulli: targets must be 0 or 1; %d of %d are not (first: %r)" % (int(bad.sum()), Yh.size, Yh[bad].ravel()[0]))
+
+
+def inv_probit(x):
+    """GPflow's probit link with its jitter, on torch tensors (the name ``Bernoulli(invlink=...)`` accepts)."""
+    return 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0))) * (1 - 2e-3) + 1e-3
+
+
+class StudentT(_QuadratureLikelihood, DeviceScalarVariance):
+    """gpflow 1.x ``StudentT(scale=1.0, df=3.0)``: ``scale`` is trainable (positive), ``df`` is fixed.  Everything but ``logp`` is
+    quadrature; ``predict_mean_and_var`` needs df > 2."""
+    # GPflow's name for the one trained scalar: the lazily refreshed host copy / device master of DeviceScalarVariance
+    scale = property(DeviceScalarVariance.host_value, DeviceScalarVariance.variance.fset)
+
+    def __init__(self, scale=1.0, df=3.0, name=None):
+        if not float(scale) > 0.0:
+            raise ValueError("StudentT: scale must be positive, got %r" % (scale,))
+        if not float(df) > 0.0:
+            raise ValueError("StudentT: df must be positive, got %r" % (df,))
+        self.scale = float(scale)
+        self.df = float(df)
+        self.name = name
+
+    @property
+    def variance(self):
+        raise AttributeError("StudentT has no 'variance': its parameters are 'scale' and 'df'")
+
+    def lik_desc(self):
+        d = _abi.LikDesc()
+        d.type = _abi.LIK_STUDENT_T
+        d.param[0], d.param0_dev = self.desc_variance()
+        d.param[1] = self.df
+        d.lgc = math.lgamma(0.5 * (self.df + 1.0)) - math.lgamma(0.5 * self.df)
+        return d
+
+    grad_name = "lik_scale"
+
+    def trained_scalar(self):
+        return self.grad_name, self.scale
+
+    def predict_mean_and_var(self, Fmu, Fvar):
+        if not self.df > 2.0:
+            raise ValueError("StudentT.predict_mean_and_var: the variance needs df > 2 (df = %g)" % self.df)
+        return super().predict_mean_and_var(Fmu, Fvar)
+
+
+def is_gaussian(likelihood):
+    """True when the models take the Gaussian routes (the fused tail and heads) for this likelihood: exactly the class above, or an
+    object without the protocol that quacks like it (``variance`` / ``desc_variance``, as before the protocol existed)."""
+    return isinstance(likelihood, Gaussian) or not hasattr(likelihood, "lik_desc")

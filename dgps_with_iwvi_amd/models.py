@@ -9,6 +9,10 @@ encoders of the latent-variable layers) and ``iwvi_dgp_forward``, whose workgrou
 tiling of X/Y over K, every layer, the Gaussian variational expectation and the local regularisers in LDS; the last workgroup
 to finish does the log-sum-exp over K, the scaled sum and subtracts the global KLs.
 
+A likelihood other than the Gaussian (``likelihoods.Bernoulli`` / ``StudentT``) takes THREE: the layer launch runs without its tail and leaves
+the final layer's moments and the local regularisers, ``iwvi_lik_elbo_reduce`` does the rest (Gauss-Hermite variational expectations, the
+log-sum-exp, the bound).  For a Gaussian nothing differs from the two-launch form.
+
 Differences from the reference, all documented in DESIGN.md:
   * ``zs`` (one N(0,1) array or None per layer) injects the noise tf.random_normal draws in-graph; None
     draws inside the kernel from a counter-based Philox stream (``settings.seed``, per-model step counter);
@@ -27,6 +31,7 @@ import torch
 
 from . import _abi, settings
 from .layers import GPLayer, LatentVariableLayer, RegularizerType
+from .likelihoods import is_gaussian
 from .temp_workaround import draw_normal, precompute_states
 
 
@@ -38,6 +43,8 @@ def _data(x):
 class DGP_VI:
     def __init__(self, X, Y, layers, likelihood, num_samples=1, minibatch_size=None, name=None):
         self.likelihood = likelihood
+        if hasattr(likelihood, "check_targets"):                      # (a Bernoulli refuses labels other than 0 / 1 here, once, on the host)
+            likelihood.check_targets(Y)
         self.num_data = X.shape[0]                                    # models.py:18
         self.num_samples = num_samples
         self._X_all, self._Y_all = _data(X), _data(Y)
@@ -186,7 +193,7 @@ class DGP_VI:
     # -- fused forward ------------------------------------------------------------------------
     def _fused_forward(self, T, row_div, row_mod, lead, zs=None, sampled_kl=True, want_layers=False,
                        want_logw=True, use_encoder=True, elbo=None, stack_from=0, want_saved=False, outputs_for=None, moments=True,
-                       X=None, Y=None, predict=None):
+                       X=None, Y=None, predict=None, local_kls=False):
         """``iwvi_dgp_forward`` over the current minibatch: every layer + log-weights in one launch.
         Row t of the flattened batch reads data row (t // row_div) % row_mod.  ``elbo`` = dict(B, K, stride_b,
         stride_k, mode_vi, want_ms, K_total): also run the reduction of models.py:138-150 in the tail of the
@@ -199,8 +206,15 @@ class DGP_VI:
         ``X`` / ``Y``: explicit inputs and targets in place of the current minibatch.  ``predict`` = dict(S, out): run
         ``iwvi_dgp_predict_density`` instead (rows t = n S + s, latent-variable layers in prior mode: ``use_encoder=False``),
         writing the per-point Monte Carlo log predictive density into ``out`` [N]; ``predict`` = dict(S, out_y[, z_y]): run
-        ``iwvi_dgp_predict_samples`` -- the same rows, y samples into ``out_y`` [N, S, Dy] (``z_y`` [N S, Dy]: the likelihood's noise)."""
+        ``iwvi_dgp_predict_samples`` -- the same rows, y samples into ``out_y`` [N, S, Dy] (``z_y`` [N S, Dy]: the likelihood's noise).
+        ``local_kls`` (with ``outputs_for``): a latent-variable layer outside ``outputs_for`` still writes its regulariser (nothing else).
+        The tail of the launch (``want_logw`` with targets, ``elbo``, ``predict``) is Gaussian: other likelihoods call it without one."""
         dev = self.X.device
+        gauss = is_gaussian(self.likelihood)
+        if not gauss and (want_logw or elbo is not None or predict is not None):
+            raise NotImplementedError("the fused tail of iwvi_dgp_forward is Gaussian; %s goes through the layer launch + iwvi_lik_elbo_reduce"
+                                      % type(self.likelihood).__name__)
+        lik_host, lik_dev = self.likelihood.desc_variance() if gauss else (1.0, None)
         layers = self.layers[stack_from:]
         n = len(layers)
         if n > _abi.MAX_STACK:
@@ -244,10 +258,11 @@ class DGP_VI:
                 Lw = layer.latent_dim
                 z2 = None if z is None else _abi.dev_tensor(z.reshape(T, Lw).contiguous(), "z")
                 o = None
-                if want_layers and (outputs_for is None or i in outputs_for):
-                    o = {k: torch.empty(*lead, D + Lw, dtype=settings.float_type, device=dev) for k in ("sample", "mean", "var")} if moments else {}
+                listed = outputs_for is None or i in outputs_for
+                if want_layers and (listed or local_kls):
+                    o = {k: torch.empty(*lead, D + Lw, dtype=settings.float_type, device=dev) for k in ("sample", "mean", "var")} if (moments and listed) else {}
                     o["kl_local"] = torch.empty(*lead, Lw, dtype=settings.float_type, device=dev)
-                    if want_saved:
+                    if want_saved and listed:
                         o["noise_out"] = torch.empty(T, Lw, dtype=settings.float_type, device=dev)
                 # encoder output of THIS minibatch from the last precompute launch, if there is one
                 eo = layer._enc_out if (use_encoder and getattr(layer, "_enc_key", None) == self._mb_key()) else None
@@ -265,7 +280,6 @@ class DGP_VI:
         words = self._words()
         if predict is not None and "out_y" in predict:
             N, S, out_y, z_y = X.shape[0], predict["S"], predict["out_y"], predict.get("z_y")
-            lik_host, lik_dev = self.likelihood.desc_variance()
             _abi.check(_abi.lib().iwvi_dgp_predict_samples(descs, n, _abi.ptr(X), X.shape[1], out_y.shape[-1], N, S, lik_host, lik_dev,
                                                            _abi.ptr(z_y), settings.seed, ctypes.c_void_p(words.data_ptr() + 8),
                                                            _abi.ptr(out_y), _abi.stream_ptr()))
@@ -273,7 +287,6 @@ class DGP_VI:
         if predict is not None:
             N, S, out = X.shape[0], predict["S"], predict["out"]
             ws = torch.empty((_abi.lib().iwvi_dgp_predict_density_ws_bytes(N, S) + 3) // 4, dtype=torch.float32, device=dev)
-            lik_host, lik_dev = self.likelihood.desc_variance()
             _abi.check(_abi.lib().iwvi_dgp_predict_density(descs, n, _abi.ptr(X), X.shape[1], _abi.ptr(Y), Y.shape[1], N, S,
                                                            lik_host, lik_dev, settings.seed, ctypes.c_void_p(words.data_ptr() + 8),
                                                            _abi.ptr(out), _abi.ptr(ws), _abi.stream_ptr()))
@@ -302,7 +315,7 @@ class DGP_VI:
             ed.scale = float(self.num_data) / float(B)                     # models.py:80-81, :144-145
             ed.K_total, ed.mode_vi = elbo.get("K_total") or K, 1 if elbo["mode_vi"] else 0
             ed.out_lse_ms = None if ms is None else ms.data_ptr()
-            ed.lik_variance_dev = self.likelihood.desc_variance()[1]
+            ed.lik_variance_dev = lik_dev
             ws = torch.empty((T + 15) // 16, dtype=torch.float64, device=dev)
             ed.out_logp, ed.out_elbo, ed.ws = logp.data_ptr(), val.data_ptr(), ws.data_ptr()
             adj = elbo.get("adj")                                # heads of the bound's adjoint from the same launch (backward.py)
@@ -315,7 +328,7 @@ class DGP_VI:
             red = (val[0], logp, ms)
         args = (descs, n, _abi.ptr(X), X.shape[1], _abi.ptr(XY), 0 if XY is None else XY.shape[1],
                 _abi.ptr(Y) if want_logw else None, Y.shape[1], T, row_div, row_mod,
-                self.likelihood.desc_variance()[0] if (ed is not None or not want_logw) else self.likelihood.variance,
+                lik_host if (ed is not None or not want_logw) else self.likelihood.variance,
                 settings.seed, ctypes.c_void_p(words.data_ptr() + 8), _abi.ptr(logw),
                 None if ed is None else ctypes.byref(ed), _abi.stream_ptr())
         _abi.check(_abi.lib().iwvi_dgp_forward(*args))
@@ -360,7 +373,7 @@ class DGP_VI:
         return elbo[0], logp, ms
 
     def _reduce(self, fmean, fvar, Y, local_kls, global_kls, B, K, stride_b, stride_k, mode_vi,
-                want_ms=False, K_total=None):
+                want_ms=False, K_total=None, ms_out=None, elbo_out=None):
         """``iwvi_iw_elbo_reduce`` on explicit final-layer moments (the layer-by-layer path)."""
         dev = fmean.device
         Dy = Y.shape[-1]
@@ -375,10 +388,23 @@ class DGP_VI:
         glob_n = (ctypes.c_int32 * max(len(glob), 1))(*[g.numel() for g in glob])
         logp = torch.empty(B, dtype=settings.float_type, device=dev)
         elbo = torch.empty(1, dtype=torch.float64, device=dev)
-        ms = torch.empty(B, 2, dtype=settings.float_type, device=dev) if want_ms else None
+        ms = torch.empty(B, 2, dtype=settings.float_type, device=dev) if (want_ms and ms_out is None) else None
         scale = float(self.num_data) / float(B)                        # models.py:80-81, :144-145
         # (a trained likelihood variance is read on the device: no device-to-host copy here -- there must be none inside a captured step --
         #  and a replayed graph follows the value)
+        if not is_gaussian(self.likelihood):                            # the same reduction with the likelihood's own expectation
+            if ms_out is not None:
+                ms = _abi.dev_tensor(ms_out, "ms_out", settings.float_type)
+                if tuple(ms.shape) != (B, 2):
+                    raise ValueError("ms_out must be [B, 2]")
+            if elbo_out is not None:
+                elbo = _abi.dev_tensor(elbo_out.view(-1), "elbo_out", torch.float64)
+            _abi.check(_abi.lib().iwvi_lik_elbo_reduce(
+                self.likelihood.lik_desc(), _abi.ptr(fmean), _abi.ptr(fvar), _abi.ptr(Y), B, K, Dy,
+                stride_b, stride_k, _abi.ptr_array(kls), kl_dims, len(kls), _abi.ptr_array(glob), glob_n, len(glob),
+                scale, K_total or K, 1 if mode_vi else 0, _abi.ptr(ms), _abi.ptr(logp), _abi.ptr(elbo),
+                _abi.ptr(self._words()), _abi.stream_ptr()))
+            return elbo[0], logp, ms
         lik_host, lik_dev = self.likelihood.desc_variance()
         _abi.check(_abi.lib().iwvi_iw_elbo_reduce_dev(
             _abi.ptr(fmean), _abi.ptr(fvar), _abi.ptr(Y), lik_host, lik_dev, B, K, Dy,
@@ -387,10 +413,22 @@ class DGP_VI:
             _abi.ptr(self._words()), _abi.stream_ptr()))
         return elbo[0], logp, ms
 
+    def _moments_then_reduce(self, T, row_div, row_mod, lead, zs, sampled_kl, red):
+        """A likelihood without a fused tail (the caller has run ``precompute``): the layer launch leaves the final layer's moments and every
+        local regulariser -- nothing else reaches memory --, ``_reduce(**red)`` finishes (``iwvi_lik_elbo_reduce``)."""
+        last = len(self.layers) - 1
+        _, outs, _ = self._fused_forward(T, row_div, row_mod, lead, zs=zs, sampled_kl=sampled_kl, want_layers=True, want_logw=False,
+                                         outputs_for={last}, local_kls=True)
+        local_kls = [o["kl_local"].reshape(T, -1) for o, l in zip(outs, self.layers) if l.regularizer_type is RegularizerType.LOCAL]
+        return self._reduce(outs[last]["mean"].reshape(T, -1), outs[last]["var"].reshape(T, -1), self.Y, local_kls, self._global_kls(), **red)
+
     def _build_likelihood(self, zs=None):
         """The VI bound, reference models.py:49-86 (2-D [S*N, D] tiling, mean over S)."""
         S, N = self.num_samples, self.X.shape[0]
         self.precompute(with_encoders=True)
+        if not is_gaussian(self.likelihood):
+            return self._moments_then_reduce(S * N, 1, N, (S * N,), zs, False,
+                                             dict(B=N, K=S, stride_b=1, stride_k=N, mode_vi=True))[0]
         # tile(X, [S, 1]) (:50-53): row t = s*N + n reads data row t % N; analytic local KL (:58-61)
         _, _, red = self._fused_forward(S * N, 1, N, (S * N,), zs=zs, sampled_kl=False,
                                         elbo=dict(B=N, K=S, stride_b=1, stride_k=N, mode_vi=True))
@@ -460,6 +498,20 @@ class DGP_VI:
         if Y.dim() != 2 or Y.shape[0] != X.shape[0] or Y.shape[1] != Dy:
             raise ValueError("Y must be [%d, %s], got %s" % (X.shape[0], Dy, tuple(Y.shape)))
         N = X.shape[0]
+        if not is_gaussian(self.likelihood):
+            # logsumexp_s sum_d predict_density(m_s, v_s, Y) - log S over predict_f_multisample's draws (layer-by-layer launches; the
+            # one-launch route is the Gaussian's)
+            zs = self._check_predict_noise("predict_log_density", S, N, zs)
+            bs = int(batch_size or max(N, 1))
+            if bs < 1:
+                raise ValueError("batch_size must be >= 1")
+            out = torch.empty(N, dtype=settings.float_type, device=X.device)
+            for lo in range(0, N, bs):
+                hi = min(N, lo + bs)
+                m, v = self.predict_f_multisample(X[lo:hi], S, zs=[None if z is None else _data(z)[:, lo:hi] for z in zs])
+                lp = self.likelihood.predict_density(m, v, Y[None, lo:hi].expand_as(m)).sum(-1)
+                out[lo:hi] = torch.logsumexp(lp, 0) - float(np.log(S))
+            return out
         zs = self._check_predict_noise("predict_log_density", S, N, zs)
         bs = batch_size or max(1, self._PREDICT_ROWS // S)
         if bs < 1:
@@ -496,6 +548,9 @@ class DGP_VI:
         ``zs``: one [S, N, dim] array or None per layer, ``z_y`` [S, N, Dy] the likelihood's noise -- with both given the result is
         ``predict_y_samples(X, S, zs, z_y)``; what is not given is drawn in the kernel.  The result is a transposed view of the kernel's
         [N, S, Dy], in which a point's S samples are contiguous (what ``evaluation.sample_stats`` reads fastest)."""
+        if not is_gaussian(self.likelihood):
+            raise NotImplementedError("predict_y_samples_fused adds Gaussian noise in the launch's tail; with %s use predict_y_samples "
+                                      "(layer by layer, the likelihood's predict_mean_and_var)" % type(self.likelihood).__name__)
         X = _data(X)
         S = int(S)
         if S < 1:
@@ -563,7 +618,8 @@ class DGP_IWVI(DGP_VI):
                 cov = torch.diagonal(cov, dim1=-2, dim2=-1).transpose(1, 2).contiguous()  # :133
             return means[-1], cov, local_kls, global_kls, samples, means, covs
         self.precompute(with_encoders=True)
-        _, outs, _ = self._fused_forward(B * K, K, B, (B, K), zs=zs, sampled_kl=True, want_layers=True)
+        _, outs, _ = self._fused_forward(B * K, K, B, (B, K), zs=zs, sampled_kl=True, want_layers=True,
+                                         want_logw=is_gaussian(self.likelihood))
         samples, means, covs = ([o[k] for o in outs] for k in ("sample", "mean", "var"))
         local_kls = [o["kl_local"] for o, l in zip(outs, self.layers) if l.regularizer_type is RegularizerType.LOCAL]
         return means[-1], covs[-1], local_kls, self._global_kls(), samples, means, covs
@@ -573,6 +629,9 @@ class DGP_IWVI(DGP_VI):
         B, K = self.X.shape[0], self.num_samples
         if self._literal():
             return None
+        if not is_gaussian(self.likelihood):
+            raise NotImplementedError("the per-sample log-weights come out of the Gaussian tail of the layer launch; E_log_p_Y / "
+                                      "lse_partials give the reduced forms for %s" % type(self.likelihood).__name__)
         self.precompute(with_encoders=True)
         return self._fused_forward(B * K, K, B, (B, K), zs=zs, sampled_kl=True)[0]
 
@@ -581,7 +640,13 @@ class DGP_IWVI(DGP_VI):
         if self._literal():                                          # literal reference path, layer by layer
             fmean, fvar, local_kls, global_kls, _, _, _ = self._forward_iw(zs, _last_sample=False)
             return self._reduce(fmean, fvar, self.Y, local_kls, global_kls, B, K, stride_b=K, stride_k=1,
-                                mode_vi=False, want_ms=want_ms, K_total=K_total)
+                                mode_vi=False, want_ms=want_ms, K_total=K_total,
+                                **({} if is_gaussian(self.likelihood) else dict(ms_out=ms_out, elbo_out=elbo_out)))
+        if not is_gaussian(self.likelihood):                         # three launches: precompute, layers, iwvi_lik_elbo_reduce
+            self.precompute(with_encoders=True)
+            return self._moments_then_reduce(B * K, K, B, (B * K,), zs, True,
+                                             dict(B=B, K=K, stride_b=K, stride_k=1, mode_vi=False, want_ms=want_ms, K_total=K_total,
+                                                  ms_out=ms_out, elbo_out=elbo_out))
         el = dict(B=B, K=K, stride_b=K, stride_k=1, mode_vi=False, want_ms=want_ms, K_total=K_total,
                   ms_out=ms_out, elbo_out=elbo_out)
         if self.lv_in_precompute and isinstance(self.layers[0], LatentVariableLayer) and (zs is None or zs[0] is None):

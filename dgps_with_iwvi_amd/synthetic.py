@@ -94,8 +94,9 @@ def make_noise(spec, seed=1, K=None, B=None):
     return zs
 
 
-def build_model(spec, device=None, cls=None, num_samples=None, minibatch=True):
-    """Device model (this package's layers/models) from a spec.  X, Y = the first B rows."""
+def build_model(spec, device=None, cls=None, num_samples=None, minibatch=True, likelihood=None):
+    """Device model (this package's layers/models) from a spec.  X, Y = the first B rows.  ``likelihood``: a likelihood object in place
+    of ``Gaussian(spec["lik_var"])``."""
     import torch
     from . import settings
     from .features import InducingPoints, MixedKernelSharedMof
@@ -128,7 +129,7 @@ def build_model(spec, device=None, cls=None, num_samples=None, minibatch=True):
         layers.append(layer.to(device))
     B = spec["B"]
     cls = cls or DGP_IWVI
-    m = cls(spec["X"][:B], spec["Y"][:B], layers, Gaussian(spec["lik_var"]),
+    m = cls(spec["X"][:B], spec["Y"][:B], layers, Gaussian(spec["lik_var"]) if likelihood is None else likelihood,
             num_samples=spec["K"] if num_samples is None else num_samples)
     m.num_data = spec["n_data"]
     return m.to(device)

@@ -5,7 +5,7 @@ decay).  Each op evaluates the IW-ELBO and its gradient on its own fresh samples
 
 Trainable set as built by ``build_models.py`` with its defaults (``fix_linear=True``): inner layers Z, lengthscales,
 q_mu, q_sqrt (kernel variance fixed, :213; W and the linear mean function's A too unless ``fix_linear=False``, :224-227); final layer Z, lengthscales,
-kernel variance; encoders; the likelihood variance.  Gradients: ``backward.iw_elbo_and_gradients``; update rules:
+kernel variance; encoders; the likelihood variance (a Student-t likelihood: its scale; a Bernoulli: nothing).  Gradients: ``backward.iw_elbo_and_gradients``; update rules:
 ``iwvi_natgrad_step`` / ``iwvi_adam_step`` (csrc/backward.hip)."""
 import ctypes
 
@@ -175,10 +175,18 @@ class Trainer:
                     self._entries.append(("l%d.W" % i, l.kern.W, 0))
                 if l.mean_function.mf_type == _abi.MF_LINEAR:
                     self._entries.append(("l%d.mfA" % i, l.mean_function.A, 0))
-        t = torch.full((1,), model.likelihood.variance, dtype=ft, device=dev)
-        self._entries.append(("lik_var", t, 1))
-        model.likelihood.bind_device_variance(t)
-        self._scalars.append((t, model.likelihood))
+        # the likelihood's trained scalar, if it has one (Gaussian: its variance, 'lik_var'; Student-t: its scale; Bernoulli: none)
+        lik = model.likelihood
+        lik_par = lik.trained_scalar() if hasattr(lik, "trained_scalar") else ("lik_var", lik.variance)
+        if lik_par is not None:
+            t = torch.full((1,), lik_par[1], dtype=ft, device=dev)
+            self._entries.append((lik_par[0], t, 1))
+            lik.bind_device_variance(t)
+            self._scalars.append((t, lik))
+        from .likelihoods import is_gaussian
+        if shard == "k" and not is_gaussian(lik):
+            raise NotImplementedError("K-sharded training (shard='k') needs the Gaussian likelihood; %s trains on one rank or N-sharded"
+                                      % type(lik).__name__)
         for name, t, _ in self._entries:
             _abi.dev_tensor(t, name)
         self._state = [tuple(torch.empty_like(t) for _ in range(3)) for _, t, _ in self._entries]
@@ -365,7 +373,7 @@ class Trainer:
 
     def sync_scalars(self):
         """Refresh the host copies of the device-resident scalars now (otherwise: lazily, on first read)."""
-        return [owner.variance for _, owner in self._scalars]
+        return [owner.host_value() for _, owner in self._scalars]
 
     # -- checkpoint / resume (reference: gpflow Saver of the whole session, run_conditional_density_estimation.py:95-125) --
     def state_dict(self):

@@ -27,9 +27,9 @@
 extern "C" {
 #endif
 
-/* 19, with an additive extension: iwvi_dgp_predict_samples and iwvi_sample_stats were added without a change to any existing entry point
- * or struct, so the number did not move and a caller built against 19 keeps working.  A C caller that wants the two symbols looks them up
- * (dlsym), Python asks hasattr(lib, ...). */
+/* 19, with additive extensions: iwvi_dgp_predict_samples and iwvi_sample_stats, then the iwvi_lik_* entry points (likelihoods other than
+ * the Gaussian), were added without a change to any existing entry point or struct, so the number did not move and a caller built against
+ * 19 keeps working.  A C caller that wants the new symbols looks them up (dlsym), Python asks hasattr(lib, ...). */
 #define IWVI_ABI_VERSION 19
 
 enum {
@@ -625,6 +625,59 @@ int iwvi_dgp_predict_samples(const iwvi_layer_desc* layers_host, int n_layers, c
 int iwvi_sample_stats(const float* samples, int64_t sample_stride, int64_t point_stride, const float* y, int64_t N, int S,
                       const double* sw_coef, const double* probs, int n_probs, float* out_logp, float* out_sqerr,
                       float* out_mean_std, float* out_W, float* out_quantiles, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Likelihoods other than the Gaussian (additive extension of ABI 19; csrc/likelihood_tail.hip).  The reference hands ANY GPflow-1.x
+ * likelihood object to its models and calls variational_expectations (models.py:66,134) and predict_mean_and_var (:105) on it.  The
+ * non-conjugate ones integrate by Gauss-Hermite quadrature, GPflow's ndiagquad with its default 20 points:
+ *   f_i = mu + sqrt(2 v) x_i,  E[g] = sum_i w_i g(f_i)   (x_i, w_i sqrt(pi)) = hermgauss(20);  the rule defines the result.
+ * type         logp(F, Y)
+ *   GAUSSIAN   log N(Y; F, param[0])                                     param[0] = variance   (through the same rule, which is exact for a
+ *              quadratic up to rounding: a cross-check of these kernels against the fused Gaussian tail -- the models never take it)
+ *   BERNOULLI  log p if Y == 1 else log(1 - p),  p = Phi(F) (1 - 2e-3) + 1e-3   (probit link with GPflow's jitter)   no parameter
+ *   STUDENT_T  lgc - log s - 1/2 log(nu pi) - (nu + 1)/2 log1p(((Y - F)/s)^2 / nu)    param[0] = s (scale), param[1] = nu (df),
+ *              lgc = lgamma((nu + 1)/2) - lgamma(nu/2), computed by the HOST (it depends on nu alone, and nu is not trained)
+ * param0_dev: optional device scalar read instead of param[0] when the launch runs (a trained variance / scale), as lik_variance_dev.
+ * ---------------------------------------------------------------------- */
+enum { IWVI_LIK_GAUSSIAN = 0, IWVI_LIK_BERNOULLI_PROBIT = 1, IWVI_LIK_STUDENT_T = 2 };
+typedef struct iwvi_lik_desc {
+    int32_t type;
+    float param[2];
+    float lgc;
+    const float* param0_dev;
+} iwvi_lik_desc;
+
+/* iwvi_iw_elbo_reduce_dev with a likelihood descriptor in place of lik_variance: the variational expectation of every (point, sample,
+ * output) by the rule above, everything else -- strides, regularisers, ticket, optional outputs, ONE launch -- as documented there. */
+int iwvi_lik_elbo_reduce(const iwvi_lik_desc* lik, const float* fmean, const float* fvar, const float* Y,
+                         int64_t B, int K, int Dy, int64_t stride_b, int64_t stride_k,
+                         const float* const* kl_local_host, const int32_t* kl_dims_host, int n_kl,
+                         const double* const* kl_global_host, const int32_t* kl_global_counts_host, int n_glob,
+                         double scale, int K_total, int mode_vi,
+                         float* out_lse_ms, float* out_logp, double* out_elbo, uint64_t* ticket, void* stream);
+
+/* iwvi_iw_elbo_backward_dev with a likelihood descriptor: out_w, d_mean, d_var, out_sums[0] and [2] as there, out_sums[1] =
+ * d ELBO / d param[0] (0 for the Bernoulli).  The heads use the reparameterised form of the rule, first derivatives only:
+ *   dE/dmu = sum_i w_i g'(f_i),   dE/dv = sum_i w_i g'(f_i) x_i / sqrt(2 v)   with v floored at 1e-8. */
+int iwvi_lik_elbo_backward(const iwvi_lik_desc* lik, const float* fmean, const float* fvar, const float* Y, int Dy,
+                           const float* const* kl_local, const int32_t* kl_dims, int n_local,
+                           int64_t B, int K, double scale, int mode_vi,
+                           float* out_w, float* d_mean, float* d_var,
+                           const double* const* kl_global, const int32_t* kl_global_counts, int n_glob,
+                           const float* lse_global, int K_total,
+                           double* out_sums, double* ws, void* stream);
+
+/* The likelihood's methods as elementwise callables on explicit moments, Fmu / Fvar / out [T, Dy], Y row (t / row_div) % row_mod as in
+ * iwvi_gaussian_var_exp.  iwvi_lik_predict_density: log of the predictive density (the Bernoulli's closed form at
+ * p = inv_probit(Fmu / sqrt(1 + Fvar)), the Student-t's log-space quadrature of logp); Fvar == NULL: logp(Fmu, Y).
+ * iwvi_lik_predict_mean_and_var (n elements): Bernoulli (p, p - p^2) at that p; Student-t (Fmu, E[s^2 nu/(nu - 2) + F^2] - Fmu^2) by the
+ * rule, nu > 2 required; Gaussian (Fmu, Fvar + variance). */
+int iwvi_lik_var_exp(const iwvi_lik_desc* lik, const float* Fmu, const float* Fvar, const float* Y,
+                     int64_t T, int Dy, int64_t row_div, int64_t row_mod, float* out, void* stream);
+int iwvi_lik_predict_density(const iwvi_lik_desc* lik, const float* Fmu, const float* Fvar, const float* Y,
+                             int64_t T, int Dy, int64_t row_div, int64_t row_mod, float* out, void* stream);
+int iwvi_lik_predict_mean_and_var(const iwvi_lik_desc* lik, const float* Fmu, const float* Fvar, int64_t n,
+                                  float* out_mean, float* out_var, void* stream);
 
 /* white=False (temp_workaround.py:63-65: "another backsubstitution in the unwhitened case").  The unwhitened
  * q(u) = N(f, q_sqrt q_sqrt^T) gives the same conditional as the whitened one with f_w = Lm^-1 f and
