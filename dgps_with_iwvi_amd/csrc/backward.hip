@@ -2583,7 +2583,8 @@ __global__ void k_d2f(const double* src, float* dst, long long ld, int rows, int
     dst[i * ld + j] = (tril && j > i) ? 0.f : (float)src[idx];
 }
 
-// Adam on GPflow's unconstrained variables.  transform 1 = positive: p = softplus(x) + 1e-6 (gpflow.transforms.Log1pe)
+// Adam on GPflow's unconstrained variables.  transform 1 = positive: p = softplus(x) + 1e-6 (gpflow.transforms.Log1pe); x is the
+// master copy: a step reads x, m, v and the gradient and WRITES p (it never reads p, whose rounding would dominate near the 1e-6 floor)
 struct AdamTensor { float* p; const float* g; float* x; float* m; float* v; long long n; int transform; int g64; };
 constexpr int ADAM_MAX = 48;
 struct AdamArgs { AdamTensor t[ADAM_MAX]; int n; float lr_t, b1, b2, eps, sign; int init; const long long* t_dev; float lr; };
@@ -2608,7 +2609,7 @@ __global__ void k_adam(AdamArgs a) {
             continue;
         }
         float x = T.x[i], g = a.sign * (T.g64 ? (float)reinterpret_cast<const double*>(T.g)[i] : T.g[i]);
-        if (T.transform == 1) g *= 1.f - __expf(-(T.p[i] - 1e-6f));          // d softplus(x) / dx = sigmoid(x)
+        if (T.transform == 1) g *= 1.f / (1.f + __expf(-x));                 // d softplus(x) / dx = sigmoid(x), from x: 1 - exp(-(p - 1e-6)) cancels twice near the floor
         const float m = a.b1 * T.m[i] + (1.f - a.b1) * g;
         const float v = a.b2 * T.v[i] + (1.f - a.b2) * g * g;
         x -= lr_t * m / (sqrtf(v) + a.eps);
@@ -3184,8 +3185,10 @@ extern "C" int iwvi_adam_step(const iwvi_adam_tensor* tensors, int n_tensors, do
         if (s.n > nmax) nmax = s.n;
     }
     a.n = n_tensors; a.init = init;
-    a.lr_t = init ? 0.f : (float)(lr * sqrt(1.0 - pow(beta2, (double)t)) / (1.0 - pow(beta1, (double)t)));
     a.b1 = (float)beta1; a.b2 = (float)beta2; a.eps = (float)eps; a.sign = maximise ? -1.f : 1.f;
+    // the bias correction of the recurrences the kernel runs, i.e. on the float32 betas (as the device form does, and TensorFlow's float32
+    // beta powers): 1 - 0.999^t and 1 - float(0.999)^t are 1.3e-5 apart while t << 1000
+    a.lr_t = init ? 0.f : (float)(lr * sqrt(1.0 - pow((double)a.b2, (double)t)) / (1.0 - pow((double)a.b1, (double)t)));
     long long blocks = (nmax + 255) / 256; if (blocks > 1024) blocks = 1024;
     hipLaunchKernelGGL(k_adam, dim3((unsigned)blocks, n_tensors), dim3(256), 0, (hipStream_t)stream_, a);
     return check_launch("k_adam");

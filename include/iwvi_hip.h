@@ -463,7 +463,11 @@ int iwvi_kde_loglik(const float* samples, int64_t sample_stride, int64_t point_s
  * iwvi_adam_step: TensorFlow AdamOptimizer on GPflow's unconstrained variables; transform 0 = identity,
  * 1 = positive (param = softplus(x) + 1e-6), | IWVI_ADAM_GRAD_F64: `grad` points to doubles (the likelihood-variance
  * gradient leaves iwvi_iw_elbo_backward in float64); x/m/v are the optimiser's state (same length as param);
- * init != 0 fills them from the current parameter values instead of stepping; t = 1-based step count. */
+ * init != 0 fills them from the current parameter values instead of stepping; t = 1-based step count.
+ * Precision of the positive transform: x is the master copy.  A step reads x, m, v and grad, forms d param / d x = sigmoid(x) from x, and
+ * WRITES param = softplus(x) + 1e-6 (it never reads param), so a parameter near the 1e-6 floor moves as accurately as one of order 1:
+ * x within a few float32 spacings of a float64 Adam per step, param within that times param.  beta1 / beta2 / eps are used as floats, in the
+ * recurrences and in the bias correction of both entry points alike.  Rule and measurements: tests/adam_reference.py, DESIGN.md section 2. */
 size_t iwvi_natgrad_ws_bytes(int M);
 int iwvi_natgrad_step(float* q_mu, float* q_sqrt, const float* dq_mu, const float* dq_sqrt,
                       int M, int R, double gamma, void* ws, void* stream);

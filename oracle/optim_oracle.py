@@ -60,14 +60,16 @@ def to_constrained(x, positive):
 
 
 class Adam:
-    """State for a list of parameters; ``step(grads_of_loss)`` returns the new constrained values."""
+    """State for a list of parameters; ``step(grads_of_loss)`` returns the new constrained values.  The unconstrained variables and
+    the two moments after the latest step are ``x``, ``m``, ``v`` (lists, one array per parameter); ``t0``: the count of the first step
+    (a run that resumes: set ``m`` / ``v`` as well); ``step(..., lr=)``: that step's rate."""
 
-    def __init__(self, params, positive, lr, beta1=0.9, beta2=0.999, eps=1e-8):
+    def __init__(self, params, positive, lr, beta1=0.9, beta2=0.999, eps=1e-8, t0=1):
         self.pos = list(positive)
         self.x = [to_unconstrained(p, s) for p, s in zip(params, self.pos)]
         self.m = [np.zeros_like(x) for x in self.x]
         self.v = [np.zeros_like(x) for x in self.x]
-        self.lr, self.b1, self.b2, self.eps, self.t = lr, beta1, beta2, eps, 0
+        self.lr, self.b1, self.b2, self.eps, self.t = lr, beta1, beta2, eps, int(t0) - 1
 
     def step(self, grads, lr=None):
         self.t += 1

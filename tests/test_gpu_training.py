@@ -78,6 +78,59 @@ def test_natgrad_step_matches_oracle(gpu_device, M, R):
         assert torch.equal(h_mu, d_mu) and torch.equal(h_sqrt, d_sqrt)
 
 
+def _natgrad_both_entries(gpu_device, q_mu, q_sqrt, g_mu, g_sqrt, gamma):
+    """(q_mu, q_sqrt) after iwvi_natgrad_step with the R-independent workspace, and after iwvi_natgrad_step_ex with the one sized for R
+    latent GPs (the route that one took is asserted); ``g_*``: gradients of the ELBO."""
+    from dgps_with_iwvi_amd import _abi
+    lib = _abi.lib()
+    M, R = q_mu.shape
+    dg_mu, dg_sqrt = _t(g_mu, gpu_device), _t(g_sqrt, gpu_device)
+    d_mu, d_sqrt, x_mu, x_sqrt = (_t(a, gpu_device) for a in (q_mu, q_sqrt, q_mu, q_sqrt))
+    ws = torch.empty(lib.iwvi_natgrad_ws_bytes(M), dtype=torch.uint8, device=gpu_device)
+    wsx = torch.empty(lib.iwvi_natgrad_ws_bytes_ex(M, R), dtype=torch.uint8, device=gpu_device)
+    _abi.check(lib.iwvi_natgrad_step(_abi.ptr(d_mu), _abi.ptr(d_sqrt), _abi.ptr(dg_mu), _abi.ptr(dg_sqrt), M, R, gamma,
+                                     ws.data_ptr(), _abi.stream_ptr()))
+    _abi.check(lib.iwvi_natgrad_step_ex(_abi.ptr(x_mu), _abi.ptr(x_sqrt), _abi.ptr(dg_mu), _abi.ptr(dg_sqrt), M, R, gamma,
+                                        wsx.data_ptr(), wsx.numel(), _abi.stream_ptr()))
+    assert lib.iwvi_debug_last_natgrad_route() == ((2 if R <= 8 else 1) if M <= 128 else 0)
+    return (d_mu, d_sqrt), (x_mu, x_sqrt)
+
+
+def _assert_natgrad(outs, ref_mu, ref_sqrt, what):
+    """rtol = 2e-5 as above, atol = 2e-6 x the largest |ref| of the array (the inputs are no longer of order 1); upper triangle exactly 0."""
+    for mu, sq in outs:
+        np.testing.assert_allclose(mu.cpu().numpy(), ref_mu, rtol=2e-5, atol=2e-6 * np.abs(ref_mu).max(), err_msg=str(what))
+        np.testing.assert_allclose(sq.cpu().numpy(), ref_sqrt, rtol=2e-5, atol=2e-6 * np.abs(ref_sqrt).max(), err_msg=str(what))
+        assert float(torch.triu(sq, 1).abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("s", [1e-5, 1e-3, 30.0])
+@pytest.mark.parametrize("M,R", [(40, 2), (128, 5), (200, 1)])       # the spread, one-workgroup-capable and multi-launch routes
+def test_natgrad_step_at_the_scales_training_visits(gpu_device, M, R, s):
+    """The inputs of test_natgrad_step_matches_oracle with q_sqrt scaled by s and its gradient by 1 / s: Phi = L^T Lbar, and with it
+    Q = I + gamma (Phi + Phi^T), is the same matrix (up to the float32 rounding of the scaled inputs), so the step is as well posed as
+    there -- at a q_sqrt of 1e-5 (a posterior that has collapsed onto the data) and of 30."""
+    rng = np.random.default_rng(M)
+    q_mu = rng.standard_normal((M, R)).astype(np.float32)
+    q_sqrt = ((np.tril(rng.standard_normal((R, M, M))) * 0.1 + np.eye(M)) * s).astype(np.float32)
+    g_mu = rng.standard_normal((M, R)).astype(np.float32)
+    g_sqrt = (np.tril(rng.standard_normal((R, M, M))) * (0.5 * min(1.0, (64.0 / M) ** 0.5) / s)).astype(np.float32)
+    ref_mu, ref_sqrt = oo.natgrad_step(q_mu, q_sqrt, -g_mu.astype(np.float64), -g_sqrt.astype(np.float64), 0.05)
+    assert np.all(np.isfinite(ref_sqrt)) and np.abs(ref_sqrt).max() < 3 * s
+    _assert_natgrad(_natgrad_both_entries(gpu_device, q_mu, q_sqrt, g_mu, g_sqrt, 0.05), ref_mu, ref_sqrt, (M, R, s))
+
+
+@pytest.mark.parametrize("M,R", [(40, 2), (128, 5), (200, 1)])
+def test_natgrad_unit_step_solves_the_conjugate_problem(gpu_device, M, R):
+    """gamma = 1 from (q_mu, q_sqrt) = (0, I) on a Gaussian model that is linear in u lands on the closed-form posterior: the device against
+    the oracle on the identical float32 gradients, the oracle (here, on the CPU) against the closed form under the same tolerance."""
+    from test_optim_oracle import conjugate_gaussian_case, within_natgrad_tolerance
+    q_mu, q_sqrt, g_mu, g_sqrt, m_star, L_star = conjugate_gaussian_case(M, R)
+    ref_mu, ref_sqrt = oo.natgrad_step(q_mu, q_sqrt, g_mu, g_sqrt, 1.0)
+    assert within_natgrad_tolerance(ref_mu, m_star) and within_natgrad_tolerance(ref_sqrt, L_star)
+    _assert_natgrad(_natgrad_both_entries(gpu_device, q_mu, q_sqrt, -g_mu, -g_sqrt, 1.0), ref_mu, ref_sqrt, (M, R))
+
+
 def test_adam_steps_match_oracle(gpu_device):
     from dgps_with_iwvi_amd import _abi
     rng = np.random.default_rng(0)
@@ -169,6 +222,10 @@ class _OracleTrainer:
         _, g = self.grad(self.spec, zs_ng)
         i = self.n - 1
         f["q_mu"], f["q_sqrt"] = oo.natgrad_step(f["q_mu"], f["q_sqrt"], -g["l%d.q_mu" % i], -g["l%d.q_sqrt" % i], self.gamma)
+        return self.adam_step(zs_adam)
+
+    def adam_step(self, zs_adam):
+        """``op_adam`` alone (Trainer.adam_op)."""
         val, g = self.grad(self.spec, zs_adam)
         sig = [np.abs(np.asarray(g[k])) > 5e-2 * max(np.abs(np.asarray(g[k])).max(), 1e-300) for k in self.names]
         self.signif = sig if self.signif is None else [a & b for a, b in zip(self.signif, sig)]

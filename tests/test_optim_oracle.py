@@ -54,3 +54,35 @@ def test_adam_first_step_moves_by_lr_against_the_gradient_sign_and_respects_posi
 def test_staircase_decay():
     assert oo.staircase_decay(0.1, 999, 0.5) == 0.1 and oo.staircase_decay(0.1, 1000, 0.5) == 0.05
     assert oo.staircase_decay(0.1, 2500, 0.5) == 0.025
+
+
+def conjugate_gaussian_case(M, R, seed=0):
+    """A Gaussian model that is linear in the whitened u: y_r = A u_r + noise of variance 0.01, N = 4 M points, prior u_r ~ N(0, I).
+    -> float32 (q_mu [M, R], q_sqrt [R, M, M]) = (0, I), the float32 roundings of the LOSS gradients there (loss = -ELBO; computed in
+    float64), and the closed-form optimum (m*, chol(S*)) in float64: S* = (I + A^T A / s)^-1, m*_r = S* A^T y_r / s.
+    Also used by tests/test_gpu_training.py::test_natgrad_unit_step_solves_the_conjugate_problem."""
+    rng = np.random.default_rng([seed, M, R])
+    N, s = 4 * M, 0.01
+    A = rng.standard_normal((N, M)) / np.sqrt(N)
+    Y = A @ rng.standard_normal((M, R)) + np.sqrt(s) * rng.standard_normal((N, R))
+    q_mu, q_sqrt = np.zeros((M, R), dtype=np.float32), np.tile(np.eye(M, dtype=np.float32), (R, 1, 1))
+    # -E_q log p(y | u) + KL[q || N(0, I)] at (m, L): d/dm = -A^T (y - A m) / s + m;  d/dS = A^T A / (2 s) + (I - S^-1) / 2;  d/dL = tril(2 dS L)
+    g_mu = (-(A.T @ Y) / s).astype(np.float32)
+    g_sqrt = np.tile(np.tril(A.T @ A / s).astype(np.float32), (R, 1, 1))
+    S_star = np.linalg.inv(np.eye(M) + A.T @ A / s)
+    return q_mu, q_sqrt, g_mu, g_sqrt, S_star @ (A.T @ Y) / s, np.tile(np.linalg.cholesky(S_star), (R, 1, 1))
+
+
+def within_natgrad_tolerance(got, ref):
+    """The natural-gradient step's tolerance (tests/test_gpu_training.py: rtol = 2e-5) with atol = 2e-6 x the largest |ref| of the array."""
+    return bool(np.all(np.abs(np.asarray(got, dtype=np.float64) - ref) <= 2e-5 * np.abs(ref) + 2e-6 * np.abs(ref).max()))
+
+
+def test_oracle_on_float32_gradients_lands_on_the_conjugate_optimum():
+    """gamma = 1 from (0, I) on the float32-rounded gradients of the linear-Gaussian model: the oracle is within the device test's
+    tolerance of the closed form, so comparing the device with the oracle there tests the known answer."""
+    for M, R in ((40, 2), (128, 5), (200, 1)):
+        q_mu, q_sqrt, g_mu, g_sqrt, m_star, L_star = conjugate_gaussian_case(M, R)
+        mu, Ls = oo.natgrad_step(q_mu, q_sqrt, g_mu, g_sqrt, 1.0)
+        assert within_natgrad_tolerance(mu, m_star) and within_natgrad_tolerance(Ls, L_star), (M, R)
+        assert 0.02 < np.abs(np.diagonal(L_star, axis1=1, axis2=2)).max() < 0.5      # far from the q_sqrt = I it started at
