@@ -226,6 +226,8 @@ PROTOTYPES = {
                                          c_float, c_void_p, c_void_p, ctypes.c_uint64, c_void_p, c_void_p, c_void_p]),
     "iwvi_sample_stats": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "iwvi_kde_density_grid": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int, c_double,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
     "iwvi_lik_elbo_reduce": (c_int, [ctypes.POINTER(LikDesc), c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_int64,
                                      ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_int32), c_int,
                                      ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_int32), c_int, c_double,

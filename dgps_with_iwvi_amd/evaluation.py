@@ -8,7 +8,11 @@ batches of test points (the layer kernels; prior-mode latent-variable layers, la
 
 ``evaluate(on_device=True)`` keeps the whole loop on the device: ``predict_y_samples_fused`` (the fused forward with a sampling tail)
 and per batch one ``iwvi_sample_stats`` launch -- a sort of each point's samples in LDS, then the KDE, the squared error, the
-Shapiro-Wilk W and any quantiles from it -- with one read-back at the end."""
+Shapiro-Wilk W and any quantiles from it -- with one read-back at the end.
+
+``kde_log_density_grid`` / ``predictive_density_grid`` evaluate each point's estimate on a whole GRID of levels in one
+``iwvi_kde_density_grid`` launch: the conditional density picture of the reference's experiments/demo.py (200 inputs x 10 000 samples x
+200 levels), with Silverman's bandwidth or a fixed one; ``evaluate(on_device=True, density_levels=...)`` adds it from the same samples."""
 import ctypes
 
 import numpy as np
@@ -124,12 +128,104 @@ def sample_stats(samples, y=None, shapiro=True, quantiles=None):
     return out
 
 
-def _evaluate_on_device(model, X_test, Y_test, num_predict_samples, predict_batch_size, quantiles):
-    parts = []
+KDE_GRID_TILE = 64                                                       # csrc/kde_grid.hip: levels per workgroup (KG_TILE) ...
+KDE_GRID_CHUNK = 2048                                                    # ... and samples staged in LDS per step (KG_CHUNK)
+
+
+def _check_bandwidth(bandwidth):
+    """None -> 0.0 (the library's Silverman per point); otherwise a finite positive float."""
+    if bandwidth is None:
+        return 0.0
+    h = float(bandwidth)
+    if not np.isfinite(h) or h <= 0.0:
+        raise ValueError("bandwidth must be None (Silverman's rule per point) or a finite positive number, got %r" % (bandwidth,))
+    return h
+
+
+def _check_levels(levels, N=None):
+    """levels [G] or [N, G], G >= 1 (a tensor or anything NumPy takes); returns it unchanged.  ``N`` None: the row count is not checked."""
+    shape = tuple(levels.shape) if isinstance(levels, torch.Tensor) else np.shape(levels)
+    if len(shape) not in (1, 2) or shape[-1] < 1 or (len(shape) == 2 and N is not None and shape[0] != N):
+        raise ValueError("levels must be [G] or [N, G]%s with G >= 1, got %s" % ("" if N is None else " (N = %d)" % N, shape))
+    return levels
+
+
+def kde_log_density_grid(samples, levels, bandwidth=None):
+    """samples [S, N] (device, any strides), levels [G] (shared) or [N, G] (per point) -> dict of device tensors through one
+    ``iwvi_kde_density_grid`` launch: ``logdens`` [N, G], the log density of each point's Gaussian KDE at each level; ``mean_std`` [N, 2];
+    ``bandwidth`` [N], the bandwidth used -- Silverman's 1.06 std S^(-1/5) per point (``bandwidth=None``, S >= 2) or the fixed positive
+    value given (S >= 1).  The samples are streamed, not sorted: S is not capped at ``MAX_SAMPLES``."""
+    h = _check_bandwidth(bandwidth)
+    if not isinstance(samples, torch.Tensor) or samples.dim() != 2:
+        raise ValueError("samples must be a [S, N] tensor")
+    if samples.dtype != settings.float_type:
+        raise ValueError("samples must be %s, got %s" % (settings.float_type, samples.dtype))
+    S, N = samples.shape
+    if S < (2 if h == 0.0 else 1):
+        raise ValueError("S=%d: %s" % (S, "Silverman's bandwidth needs S >= 2" if S == 1 else "no samples"))
+    _check_levels(levels, N)
+    if isinstance(levels, torch.Tensor) and levels.dtype != settings.float_type:
+        raise ValueError("levels must be %s, got %s" % (settings.float_type, levels.dtype))
+    if N > 0 and min(samples.stride()) <= 0:                             # (an expanded view: the kernel takes positive strides)
+        samples = samples.contiguous()
+    if not samples.is_cuda:
+        _abi.dev_tensor(samples.contiguous(), "samples")                 # (raises: no CPU fallback)
+    dev = samples.device
+    if not isinstance(levels, torch.Tensor):
+        levels = torch.as_tensor(np.asarray(levels, dtype=np.float32), device=dev)
+    levels = _abi.dev_tensor(levels.contiguous(), "levels")
+    G = levels.shape[-1]
+    out = {"logdens": torch.empty(N, G, dtype=settings.float_type, device=dev),
+           "mean_std": torch.empty(N, 2, dtype=settings.float_type, device=dev),
+           "bandwidth": torch.empty(N, dtype=settings.float_type, device=dev)}
+    if N == 0:
+        return out
+    ss, sn = samples.stride()
+    _abi.check(_abi.lib().iwvi_kde_density_grid(ctypes.c_void_p(samples.data_ptr()), ss, sn, N, S, _abi.ptr(levels),
+                                               G if levels.dim() == 2 else 0, G, h, _abi.ptr(out["logdens"]), _abi.ptr(out["mean_std"]),
+                                               _abi.ptr(out["bandwidth"]), _abi.stream_ptr()))
+    return out
+
+
+def predictive_density_grid(model, X, levels, num_samples=10000, predict_batch_size=None, bandwidth=None):
+    """[N, G] (device): log density of the model's predictive at ``levels`` ([G] or [N, G]) for every row of ``X``, estimated as the
+    reference's demo does -- ``num_samples`` predictive samples per input, a Gaussian KDE with Silverman's bandwidth (or a fixed one) --
+    with per batch of inputs one sampling launch (``predict_y_samples_fused``; layer by layer for a non-Gaussian likelihood) and one
+    ``iwvi_kde_density_grid`` launch.  One output column.  ``predict_batch_size`` None: as many inputs per batch as the sampling launch's
+    row budget allows, at least one, so a ``num_samples`` beyond that budget still runs."""
+    from .likelihoods import is_gaussian
+    h = _check_bandwidth(bandwidth)
+    S = int(num_samples)
+    if S < (2 if h == 0.0 else 1):
+        raise ValueError("num_samples=%d too small (Silverman's bandwidth needs 2)" % S)
+    if model._output_dim() != 1:
+        raise ValueError("the density grid is for one output column, the model has %s" % (model._output_dim(),))
+    dev = model.X.device
+    X = torch.as_tensor(np.asarray(X, dtype=np.float32), device=dev) if not isinstance(X, torch.Tensor) else X.to(dev, settings.float_type)
+    N = X.shape[0]
+    _check_levels(levels, N)
+    levels = torch.as_tensor(np.asarray(levels, dtype=np.float32), device=dev) if not isinstance(levels, torch.Tensor) else levels.to(dev, settings.float_type)
+    bs = max(1, model._PREDICT_ROWS // S) if predict_batch_size is None else int(predict_batch_size)
+    if bs < 1:
+        raise ValueError("predict_batch_size must be >= 1")
+    out = torch.empty(N, levels.shape[-1], dtype=settings.float_type, device=dev)
+    fused = is_gaussian(model.likelihood)
+    for lo in range(0, N, bs):
+        x = X[lo:lo + bs]
+        smp = (model.predict_y_samples_fused(x, S, batch_size=bs) if fused else model.predict_y_samples(x, S))[:, :, 0]    # [S, n]
+        out[lo:lo + bs] = kde_log_density_grid(smp, levels if levels.dim() == 1 else levels[lo:lo + bs], bandwidth)["logdens"]
+    return out
+
+
+def _evaluate_on_device(model, X_test, Y_test, num_predict_samples, predict_batch_size, quantiles, density_levels=None):
+    parts, grids = [], []
     for lo in range(0, X_test.shape[0], predict_batch_size):
         x, y = X_test[lo:lo + predict_batch_size], Y_test[lo:lo + predict_batch_size]
         smp = model.predict_y_samples_fused(x, num_predict_samples)[:, :, 0]       # [S, n], a point's samples contiguous
         parts.append(sample_stats(smp, y, shapiro=True, quantiles=quantiles))
+        if density_levels is not None:                                             # the same samples, one more launch
+            lv = density_levels if density_levels.dim() == 1 else density_levels[lo:lo + predict_batch_size]
+            grids.append(kde_log_density_grid(smp, lv)["logdens"])
     cat = {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
     # one read-back: the three scalars in one tensor (NumPy's median: the mean of the two middle values for an even count)
     W = cat["W"].double().sort().values
@@ -138,17 +234,24 @@ def _evaluate_on_device(model, X_test, Y_test, num_predict_samples, predict_batc
     res = {"test_loglik": float(vals[0]), "test_rmse": float(vals[1]), "test_shapiro_W_median": float(vals[2])}
     if quantiles is not None:
         res["test_quantiles"] = cat["quantiles"].cpu().numpy()
+    if density_levels is not None:
+        res["test_density_grid"] = torch.cat(grids).cpu().numpy()
     return res
 
 
 def evaluate(model, X_test, Y_test, num_predict_samples=2000, predict_batch_size=1000, shapiro=False, mc_loglik=False,
-             on_device=False, quantiles=None):
+             on_device=False, quantiles=None, density_levels=None):
     """-> dict(test_loglik, test_rmse[, test_shapiro_W_median]) as the reference's ``res`` (:167-169); Y one column.
     ``mc_loglik``: also ``test_loglik_mc``, the mean Monte Carlo log predictive density (``model.predict_log_density`` with
     ``num_predict_samples`` draws per point), the usual DGP test metric beside the reference's KDE estimate.
     ``on_device``: per batch ``predict_y_samples_fused`` and one ``iwvi_sample_stats`` launch, one read-back at the end;
     ``test_shapiro_W_median`` is then always in the result (the reference's row), and ``quantiles=[...]`` (on-device only) adds
-    ``test_quantiles`` [N, len(quantiles)], the predictive quantiles per test point."""
+    ``test_quantiles`` [N, len(quantiles)], the predictive quantiles per test point; ``density_levels`` ([G] or [N, G], on-device only)
+    adds ``test_density_grid`` [N, G], the KDE's log density at those levels from the same samples (``kde_log_density_grid``)."""
+    if density_levels is not None:
+        if not on_device:
+            raise ValueError("density_levels need on_device=True")
+        _check_levels(density_levels, np.shape(X_test)[0])
     if quantiles is not None:
         if not on_device:
             raise ValueError("quantiles need on_device=True")
@@ -162,7 +265,11 @@ def evaluate(model, X_test, Y_test, num_predict_samples=2000, predict_batch_size
     if N == 0 or Y_test.shape[0] != N:
         raise ValueError("X_test has %d rows, Y_test %d" % (N, Y_test.shape[0]))
     if on_device:
-        res = _evaluate_on_device(model, X_test, Y_test, num_predict_samples, predict_batch_size, quantiles)
+        if density_levels is not None and not isinstance(density_levels, torch.Tensor):
+            density_levels = np.asarray(density_levels, dtype=np.float32)
+        if density_levels is not None:
+            density_levels = torch.as_tensor(density_levels).to(dev, settings.float_type)
+        res = _evaluate_on_device(model, X_test, Y_test, num_predict_samples, predict_batch_size, quantiles, density_levels)
         if mc_loglik:
             lp = model.predict_log_density(X_test, Y_test.reshape(N, -1), num_predict_samples, batch_size=predict_batch_size)
             res["test_loglik_mc"] = float(lp.double().mean())

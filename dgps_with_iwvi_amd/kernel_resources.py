@@ -4,7 +4,7 @@ The layer kernel's hot variants sit at the 256-VGPR limit: a source change anywh
 scratch, and a variant that only the large configs take then regresses unnoticed (round 4: the five-sub-tile large-M variant went
 216 B into scratch, configs[3] 1.27 -> 1.43 ms, for four commits).  ``check()`` is run by ``__graft_entry__.build()`` and by
 tests/test_kernel_resources.py: it fails when a ``k_dgp_forward`` or ``k_bw_chain`` instantiation (the predictive and sampling variants of the
-forward included), ``k_sample_stats`` or a likelihood-tail kernel (every ``k_lik_*``) uses scratch memory
+forward included), ``k_sample_stats``, ``k_kde_grid`` or a likelihood-tail kernel (every ``k_lik_*``) uses scratch memory
 (``.private_segment_fixed_size`` > 0) beyond what ``ALLOWED_SCRATCH`` lists, when a listed spill count grows, or when a kernel listed in ``MAX_VGPRS`` exceeds its VGPR ceiling.
 
   python -m dgps_with_iwvi_amd.kernel_resources [--write profiles/<tag>_kernel_resources.txt]
@@ -26,7 +26,7 @@ FIELDS = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_sp
 
 # kernels whose instantiations must not touch scratch memory at all ...
 # (k_lik_*: csrc/likelihood_tail.hip -- twenty quadrature nodes unrolled per element: no scratch, and a VGPR ceiling each, MAX_VGPRS below)
-NO_SCRATCH = ("k_dgp_forward", "k_bw_chain", "k_sample_stats", "k_lik_elbo", "k_lik_elbo_bwd", "k_lik_elem", "k_lik_finish")
+NO_SCRATCH = ("k_dgp_forward", "k_bw_chain", "k_sample_stats", "k_lik_elbo", "k_lik_elbo_bwd", "k_lik_elem", "k_lik_finish", "k_kde_grid")
 # ... except these (demangled-name substring -> bytes of scratch it is known to use; lower it when a kernel improves)
 ALLOWED_SCRATCH = {
     # round 6 (profiles/r06_kernel_resources.txt): every BIG variant (some layer with M > 128: configs[3] / [4]) and every float64-route

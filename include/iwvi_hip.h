@@ -630,6 +630,27 @@ int iwvi_sample_stats(const float* samples, int64_t sample_stride, int64_t point
                       const double* sw_coef, const double* probs, int n_probs, float* out_logp, float* out_sqerr,
                       float* out_mean_std, float* out_W, float* out_quantiles, void* stream);
 
+/* Log density of each point's Gaussian kernel-density estimate on a GRID of levels, one launch (additive extension of ABI 19;
+ * csrc/kde_grid.hip): the reference's conditional density picture (experiments/demo.py), 200 inputs x 10 000 samples x 200 levels.
+ *   out_logdens[n, g] = logsumexp_s(-((l_ng - x_ns) / h_n)^2 / 2) - log(S h_n) - log sqrt(2 pi)
+ * samples: element (s, n) at samples[s*sample_stride + n*point_stride] (positive strides, as iwvi_sample_stats; a point's samples
+ *   contiguous is the fast case).  The samples are streamed through LDS, not sorted: S has no cap but S <= 2^31 - 1 - 2048.
+ * levels: [G] shared by all points when level_point_stride == 0; otherwise point n's G levels start at levels + n*level_point_stride
+ *   (level_point_stride >= G).  G >= 1.
+ * bandwidth <= 0: Silverman's rule per point, h_n = 1.06 std_n S^(-1/5) with the population standard deviation (needs S >= 2), the
+ *   formula of iwvi_kde_loglik and iwvi_sample_stats.  bandwidth > 0: that value for every point (S >= 1).  It must be finite.
+ * Differences, standard deviation, bandwidth, exponents and the sum of exponentials are float64 formed from the float32 values; the sum
+ * is taken relative to the exponent of the sample nearest to the level, so a level hundreds of standard deviations away gets the finite
+ * value of the formula (-1e5 .. -1e6), never -inf.  The result is rounded to float32 once.  Two calls on the same inputs give the same bits.
+ *   out_logdens [N, G] row-major;  out_mean_std [N, 2] or NULL: sample mean and population standard deviation;
+ *   out_bandwidth [N] or NULL: the h_n actually used.
+ * Silverman with all samples of a point equal: a point mass, +inf at a level equal to that value and -inf elsewhere, bandwidth 0.  A NaN
+ * sample: NaN in that point's whole row, its mean, standard deviation and bandwidth; other points are not affected.  A NaN level: NaN in
+ * that entry.  N == 0 returns IWVI_OK without a launch; N x ceil(G / 64) <= 2^31 - 1. */
+int iwvi_kde_density_grid(const float* samples, int64_t sample_stride, int64_t point_stride, int64_t N, int64_t S,
+                          const float* levels, int64_t level_point_stride, int G, double bandwidth,
+                          float* out_logdens, float* out_mean_std, float* out_bandwidth, void* stream);
+
 /* ------------------------------------------------------------------------
  * Likelihoods other than the Gaussian (additive extension of ABI 19; csrc/likelihood_tail.hip).  The reference hands ANY GPflow-1.x
  * likelihood object to its models and calls variational_expectations (models.py:66,134) and predict_mean_and_var (:105) on it.  The
