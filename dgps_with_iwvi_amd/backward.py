@@ -2,14 +2,19 @@
 
 The reference obtains its gradients from TensorFlow's autodiff of the graph of ``models.py:112-150``
 (``experiments/build_models.py:284-304``); here every layer has a hand-written adjoint behind the C-ABI
-(``iwvi_gp_layer_backward`` ...), driven layer by layer in reverse.  First version: correct and
-deterministic, intermediates in HBM; not fused like the forward yet."""
+(``iwvi_gp_layer_backward`` ...), driven layer by layer in reverse.
+
+``iw_elbo_and_gradients`` is a short driver over the steps of one evaluation, each a function of this module: ``_checked``, ``_prepare``
+(the adjoint's operands, queued relative to the forward's precompute), ``_saving_forward`` (a ``GpSaved`` / ``LvSaved`` per layer), ``_heads``,
+then ``_final_q_gradients`` or ``_reverse_sweep`` with its parameter branches where ``branch_placement`` puts them.  The launch order, the
+stream joins and the placement each bought measured time: the comments next to them say how much."""
+import collections
 import ctypes
 
 import torch
 
 from . import _abi, settings
-from .layers import GPLayer, SharedMixedMok
+from .layers import GPLayer, LatentVariableLayer, SharedMixedMok
 from .temp_workaround import precompute_states
 
 
@@ -37,6 +42,19 @@ class GpSaved:
     __slots__ = ("F", "noise", "A", "U", "sample", "mean", "var", "T", "GMV")
 
 
+# What a latent-variable layer's forward leaves for its adjoint: the encoder's rows (means | raw), the draws, the local KL [B, latent_dim]
+# and the number of input columns in front of the latent ones.  (A layer whose forward left nothing -- ``wrt="final_q"`` -- has None.)
+LvSaved = collections.namedtuple("LvSaved", "enc_out eps kl D_in")
+
+
+def _gp_layers(model):
+    return [(i, l) for i, l in enumerate(model.layers) if isinstance(l, GPLayer)]
+
+
+def _workspace(layer, T, D, dev):
+    return torch.empty(_abi.lib().iwvi_gp_layer_backward_ws_bytes(T, layer.num_inducing, D, layer.num_outputs), dtype=torch.uint8, device=dev)
+
+
 def needs_saved_u(layer, T):
     """The adjoint's streaming chain (csrc/backward.hip: k_bw_chain; M <= 512, M and T multiples of 16 -- T of 32 beyond M = 256 --, its tiles within the LDS) works
     from a = Lm^-1 k alone; every other shape takes the GEMM path, which also reads the forward's u_r = L_r^T a.  The library
@@ -44,10 +62,6 @@ def needs_saved_u(layer, T):
     R = layer.num_outputs
     P = layer.kern.W.shape[0] if isinstance(layer.kern, SharedMixedMok) else R
     return bool(_abi.lib().iwvi_gp_layer_backward_needs_u(int(T), layer.num_inducing, layer._Z().shape[1], R, P))
-
-
-def _words(device):
-    return torch.zeros(4, dtype=torch.int64, device=device)
 
 
 def precompute_dense(layers):
@@ -86,7 +100,7 @@ def gp_forward_saved(layer, F, z=None, words=None, precomputed=False):
         outs["u_out"] = s.U
     ld, keep = layer.fused_desc(z2, outs)
     descs = (_abi.LayerDesc * 1)(ld)
-    words = _words(dev) if words is None else words
+    words = torch.zeros(4, dtype=torch.int64, device=dev) if words is None else words
     _abi.check(_abi.lib().iwvi_dgp_forward(
         descs, 1, _abi.ptr(F), D, None, 0, None, 0, T, 1, T, 1.0,
         settings.seed, ctypes.c_void_p(words.data_ptr() + 8), None, None, _abi.stream_ptr()))
@@ -112,14 +126,29 @@ def _param_desc(layer, dense_state=None):
 def prepare_alloc(model, T):
     """Workspace + dense state per GP layer -> {layer index: (workspace, dense state)} (allocated on the caller's stream BEFORE the
     forward is queued: ``prepare_side`` may then run on another stream ordered only after this point)."""
-    dev = model.X.device
-    out = {}
-    for i, l in enumerate(model.layers):
-        if isinstance(l, GPLayer):
-            D = l._Z().shape[1]
-            ws = torch.empty(_abi.lib().iwvi_gp_layer_backward_ws_bytes(T, l.num_inducing, D, l.num_outputs), dtype=torch.uint8, device=dev)
-            out[i] = (ws, l.state_dense())
-    return out
+    return {i: (_workspace(l, T, l._Z().shape[1], model.X.device), l.state_dense()) for i, l in _gp_layers(model)}
+
+
+def _pack_operands(gps, out, T, batched, flags=0):
+    """The parameter-only part of these GP layers' adjoints (``out[i]`` = (workspace, state) of layer i), on the current stream:
+    ``batched`` -> every layer in one launch (``iwvi_gp_layers_backward_prepare``: k_prepare_all), else one
+    ``iwvi_gp_layer_backward_prepare`` per layer (k_prep + k_pack_bw).  Different kernels: each caller passes its own condition."""
+    if batched:
+        arr = (_abi.GpBwdDesc * len(gps))()
+        wsp = (ctypes.c_void_p * len(gps))()
+        keeps = []
+        for k, (i, l) in enumerate(gps):
+            b, keep = _param_desc(l, out[i][1])
+            b.flags |= flags
+            arr[k] = b
+            wsp[k] = out[i][0].data_ptr()
+            keeps.append(keep)
+        _abi.check(_abi.lib().iwvi_gp_layers_backward_prepare(arr, len(gps), T, wsp, _abi.stream_ptr()))
+        return
+    for i, l in gps:
+        b, keep = _param_desc(l, out[i][1])
+        b.flags |= flags
+        _abi.check(_abi.lib().iwvi_gp_layer_backward_prepare(ctypes.byref(b), T, out[i][0].data_ptr(), _abi.stream_ptr()))
 
 
 def prepare_inline(model, T):
@@ -129,28 +158,10 @@ def prepare_inline(model, T):
     the dense factorisation of ``prepare_side`` holds one CU per layer for twice as long as the fast one, and two workgroups of the
     layer kernel -- which needs every CU -- wait for it.  -> {layer index: (workspace, state)} like ``prepare_side``; the caller must
     NOT run ``model.precompute`` again."""
-    dev = model.X.device
-    gps = [(i, l) for i, l in enumerate(model.layers) if isinstance(l, GPLayer)]
-    out = {}
-    for i, l in gps:
-        D = l._Z().shape[1]
-        ws = torch.empty(_abi.lib().iwvi_gp_layer_backward_ws_bytes(T, l.num_inducing, D, l.num_outputs), dtype=torch.uint8, device=dev)
-        out[i] = (ws, l.state())
+    gps = _gp_layers(model)
+    out = {i: (_workspace(l, T, l._Z().shape[1], model.X.device), l.state()) for i, l in gps}
     model.precompute(with_encoders=True, dense="lm")
-    if len(gps) <= _abi.MAX_STACK:
-        arr = (_abi.GpBwdDesc * len(gps))()
-        wsp = (ctypes.c_void_p * len(gps))()
-        keeps = []
-        for k, (i, l) in enumerate(gps):
-            b, keep = _param_desc(l, out[i][1])
-            arr[k] = b
-            wsp[k] = out[i][0].data_ptr()
-            keeps.append(keep)
-        _abi.check(_abi.lib().iwvi_gp_layers_backward_prepare(arr, len(gps), T, wsp, _abi.stream_ptr()))
-    else:
-        for i, l in gps:
-            b, keep = _param_desc(l, out[i][1])
-            _abi.check(_abi.lib().iwvi_gp_layer_backward_prepare(ctypes.byref(b), T, out[i][0].data_ptr(), _abi.stream_ptr()))
+    _pack_operands(gps, out, T, batched=len(gps) <= _abi.MAX_STACK)
     return out
 
 
@@ -159,11 +170,10 @@ def prefactor_dense(model, stream, after, skip_q_of=()):
     ``prepare_side`` that depends on Z and the kernel parameters only.  A training step queues it beside the natural-gradient update of its
     first op (whose kernels leave most of the chip idle); the second op's ``prepare_side(dense_ready=...)`` then starts from it.  Layers in
     ``skip_q_of`` get the factorisation only (IWVI_GP_FACTOR_ONLY): their q(u) is being written meanwhile."""
-    gps = [(i, l) for i, l in enumerate(model.layers) if isinstance(l, GPLayer)]
     stream.wait_event(after)
     with torch.cuda.stream(stream):
         descs = []
-        for i, l in gps:
+        for i, l in _gp_layers(model):
             d = l.state_desc(state=l.state_dense())
             d.flags |= _abi.GP_WANT_LM | (_abi.GP_FACTOR_ONLY if i in skip_q_of else 0)
             descs.append(d)
@@ -179,7 +189,7 @@ def prepare_side(model, T, stream, out=None, after=None, dense_ready=None, flags
     ``out`` = ``prepare_alloc``'s result, ``after`` = an event recorded on the caller's stream right after it: the side work then
     depends on nothing queued later -- the caller can queue its own precompute + forward FIRST, so that in a captured graph they
     continue the caller's hardware queue (the first successor captured does; the other pays ~10 us of cross-queue dispatch)."""
-    gps = [(i, l) for i, l in enumerate(model.layers) if isinstance(l, GPLayer)]
+    gps = _gp_layers(model)
     if out is None:
         out = prepare_alloc(model, T)
     if stream != torch.cuda.current_stream():
@@ -187,11 +197,6 @@ def prepare_side(model, T, stream, out=None, after=None, dense_ready=None, flags
             stream.wait_event(after)
         else:
             stream.wait_stream(torch.cuda.current_stream())
-    import os
-    # the factorisation leaves only the dense factor, Lm^-1 comes from iwvi_gp_dense_inverse (nbk workgroups per layer): the factorising
-    # workgroups then hold their CUs for ~29 us instead of ~52 (two workgroups of the layer kernel wait for them) -- 0.268 -> 0.2635 ms per
-    # value + gradient at configs[2] (scripts/ab_bw_env.py, round 6).  IWVI_BW_DENSE=full: the factorising workgroup inverts as well
-    lm = os.environ.get("IWVI_BW_DENSE", "lm") == "lm"
     with torch.cuda.stream(stream):
         descs = []
         for i, l in gps:
@@ -201,28 +206,16 @@ def prepare_side(model, T, stream, out=None, after=None, dense_ready=None, flags
                     continue
                 d.flags |= _abi.GP_REUSE_FACTOR
             else:
-                d.flags |= _abi.GP_WANT_LM if lm else _abi.GP_WANT_DENSE
+                d.flags |= _abi.GP_WANT_LM
             descs.append(d)
         precompute_states(descs)
-        if lm and dense_ready is None:
+        if dense_ready is None:
+            # the factorisation leaves only the dense factor, Lm^-1 comes from iwvi_gp_dense_inverse (nbk workgroups per layer): the
+            # factorising workgroups then hold their CUs for ~29 us instead of ~52 (two workgroups of the layer kernel wait for them) --
+            # 0.268 -> 0.2635 ms per value + gradient at configs[2] against the factorising workgroup inverting as well (IWVI_GP_WANT_DENSE)
             arr_d = (_abi.GpDesc * len(descs))(*descs)
             _abi.check(_abi.lib().iwvi_gp_dense_inverse(arr_d, len(descs), _abi.stream_ptr()))
-        if 1 < len(gps) <= _abi.MAX_STACK:                       # every layer's operands in one launch
-            arr = (_abi.GpBwdDesc * len(gps))()
-            wsp = (ctypes.c_void_p * len(gps))()
-            keeps = []
-            for k, (i, l) in enumerate(gps):
-                b, keep = _param_desc(l, out[i][1])
-                b.flags |= flags
-                arr[k] = b
-                wsp[k] = out[i][0].data_ptr()
-                keeps.append(keep)
-            _abi.check(_abi.lib().iwvi_gp_layers_backward_prepare(arr, len(gps), T, wsp, _abi.stream_ptr()))
-        else:
-            for i, l in gps:
-                b, keep = _param_desc(l, out[i][1])
-                b.flags |= flags
-                _abi.check(_abi.lib().iwvi_gp_layer_backward_prepare(ctypes.byref(b), T, out[i][0].data_ptr(), _abi.stream_ptr()))
+        _pack_operands(gps, out, T, batched=1 < len(gps) <= _abi.MAX_STACK, flags=flags)
     return out
 
 
@@ -237,7 +230,6 @@ def gp_backward(layer, saved, d_sample=None, d_mean=None, d_var=None, kl_weight=
     dev = saved.F.device
     T, D = saved.F.shape
     M, R = layer.num_inducing, layer.num_outputs
-    kern = layer._base_kern()
     W = _abi.dev_tensor(layer.kern.W, "W") if isinstance(layer.kern, SharedMixedMok) else None
     P = W.shape[0] if W is not None else R
     ft = settings.float_type
@@ -274,7 +266,7 @@ def gp_backward(layer, saved, d_sample=None, d_mean=None, d_var=None, kl_weight=
     b.kl_weight = float(kl_weight)
     for k, t in out.items():
         setattr(b, k, t.data_ptr())
-    ws = prepared[0] if prepared else torch.empty(_abi.lib().iwvi_gp_layer_backward_ws_bytes(T, M, D, R), dtype=torch.uint8, device=dev)
+    ws = prepared[0] if prepared else _workspace(layer, T, D, dev)
     if side_stream is not None:                                  # parameter gradients beside the next layer's adjoint
         b.side_stream = ctypes.c_void_p(side_stream.cuda_stream)
         if side_stream2 is not None:
@@ -300,32 +292,32 @@ def gp_backward(layer, saved, d_sample=None, d_mean=None, d_var=None, kl_weight=
     return out
 
 
+def _encoder_adjoint_buffers(layer, XY, B, dev):
+    """-> (dW, db, the input rows' pointer, the encoder's ABI arguments, (dW pointers, db pointers, workspace), what to keep alive)."""
+    Wp, bp, dims, n, keep = layer.encoder.abi_args()
+    dW, db = [torch.empty_like(t) for t in keep[0]], [torch.empty_like(t) for t in keep[1]]
+    ws = torch.empty(_abi.lib().iwvi_encoder_backward_ws_bytes(B, dims, n), dtype=torch.uint8, device=dev)
+    XY = _abi.dev_tensor(XY.contiguous(), "encoder input")
+    return dW, db, _abi.ptr(XY), (Wp, bp, dims, n, layer.encoder.act), (_abi.ptr_array(dW), _abi.ptr_array(db), ws.data_ptr()), (keep, ws, XY)
+
+
 def lv_backward(layer, XY, enc_out, eps, dF_next, col0, w, B, K, sampled_kl=True, fused=True):
     """``iwvi_lv_layer_backward`` + ``iwvi_encoder_backward`` -> (dW list, db list) of the layer's encoder.
     ``enc_out`` [B, 2*latent_dim] = (means | raw) as the precompute launch leaves it (``layer._enc_out``)."""
     dev = enc_out.device
     Lw = layer.latent_dim
-    ft = settings.float_type
     enc_out = _abi.dev_tensor(enc_out, "enc_out")
+    # (means, raw, their row stride, ..., the adjoint of the layer above and the columns it has for this layer, the weights)
+    latent = (ctypes.c_void_p(enc_out.data_ptr()), ctypes.c_void_p(enc_out.data_ptr() + 4 * Lw), 2 * Lw, 1,
+              _abi.ptr(eps), _abi.ptr(dF_next), 0 if dF_next is None else dF_next.shape[1], col0,
+              _abi.ptr(w), Lw, B, K, 1 if sampled_kl else 0)
     if layer.encoder.custom_act is None and fused:
         # one launch: the encoder's workgroups form the d(means | raw) of their own rows (iwvi_lv_encoder_backward)
-        Wp, bp, dims, n, keep = layer.encoder.abi_args()
-        dW = [torch.empty_like(t) for t in keep[0]]
-        db = [torch.empty_like(t) for t in keep[1]]
-        dWp, dbp = _abi.ptr_array(dW), _abi.ptr_array(db)
-        ws = torch.empty(_abi.lib().iwvi_encoder_backward_ws_bytes(B, dims, n), dtype=torch.uint8, device=dev)
-        XY = _abi.dev_tensor(XY.contiguous(), "encoder input")
-        _abi.check(_abi.lib().iwvi_lv_encoder_backward(
-            ctypes.c_void_p(enc_out.data_ptr()), ctypes.c_void_p(enc_out.data_ptr() + 4 * Lw), 2 * Lw, 1,
-            _abi.ptr(eps), _abi.ptr(dF_next), 0 if dF_next is None else dF_next.shape[1], col0,
-            _abi.ptr(w), Lw, B, K, 1 if sampled_kl else 0,
-            _abi.ptr(XY), Wp, bp, dims, n, layer.encoder.act, dWp, dbp, ws.data_ptr(), _abi.stream_ptr()))
+        dW, db, xy, enc, out, _keep = _encoder_adjoint_buffers(layer, XY, B, dev)
+        _abi.check(_abi.lib().iwvi_lv_encoder_backward(*latent, xy, *enc, *out, _abi.stream_ptr()))
         return dW, db
-    d_enc = torch.empty(B, 2 * Lw, dtype=ft, device=dev)
-    _abi.check(_abi.lib().iwvi_lv_layer_backward(
-        ctypes.c_void_p(enc_out.data_ptr()), ctypes.c_void_p(enc_out.data_ptr() + 4 * Lw), 2 * Lw, 1,
-        _abi.ptr(eps), _abi.ptr(dF_next), 0 if dF_next is None else dF_next.shape[1], col0,
-        _abi.ptr(w), Lw, B, K, 1 if sampled_kl else 0, _abi.ptr(d_enc), _abi.stream_ptr()))
+    d_enc = torch.empty(B, 2 * Lw, dtype=settings.float_type, device=dev)
+    _abi.check(_abi.lib().iwvi_lv_layer_backward(*latent, _abi.ptr(d_enc), _abi.stream_ptr()))
     if layer.encoder.custom_act is not None:
         # a user-supplied activation: the encoder is torch ops (layers.Encoder.torch_raw), so are its weight gradients -- the
         # vector-Jacobian product of d(encoder output), which the kernel above formed
@@ -336,15 +328,228 @@ def lv_backward(layer, XY, enc_out, eps, dF_next, col0, w, B, K, sampled_kl=True
             raw = enc.torch_raw(_abi.dev_tensor(XY.contiguous(), "encoder input"), Ws, bs)
             gr = torch.autograd.grad(raw, Ws + bs, grad_outputs=d_enc)
         return list(gr[:len(Ws)]), list(gr[len(Ws):])
-    Wp, bp, dims, n, keep = layer.encoder.abi_args()
-    dW = [torch.empty_like(t) for t in keep[0]]
-    db = [torch.empty_like(t) for t in keep[1]]
-    dWp, dbp = _abi.ptr_array(dW), _abi.ptr_array(db)
-    ws = torch.empty(_abi.lib().iwvi_encoder_backward_ws_bytes(B, dims, n), dtype=torch.uint8, device=dev)
-    XY = _abi.dev_tensor(XY.contiguous(), "encoder input")
-    _abi.check(_abi.lib().iwvi_encoder_backward_act(_abi.ptr(XY), B, Wp, bp, dims, n, layer.encoder.act, _abi.ptr(d_enc), dWp, dbp,
-                                                   ws.data_ptr(), _abi.stream_ptr()))
+    dW, db, xy, enc, out, _keep = _encoder_adjoint_buffers(layer, XY, B, dev)
+    _abi.check(_abi.lib().iwvi_encoder_backward_act(xy, B, *enc, _abi.ptr(d_enc), *out, _abi.stream_ptr()))
     return dW, db
+
+
+def _checked(model, zs, mode_vi, gauss, exchange, wrt, overlap, q_moved, prepare_route):
+    """Everything the evaluation refuses before it queues work -> (zs: per layer None or [B, K, dim], final_q, inline)."""
+    layers = model.layers
+    B, K = model.X.shape[0], model.num_samples
+    zs = [None] * len(layers) if zs is None else list(zs)
+    if len(zs) != len(layers):
+        raise ValueError("zs needs one entry per layer")
+    if mode_vi:                                                  # [S*N, dim] -> the kernels' point-major order t = n*S + s
+        zs = [None if z is None else z.reshape(K, B, -1).transpose(0, 1).contiguous() for z in zs]
+    if not all(isinstance(layer, (GPLayer, LatentVariableLayer)) for layer in layers):
+        raise TypeError("the backward pass knows GPLayer and LatentVariableLayer")
+    if not mode_vi and getattr(model, "_joint_over_samples", lambda: False)():
+        raise NotImplementedError("an inner GPLayer with a plain (non-SharedMixedMok) kernel draws its K samples jointly "
+                                  "(temp_workaround.py:149-155); the hand-written adjoints cover the marginal-sampling stacks only")
+    n_lv = sum(isinstance(l, LatentVariableLayer) for l in layers)
+    if n_lv > 2:
+        raise NotImplementedError("the backward pass reads the encoder outputs of the precompute launch, which evaluates at most "
+                                  "2 latent-variable layers (%d in this model)" % n_lv)
+    if not gauss and exchange is not None:
+        raise NotImplementedError("K-sharded training exchanges the Gaussian tail's per-point pairs; a %s model trains on one rank "
+                                  "or N-sharded" % type(model.likelihood).__name__)
+    if wrt not in ("all", "final_q"):
+        raise ValueError("wrt is 'all' or 'final_q'")
+    final_q = wrt == "final_q"
+    inline = (not final_q) and len(_gp_layers(model)) <= _abi.MAX_STACK and prepare_route == "inline"
+    if q_moved is not None and (final_q or not overlap or inline):
+        raise ValueError("q_moved goes with wrt='all', overlap=True and the side-stream preparation")
+    return zs, final_q, inline
+
+
+def _prepare(model, T, cur, overlap, final_q, inline, q_moved):
+    """The adjoint's preparation and the forward's precompute, in the order the route needs -> (prepared, the stream to join before the first
+    ``gp_backward``): none (``final_q``: the q-only adjoint reads no prepared operand), side stream (default), ``q_moved``, inline."""
+    prep_stream = prepare_stream(model.X.device) if (overlap and not final_q) else cur
+    if q_moved is not None:
+        # the caller's own (short) precompute + layer launch are captured FIRST: behind the previous op's last node the first successor
+        # captured continues its hardware queue, the preparation -- 12 us of work, needed 50 us later -- takes the cross-queue dispatch
+        alloc = prepare_alloc(model, T)
+        after = torch.cuda.Event()
+        after.record(cur)
+        model.precompute(with_encoders=True, q_moved=set(q_moved))
+        # (the dense state's q(u) images are NOT refreshed: the adjoint reads nothing of them but the split-f16 scale of S_r = L_r L_r^T, which
+        #  the packing takes from L_r itself here (IWVI_BW_OWN_QSCALE) -- the preparation is k_prepare_all alone, ordered behind the start
+        #  of this op only and over long before the layer launch ends: no cross-queue join in front of the first chain)
+        return prepare_side(model, T, prep_stream, out=alloc, after=after, dense_ready=set(), flags=_abi.BW_OWN_QSCALE), prep_stream
+    if inline:
+        # IWVI_BW_PREPARE=inline: one factorisation for both passes (prepare_inline).  Measured, not the default: the inversion launch sits
+        # in front of the layer kernel (17 us at M = 128) where the side stream's dense factorisation costs the layer kernel 7 us and a
+        # join 10 -- configs[2] 0.318 vs 0.309 ms per value + gradient, configs[3] 8.98 vs 8.90 ms (DESIGN.md section 5b)
+        return prepare_inline(model, T), cur
+    # (queued BEFORE the caller's own precompute: queued after it -- ordered by an event only -- the dense factorisation lands beside the
+    # layer kernel instead, whose workgroups then wait for its two CUs: 0.355 -> 0.382 ms at configs[2])
+    prepared = {} if final_q else prepare_side(model, T, prep_stream)
+    model.precompute(with_encoders=True)
+    return prepared, prep_stream
+
+
+def _saving_forward(model, X, zs, mode_vi, try_fused, final_q, adj):
+    """ONE fused layer launch (behind ``_prepare``'s factorisation launch: packed operands, encoders) that also leaves what the adjoints need
+    in HBM (a = Lm^-1 k, the draws, every layer's output rows) -> (a ``GpSaved`` / ``LvSaved`` / None per layer, fused_heads).
+    The heads of the bound's adjoint (w, d / d final mean and variance, the sums: ``adj``) come out of the layer launch's own tail when the
+    bound is importance-weighted, unsharded, and every point's K samples sit in one chunk of the launch (include/iwvi_hip.h:
+    iwvi_elbo_desc.adj_*): two launches less in front of the first chain.  The library refuses (before launching anything) when the
+    launch's chunk does not hold whole points; ``_heads`` then makes the separate launch."""
+    B, K = model.X.shape[0], model.num_samples
+    T = B * K
+    zflat = [None if z is None else z.reshape(T, -1) for z in zs]
+    fused_heads = False
+    if try_fused:
+        try:
+            # (wrt = "final_q", the natural-gradient op: with the heads fused, of everything the launch can leave in HBM only the final
+            #  layer's a, draws and latent moments are read -- no per-layer rows, nothing of the inner layers: ~25 MB of stores less at configs[2])
+            _, outs, _ = model._fused_forward(T, K, B, (T,), zs=zflat, sampled_kl=True, want_layers=True, want_logw=True, want_saved=True,
+                                              elbo=dict(B=B, K=K, stride_b=K, stride_k=1, mode_vi=False, adj=adj),
+                                              outputs_for={len(model.layers) - 1} if final_q else None, moments=not final_q)
+            fused_heads = True
+        except _abi.IwviError as e:
+            if e.rc != _abi.ERR_UNSUPPORTED:                     # the library's "this stack cannot fuse the heads": the two-launch form
+                raise
+    if not fused_heads:
+        _, outs, _ = model._fused_forward(T, K, B, (T,), zs=zflat, sampled_kl=not mode_vi, want_layers=True, want_logw=False,
+                                          want_saved=True)
+    # (the layer launch itself advances the device-resident noise counter: the next evaluation draws fresh noise)
+    if fused_heads and final_q:                                  # only the final layer left anything (its adjoint reads a, noise, latent moments)
+        o, s = outs[-1], GpSaved()
+        s.F = torch.empty(T, model.layers[-1]._Z().shape[1], dtype=settings.float_type, device=X.device)   # (shape only: the q-only adjoint does not read the inputs)
+        s.T, s.A, s.U, s.noise, s.GMV = T, o["a_out"], o.get("u_out"), o["noise_out"], o["gmv_out"]
+        s.sample = s.mean = s.var = None
+        return [None] * (len(outs) - 1) + [s], fused_heads
+    saved, F = [], None
+    for layer, o in zip(model.layers, outs):
+        if isinstance(layer, LatentVariableLayer):
+            saved.append(LvSaved(layer._enc_out, o["noise_out"], o["kl_local"], X.shape[1] if F is None else F.shape[1]))
+        else:
+            if F is None:                                        # first layer: the tiled inputs (models.py:113)
+                F = X[:, None, :].expand(B, K, X.shape[1]).reshape(T, -1).contiguous()
+            s = GpSaved()
+            s.F, s.T, s.A, s.U, s.noise, s.GMV = F, T, o["a_out"], o.get("u_out"), o["noise_out"], o["gmv_out"]
+            s.sample, s.mean, s.var = o["sample"], o["mean"], o["var"]
+            saved.append(s)
+        F = o["sample"]
+    if not isinstance(saved[-1], GpSaved):
+        raise ValueError("the last layer must be a GPLayer")
+    return saved, fused_heads
+
+
+def _heads(model, saved, Y, mode_vi, gauss, fused_heads, exchange, K_total, cur, prep_stream, adj):
+    """The bound and the heads of its adjoint -> (elbo, grads with the likelihood parameter's gradient).  ``adj`` (w [T], d_mean, d_var [T, Dy],
+    sums [3]) was filled by the layer launch (``fused_heads``) or is here; sharded, against the job's logsumexp from ``exchange``."""
+    B, K, dev = model.X.shape[0], model.num_samples, model.X.device
+    fin = saved[-1]
+    kls = [s.kl for s in saved if isinstance(s, LvSaved)]        # (only the unfused heads read them)
+    klp = _abi.ptr_array(kls)
+    kld = (ctypes.c_int32 * max(len(kls), 1))(*[k.shape[1] for k in kls])
+    glob = [_abi.dev_tensor(g.reshape(-1), "global kl", torch.float64) for g in model._global_kls()]
+    glob_p = _abi.ptr_array(glob)
+    glob_n = (ctypes.c_int32 * max(len(glob), 1))(*[g.numel() for g in glob])
+    ws = torch.empty(2 * B, dtype=torch.float64, device=dev)
+    lse_g = None
+    if exchange is not None:
+        if mode_vi:
+            raise ValueError("the K-sharded exchange is for the importance-weighted bound")
+        _, _, ms = model._reduce(fin.mean, fin.var, Y, kls, [], B, K, stride_b=K, stride_k=1, mode_vi=False, want_ms=True)
+        from . import sharding
+        if sharding._RECORDER is not None and prep_stream != cur:
+            cur.wait_stream(prep_stream)                         # a segmented capture cuts the graph at the exchange: no forked work may be left open across the cut
+        lse_g = _abi.dev_tensor(exchange(ms).to(settings.float_type).contiguous(), "lse_global")
+    if not (gauss and fused_heads):
+        # (the two entries differ in one place: a likelihood descriptor in front, or the Gaussian's variance behind the KLs)
+        moments = (_abi.ptr(fin.mean), _abi.ptr(fin.var), _abi.ptr(Y), Y.shape[1], klp, kld, len(kls), B, K)
+        tail = (float(model.num_data) / float(B), 1 if mode_vi else 0, _abi.ptr(adj["w"]), _abi.ptr(adj["d_mean"]), _abi.ptr(adj["d_var"]),
+                glob_p, glob_n, len(glob), _abi.ptr(lse_g), int(K_total or K),
+                ctypes.c_void_p(adj["sums"].data_ptr()), ctypes.c_void_p(ws.data_ptr()), _abi.stream_ptr())
+        if gauss:
+            _abi.check(_abi.lib().iwvi_iw_elbo_backward_dev(*moments, *model.likelihood.desc_variance(), *tail))
+        else:
+            _abi.check(_abi.lib().iwvi_lik_elbo_backward(model.likelihood.lik_desc(), *moments, *tail))
+    lik_name = getattr(model.likelihood, "grad_name", "lik_var")    # (a class attribute: no read of the value, which may live on the device)
+    # sums[2]: scale * sum_n(...) - sum of the global KLs, formed on the device
+    return adj["sums"][2], ({} if lik_name is None else {lik_name: adj["sums"][1]})
+
+
+def _final_q_gradients(model, fin, adj, kl_weight, prefactor, cur):
+    """``wrt="final_q"``: of the adjoints only the final layer's two sums over samples -> its 'l<i>.q_mu' / 'l<i>.q_sqrt'."""
+    i = len(model.layers) - 1
+    g = gp_backward(model.layers[i], fin, d_mean=adj["d_mean"], d_var=adj["d_var"], kl_weight=kl_weight, q_only=True)
+    if prefactor:                                                # the point the dense factors may start from; the CALLER queues them (prefactor_dense)
+        done = torch.cuda.Event()                                # AFTER its update: the first successor captured behind these launches keeps their
+        done.record(cur)                                         # hardware queue, and that has to be the update, not the side work
+        model._prefactor_after = done
+    return {"l%d.q_mu" % i: g["dq_mu"], "l%d.q_sqrt" % i: g["dq_sqrt"]}
+
+
+def branch_placement(layers, overlap, branch_order):
+    """Where the reverse sweep queues the parameter branches -> (the layer whose branch is finished on the CALLER's stream, the layer
+    whose branch is split in two), -1 = none; every other branch runs whole on the side stream.  Host arithmetic on the stack's shape: a
+    placement changes no bit, only the time, so only its table in tests/test_backward_placement.py pins this policy."""
+    deferred = [j for j, l in enumerate(layers) if isinstance(l, GPLayer) and j > 0]      # (the bottom layer's branch is never deferred)
+    if not (deferred and overlap):
+        return -1, -1
+    # With two or more branches: a chain kernel fills every CU, so the branch of the layer above the lowest one does not get to run beside
+    # the lowest layer's chain anyway -- on the side stream it ends up IN FRONT of the lowest layer's branch, one after the other.  It is
+    # therefore queued on the caller's stream behind everything else there, and the lowest layer's branch runs whole on the side stream:
+    # the two branches then run side by side (configs[2]: 0.331 -> 0.307 ms per value + gradient).  IWVI_BW_BRANCH_ORDER=old: both on the side stream.
+    # (M <= 128 only: at M = 256 the branches are GEMM-sized and do overlap the chains -- configs[3]: 8.88 ms this way round, 9.09 ms the other)
+    # (Round 6, measured and not kept: every branch but the lowest queued on the side stream right behind its own chain, the lowest as
+    # two chains -- 0.268 -> 0.281 ms: the first successor captured behind a chain takes over its hardware queue, so the NEXT chain pays
+    # the cross-queue dispatch; and of a branch only its reduction runs beside a chain kernel (k_gl_tril does not fit next to a chain
+    # workgroup's LDS, the float64 products need 304 registers a wave): the rest queues up in front of the lowest branch.)
+    if len(deferred) >= 2 and branch_order != "old" and layers[deferred[1]].num_inducing <= 128:
+        return deferred[1], -1
+    # the LAST branch to be queued (the lowest GP layer that has one) runs as two chains: the adjoint of the factorisation on the side
+    # stream, every other sum on the caller's own stream -- nothing else is left to run there (0.364 -> 0.350 ms at configs[2])
+    return -1, deferred[0]
+
+
+def _reverse_sweep(model, saved, prepared, XY, adj, mode_vi, kl_weight, overlap, branch_order, cur, grads):
+    """The layers' adjoints, top to bottom, into ``grads``: the GP layers' per-sample chains back to back on the caller's stream ``cur``; a
+    layer's parameter branch ("_finish") is queued once the chain of the layer BELOW is, where ``branch_placement`` puts it."""
+    layers = model.layers
+    B, K = model.X.shape[0], model.num_samples
+    side = _side_stream(model.X.device) if overlap else None
+    on_cur, split = branch_placement(layers, overlap, branch_order)
+    held, dF = [], None
+    pending = finish_on_cur = None                               # pending: the parameter branch of the layer above
+    for i in range(len(layers) - 1, -1, -1):
+        layer, s = layers[i], saved[i]
+        if isinstance(s, GpSaved):
+            last = i == len(layers) - 1
+            g = gp_backward(layer, s, d_sample=None if last else dF, d_mean=adj["d_mean"] if last else None,
+                            d_var=adj["d_var"] if last else None, kl_weight=kl_weight, want_dF=i > 0,
+                            side_stream=side if i > 0 else None, keep=held, prepared=prepared.get(i), defer_params=True,
+                            # (one side stream: with the chains of consecutive layers back to back on the caller's stream -- defer_params --
+                            # a second one for the Cholesky-adjoint chain no longer pays: 0.400 -> 0.369 ms at configs[2] without it; alternating
+                            # the layers' branches between two side streams: 0.356 -> 0.379 ms)
+                            side_stream2=cur if i == split else None)
+            for k_out, k_name in (("dZ", "Z"), ("dls", "ls"), ("dvariance", "var"), ("dq_mu", "q_mu"), ("dq_sqrt", "q_sqrt"),
+                                  ("dW", "W"), ("dmf_A", "mfA")):
+                if k_out in g:
+                    grads["l%d.%s" % (i, k_name)] = g[k_out]
+            dF = g.get("dF")
+            if pending is not None:
+                pending()
+            pending = g.pop("_finish", None)
+            if i == on_cur:                                      # queued behind everything else on the caller's stream, below
+                finish_on_cur, pending = pending, None
+        else:
+            dW, db = lv_backward(layer, XY, s.enc_out, s.eps, dF, s.D_in, adj["w"], B, K, not mode_vi)
+            for j, (a, b) in enumerate(zip(dW, db)):
+                grads["l%d.encW%d" % (i, j)], grads["l%d.encb%d" % (i, j)] = a, b
+            dF = None if (dF is None or i == 0) else dF[:, :s.D_in].contiguous()
+    if pending is not None:
+        pending()
+    if finish_on_cur is not None:
+        finish_on_cur(cur)
+    if side is not None:
+        cur.wait_stream(side)                                    # join: the parameter gradients are complete on the caller's stream
 
 
 def iw_elbo_and_gradients(model, zs=None, mode_vi=None, exchange=None, K_total=None, kl_weight=1.0, overlap=True, wrt="all", fuse_heads=True,
@@ -376,240 +581,35 @@ def iw_elbo_and_gradients(model, zs=None, mode_vi=None, exchange=None, K_total=N
     A likelihood other than the Gaussian (``likelihoods.Bernoulli`` / ``StudentT``): the heads never come out of the layer launch
     (``fuse_heads`` is off) but from ``iwvi_lik_elbo_backward`` on the final layer's moments; the layer adjoints are the same.  The
     likelihood's gradient is named by its ``grad_name`` ('lik_scale' for the Student-t; the Bernoulli has none)."""
-    from .layers import LatentVariableLayer
     from .likelihoods import is_gaussian
     from .models import DGP_IWVI
-    from .temp_workaround import draw_normal
-    dev = model.X.device
-    ft = settings.float_type
+    dev, ft = model.X.device, settings.float_type
     B, K = model.X.shape[0], model.num_samples
     T = B * K
-    layers = model.layers
     mode_vi = (not isinstance(model, DGP_IWVI)) if mode_vi is None else bool(mode_vi)
-    zs = [None] * len(layers) if zs is None else list(zs)
-    if len(zs) != len(layers):
-        raise ValueError("zs needs one entry per layer")
-    if mode_vi:                                                  # [S*N, dim] -> the kernels' point-major order t = n*S + s
-        zs = [None if z is None else z.reshape(K, B, -1).transpose(0, 1).contiguous() for z in zs]
-    X = _abi.dev_tensor(model.X.contiguous(), "X")
-    Y = _abi.dev_tensor(model.Y.contiguous(), "Y")
-    for layer in layers:
-        if not isinstance(layer, (GPLayer, LatentVariableLayer)):
-            raise TypeError("the backward pass knows GPLayer and LatentVariableLayer")
-    if not mode_vi and getattr(model, "_joint_over_samples", lambda: False)():
-        raise NotImplementedError("an inner GPLayer with a plain (non-SharedMixedMok) kernel draws its K samples jointly "
-                                  "(temp_workaround.py:149-155); the hand-written adjoints cover the marginal-sampling stacks only")
-    n_lv = sum(isinstance(l, LatentVariableLayer) for l in layers)
-    if n_lv > 2:
-        raise NotImplementedError("the backward pass reads the encoder outputs of the precompute launch, which evaluates at most "
-                                  "2 latent-variable layers (%d in this model)" % n_lv)
-    has_lv = any(isinstance(l, LatentVariableLayer) for l in layers)
-    XY = model._xy_minibatch() if has_lv else None
     gauss = is_gaussian(model.likelihood)
-    if not gauss:
-        if exchange is not None:
-            raise NotImplementedError("K-sharded training exchanges the Gaussian tail's per-point pairs; a %s model trains on one rank "
-                                      "or N-sharded" % type(model.likelihood).__name__)
-        fuse_heads = False
-    # beside the forward, on its own stream: dense float64 factors + the parameter-only part of every layer's adjoint
+    prepare_route, branch_order = settings.backward_routes()
+    zs, final_q, inline = _checked(model, zs, mode_vi, gauss, exchange, wrt, overlap, q_moved, prepare_route)
+    X, Y = _abi.dev_tensor(model.X.contiguous(), "X"), _abi.dev_tensor(model.Y.contiguous(), "Y")
+    XY = model._xy_minibatch() if any(isinstance(l, LatentVariableLayer) for l in model.layers) else None
     cur = torch.cuda.current_stream()
-    import os
-    if wrt not in ("all", "final_q"):
-        raise ValueError("wrt is 'all' or 'final_q'")
-    final_q = wrt == "final_q"
-    prep_stream = _side_stream(dev, 2) if (overlap and not final_q) else cur
-    # (queued BEFORE the caller's own precompute: queued after it -- ordered by an event only -- the dense factorisation lands beside the
-    # layer kernel instead, whose workgroups then wait for its two CUs: 0.355 -> 0.382 ms at configs[2])
-    n_gp = sum(isinstance(l, GPLayer) for l in layers)
-    inline = (not final_q) and n_gp <= _abi.MAX_STACK and os.environ.get("IWVI_BW_PREPARE") == "inline"
-    if q_moved is not None and (final_q or not overlap or inline):
-        raise ValueError("q_moved goes with wrt='all', overlap=True and the side-stream preparation")
-    if q_moved is not None:
-        # the caller's own (short) precompute + layer launch are captured FIRST: behind the previous op's last node the first successor
-        # captured continues its hardware queue, the preparation -- 12 us of work, needed 50 us later -- takes the cross-queue dispatch
-        q_moved = set(q_moved)
-        alloc = prepare_alloc(model, T)
-        after = torch.cuda.Event()
-        after.record(cur)
-        model.precompute(with_encoders=True, q_moved=q_moved)
-        # (the dense state's q(u) images are NOT refreshed: the adjoint reads nothing of them but the split-f16 scale of S_r = L_r L_r^T, which
-        #  the packing takes from L_r itself here (IWVI_BW_OWN_QSCALE) -- the preparation is k_prepare_all alone, ordered behind the start
-        #  of this op only and over long before the layer launch ends: no cross-queue join in front of the first chain)
-        prepared = prepare_side(model, T, prep_stream, out=alloc, after=after, dense_ready=set(), flags=_abi.BW_OWN_QSCALE)
-    elif inline:
-        # IWVI_BW_PREPARE=inline: one factorisation for both passes (prepare_inline).  Measured, not the default: the inversion launch sits
-        # in front of the layer kernel (17 us at M = 128) where the side stream's dense factorisation costs the layer kernel 7 us and a
-        # join 10 -- configs[2] 0.318 vs 0.309 ms per value + gradient, configs[3] 8.98 vs 8.90 ms (DESIGN.md section 5b)
-        prepared = prepare_inline(model, T)
-        prep_stream = cur
-    else:
-        prepared = {} if final_q else prepare_side(model, T, prep_stream)
-        # forward: one factorisation launch (packed operands, encoders) + ONE fused layer launch that also leaves what the
-        # adjoints need in HBM (a = Lm^-1 k, the draws, every layer's output rows)
-        model.precompute(with_encoders=True)
-    zflat = [None if z is None else z.reshape(T, -1) for z in zs]
-    Dy = Y.shape[1]
-    w = torch.empty(T, dtype=ft, device=dev)
-    d_mean, d_var = torch.empty(T, Dy, dtype=ft, device=dev), torch.empty(T, Dy, dtype=ft, device=dev)
-    sums = torch.empty(3, dtype=torch.float64, device=dev)
-    # The heads of the bound's adjoint (w, d / d final mean and variance, the sums) come out of the layer launch's own tail when the
-    # bound is importance-weighted, unsharded, and every point's K samples sit in one chunk of the launch (include/iwvi_hip.h:
-    # iwvi_elbo_desc.adj_*): two launches less in front of the first chain.  The library refuses (before launching anything) when the
-    # launch's chunk does not hold whole points; the separate iwvi_iw_elbo_backward below then does it.
-    fused_heads = False
-    if (not mode_vi) and exchange is None and (K_total is None or int(K_total) == K) and fuse_heads:
-        try:
-            # (wrt = "final_q", the natural-gradient op: with the heads fused, of everything the launch can leave in HBM only the final
-            #  layer's a, draws and latent moments are read -- no per-layer rows, nothing of the inner layers: ~25 MB of stores less at configs[2])
-            slim = wrt == "final_q"
-            _, outs, _ = model._fused_forward(T, K, B, (T,), zs=zflat, sampled_kl=True, want_layers=True, want_logw=True, want_saved=True,
-                                              elbo=dict(B=B, K=K, stride_b=K, stride_k=1, mode_vi=False,
-                                                        adj=dict(w=w, d_mean=d_mean, d_var=d_var, sums=sums)),
-                                              outputs_for={len(layers) - 1} if slim else None, moments=not slim)
-            fused_heads = True
-        except _abi.IwviError as e:
-            if e.rc != _abi.ERR_UNSUPPORTED:                     # the library's "this stack cannot fuse the heads": the two-launch form below
-                raise
-    if not fused_heads:
-        _, outs, _ = model._fused_forward(T, K, B, (T,), zs=zflat, sampled_kl=not mode_vi, want_layers=True, want_logw=False,
-                                          want_saved=True)
-    # (the layer launch itself advances the device-resident noise counter: the next evaluation draws fresh noise)
-    saved = []
-    F = None
-    slim_q = fused_heads and wrt == "final_q"                    # only the final layer left anything (its adjoint reads a, noise, latent moments)
-    for i, (layer, o) in enumerate(zip(layers, outs)):
-        if slim_q:
-            if i < len(layers) - 1:
-                saved.append(("skipped",))
-                continue
-            s = GpSaved()
-            s.F = torch.empty(T, layer._Z().shape[1], dtype=ft, device=dev)        # (shape only: the q-only adjoint does not read the inputs)
-            s.T, s.A, s.U, s.noise, s.GMV = T, o["a_out"], o.get("u_out"), o["noise_out"], o["gmv_out"]
-            s.sample = s.mean = s.var = None
-            saved.append(("gp", s))
-            continue
-        if F is None and isinstance(layer, GPLayer):                              # first layer: the tiled inputs (models.py:113)
-            F = X[:, None, :].expand(B, K, X.shape[1]).reshape(T, -1).contiguous()
-        if isinstance(layer, LatentVariableLayer):
-            D_in = X.shape[1] if F is None else F.shape[1]
-            saved.append(("lv", layer._enc_out, o["noise_out"], o["kl_local"], D_in))
-        else:
-            s = GpSaved()
-            s.F, s.T, s.A, s.U, s.noise, s.GMV = F, T, o["a_out"], o.get("u_out"), o["noise_out"], o["gmv_out"]
-            s.sample, s.mean, s.var = o["sample"], o["mean"], o["var"]
-            saved.append(("gp", s))
-        F = o["sample"]
-    if saved[-1][0] != "gp":
-        raise ValueError("the last layer must be a GPLayer")
-    fin = saved[-1][1]
-    kls = [s[3] for s in saved if s[0] == "lv"]                  # (only the unfused heads read them)
-    klp = _abi.ptr_array(kls)
-    kld = (ctypes.c_int32 * max(len(kls), 1))(*[k.shape[1] for k in kls])
-    glob = [_abi.dev_tensor(g.reshape(-1), "global kl", torch.float64) for g in model._global_kls()]
-    glob_p = _abi.ptr_array(glob)
-    glob_n = (ctypes.c_int32 * max(len(glob), 1))(*[g.numel() for g in glob])
-    ws = torch.empty(2 * B, dtype=torch.float64, device=dev)
-    scale = float(model.num_data) / float(B)
-    lse_g = None
-    if exchange is not None:
-        if mode_vi:
-            raise ValueError("the K-sharded exchange is for the importance-weighted bound")
-        _, _, ms = model._reduce(fin.mean, fin.var, Y, kls, [], B, K, stride_b=K, stride_k=1, mode_vi=False, want_ms=True)
-        from . import sharding
-        if sharding._RECORDER is not None and prep_stream != cur:
-            cur.wait_stream(prep_stream)                         # a segmented capture cuts the graph at the exchange: no forked work may be left open across the cut
-        lse_g = _abi.dev_tensor(exchange(ms).to(ft).contiguous(), "lse_global")
-    if not gauss:
-        _abi.check(_abi.lib().iwvi_lik_elbo_backward(
-            model.likelihood.lik_desc(), _abi.ptr(fin.mean), _abi.ptr(fin.var), _abi.ptr(Y), Dy, klp, kld, len(kls), B, K,
-            scale, 1 if mode_vi else 0, _abi.ptr(w), _abi.ptr(d_mean), _abi.ptr(d_var),
-            glob_p, glob_n, len(glob), _abi.ptr(lse_g), int(K_total or K),
-            ctypes.c_void_p(sums.data_ptr()), ctypes.c_void_p(ws.data_ptr()), _abi.stream_ptr()))
-    lik_host, lik_dev = model.likelihood.desc_variance() if gauss else (1.0, None)
-    if gauss and not fused_heads:
-        _abi.check(_abi.lib().iwvi_iw_elbo_backward_dev(
-            _abi.ptr(fin.mean), _abi.ptr(fin.var), _abi.ptr(Y), Dy, klp, kld, len(kls), B, K,
-            lik_host, lik_dev, scale, 1 if mode_vi else 0, _abi.ptr(w), _abi.ptr(d_mean), _abi.ptr(d_var),
-            glob_p, glob_n, len(glob), _abi.ptr(lse_g), int(K_total or K),
-            ctypes.c_void_p(sums.data_ptr()), ctypes.c_void_p(ws.data_ptr()), _abi.stream_ptr()))
-    lik_name = getattr(model.likelihood, "grad_name", "lik_var")    # (a class attribute: no read of the value, which may live on the device)
-    grads = {} if lik_name is None else {lik_name: sums[1]}
-    elbo = sums[2]                                               # scale * sum_n(...) - sum of the global KLs, formed on the device
+    prepared, prep_stream = _prepare(model, T, cur, overlap, final_q, inline, q_moved)
+    adj = dict(w=torch.empty(T, dtype=ft, device=dev), d_mean=torch.empty(T, Y.shape[1], dtype=ft, device=dev),
+               d_var=torch.empty(T, Y.shape[1], dtype=ft, device=dev), sums=torch.empty(3, dtype=torch.float64, device=dev))
+    try_fused = fuse_heads and gauss and (not mode_vi) and exchange is None and (K_total is None or int(K_total) == K)
+    saved, fused_heads = _saving_forward(model, X, zs, mode_vi, try_fused, final_q, adj)
+    elbo, grads = _heads(model, saved, Y, mode_vi, gauss, fused_heads, exchange, K_total, cur, prep_stream, adj)
     if final_q:
-        i = len(layers) - 1
-        g = gp_backward(layers[i], fin, d_mean=d_mean, d_var=d_var, kl_weight=kl_weight, q_only=True)
-        if prefactor:                                            # the point the dense factors may start from; the CALLER queues them (prefactor_dense)
-            done = torch.cuda.Event()                            # AFTER its update: the first successor captured behind these launches keeps their
-            done.record(cur)                                     # hardware queue, and that has to be the update, not the side work
-            model._prefactor_after = done
-        return elbo, {"l%d.q_mu" % i: g["dq_mu"], "l%d.q_sqrt" % i: g["dq_sqrt"]}
+        return elbo, _final_q_gradients(model, saved[-1], adj, kl_weight, prefactor, cur)
     if prep_stream != cur:
         cur.wait_stream(prep_stream)                             # dense factors and packed adjoint operands are ready
-    side = _side_stream(dev) if overlap else None
-    held = []
-    dF = None
-    pending = None                                               # the parameter branch of the layer above, queued once this layer's chain is
-    # the LAST branch to be queued (the lowest GP layer that has one) runs as two chains: the adjoint of the factorisation on the side
-    # stream, every other sum on the caller's own stream -- nothing else is left to run there (0.364 -> 0.350 ms at configs[2])
-    deferred = [j for j, l in enumerate(layers) if isinstance(l, GPLayer) and j > 0]
-    last_deferred = min(deferred) if (deferred and overlap) else -1
-    # With two or more branches: a chain kernel fills every CU, so the branch of the layer above the lowest one does not get to run beside
-    # the lowest layer's chain anyway -- on the side stream it ends up IN FRONT of the lowest layer's branch, one after the other.  It is
-    # therefore queued on the caller's stream behind everything else there, and the lowest layer's branch runs whole on the side stream:
-    # the two branches then run side by side (configs[2]: 0.331 -> 0.307 ms per value + gradient).  IWVI_BW_BRANCH_ORDER=old: both on the side stream.
-    # (M <= 128 only: at M = 256 the branches are GEMM-sized and do overlap the chains -- configs[3]: 8.88 ms this way round, 9.09 ms the other)
-    # (Round 6, measured and not kept: every branch but the lowest queued on the side stream right behind its own chain, the lowest as
-    # two chains -- 0.268 -> 0.281 ms: the first successor captured behind a chain takes over its hardware queue, so the NEXT chain pays
-    # the cross-queue dispatch; and of a branch only its reduction runs beside a chain kernel (k_gl_tril does not fit next to a chain
-    # workgroup's LDS, the float64 products need 304 registers a wave): the rest queues up in front of the lowest branch.)
-    on_cur = sorted(deferred)[1] if (len(deferred) >= 2 and overlap and os.environ.get("IWVI_BW_BRANCH_ORDER") != "old"
-                                     and layers[sorted(deferred)[1]].num_inducing <= 128) else -1
-    finish_on_cur = None
-    for i in range(len(layers) - 1, -1, -1):
-        layer, s = layers[i], saved[i]
-        if s[0] == "gp":
-            last = i == len(layers) - 1
-            g = gp_backward(layer, s[1], d_sample=None if last else dF, d_mean=d_mean if last else None,
-                            d_var=d_var if last else None, kl_weight=kl_weight, want_dF=i > 0,
-                            side_stream=side if i > 0 else None, keep=held, prepared=prepared.get(i), defer_params=True,
-                            # (one side stream: with the chains of consecutive layers back to back on the caller's stream -- defer_params --
-                            # a second one for the Cholesky-adjoint chain no longer pays: 0.400 -> 0.369 ms at configs[2] without it; alternating
-                            # the layers' branches between two side streams: 0.356 -> 0.379 ms)
-                            side_stream2=cur if (i == last_deferred and on_cur < 0) else None)
-            for k_out, k_name in (("dZ", "Z"), ("dls", "ls"), ("dvariance", "var"), ("dq_mu", "q_mu"), ("dq_sqrt", "q_sqrt"),
-                                  ("dW", "W"), ("dmf_A", "mfA")):
-                if k_out in g:
-                    grads["l%d.%s" % (i, k_name)] = g[k_out]
-            dF = g.get("dF")
-            if i == on_cur:
-                finish_on_cur = g.pop("_finish", None)
-                if pending is not None:
-                    pending()
-                pending = None
-                continue
-            if pending is not None:
-                pending()
-            pending = g.pop("_finish", None)
-        else:
-            _, enc_out, eps, _, D_in = s
-            dW, db = lv_backward(layer, XY, enc_out, eps, dF, D_in, w, B, K, not mode_vi)
-            for j, (a, b) in enumerate(zip(dW, db)):
-                grads["l%d.encW%d" % (i, j)], grads["l%d.encb%d" % (i, j)] = a, b
-            dF = None if (dF is None or i == 0) else dF[:, :D_in].contiguous()
-    if pending is not None:
-        pending()
-    if finish_on_cur is not None:
-        finish_on_cur(cur)
-    if side is not None:
-        cur.wait_stream(side)                                    # join: the parameter gradients are complete on the caller's stream
-    del held
+    _reverse_sweep(model, saved, prepared, XY, adj, mode_vi, kl_weight, overlap, branch_order, cur, grads)
     return elbo, grads
 
 
 def parameter_list(model):
     """[(name, tensor)] of the model's tensor parameters, named like the gradients (host-scalar parameters -- kernel
     and likelihood variances -- are not tensors and are left to ``training.Trainer``)."""
-    from .layers import LatentVariableLayer
     out = []
     for i, l in enumerate(model.layers):
         if isinstance(l, LatentVariableLayer):

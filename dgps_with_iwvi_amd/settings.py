@@ -46,6 +46,16 @@ def use_f64_stage1(input_dim, override=None, measured=None):
 bw_f32_chain = bool(os.environ.get("IWVI_BW_F32_CHAIN"))
 
 
+def backward_routes():
+    """The two host-side route switches of the value + gradient evaluation -> (preparation: "inline" or "side", branch order: "old" or
+    "default"), from IWVI_BW_PREPARE / IWVI_BW_BRANCH_ORDER.  Read when CALLED, not at import: tests and scripts/ab_bw_env.py set them between
+    evaluations.  ``backward.iw_elbo_and_gradients`` asks once per evaluation, ``training.Trainer`` when it decides whether a step's two
+    ops may share a factorisation (the inline route factorises per evaluation).  Both non-default routes were measured slower
+    (backward.py says by how much); they stay as references for the stream-ordering tests."""
+    return ("inline" if os.environ.get("IWVI_BW_PREPARE") == "inline" else "side",
+            "old" if os.environ.get("IWVI_BW_BRANCH_ORDER") == "old" else "default")
+
+
 def split16_variance_ok(num_inducing, variance):
     """False for a GP layer whose launch must take the fp32-MFMA variant (``IWVI_LAYER_F32_STAGE2``) whatever ``fw_f32_stage2`` says: M > 240
     and kernel variance / jitter >= 2^30.  The split-f16 image of the super-block inverses holds 2^ceil(log2 sigma) (L_II)^-1 as f16 pairs;

@@ -242,9 +242,11 @@ class Trainer:
 
     def _one_factor(self):
         """``step`` shares one factorisation between its two ops: single rank (a sharded step's collectives sit between the first op's
-        evaluation and its update -- the dense factors would be in flight across them), N-layout."""
+        evaluation and its update -- the dense factors would be in flight across them), N-layout, and the side-stream preparation (the
+        inline route takes the adjoint's operands from each evaluation's own factorisation: ``q_moved`` has nothing to reuse there)."""
         from . import sharding as _sh
-        return self.one_factorisation and self.world == 1 and self.shard != "k" and not _sh._FORCE_ONE_RANK_COLLECTIVES
+        return (self.one_factorisation and self.world == 1 and self.shard != "k" and not _sh._FORCE_ONE_RANK_COLLECTIVES
+                and settings.backward_routes()[0] != "inline")
 
     def natgrad_op(self, zs=None, _advance=True, _prefactor=False):
         """``op_ng``: one ELBO + gradient evaluation, natural-gradient step on the final layer's q(u).  Only that layer's

@@ -1,5 +1,5 @@
 """A/B of host-side routes of the value + gradient evaluation that are chosen by an environment variable when the evaluation is queued
-(IWVI_BW_BRANCH_ORDER, IWVI_BW_DENSE, IWVI_BW_PREPARE ...): one captured graph per setting, replayed alternately in ONE process; the
+(IWVI_BW_BRANCH_ORDER, IWVI_BW_PREPARE: settings.backward_routes): one captured graph per setting, replayed alternately in ONE process; the
 gradients of the settings compared on the same injected noise.
 Usage: python scripts/ab_bw_env.py VAR=a,b [VAR2=c,d ...] [--config 2] [--rounds 5] [--iters 50]   (the cross product is timed)"""
 import argparse

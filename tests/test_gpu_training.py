@@ -365,16 +365,21 @@ def test_graph_mode_training_step_equals_the_eager_one(gpu_device):
     assert out[0][2] != spec["lik_var"]                          # the likelihood variance did move (and was read back lazily)
 
 
-@pytest.mark.parametrize("case", ["full_batch_eager", "full_batch_graph", "minibatch_graph", "f64_route_graph"])
-def test_one_factorisation_per_step_is_the_same_step(gpu_device, case):
+@pytest.mark.parametrize("case", ["full_batch_eager", "full_batch_graph", "minibatch_graph", "f64_route_graph",
+                                  "inline_prepare_eager", "inline_prepare_graph"])
+def test_one_factorisation_per_step_is_the_same_step(gpu_device, case, monkeypatch):
     """Trainer(one_factorisation=True), the default: the Adam op re-packs the final layer's q(u) images instead of factorising every
     K_uu again (IWVI_GP_REUSE_FACTOR), and its dense factors were formed beside the natural-gradient update of the first op
     (IWVI_GP_FACTOR_ONLY on the layer whose q(u) is being written).  Same kernels on the same numbers: bounds and parameters are
     bit-identical to the step that factorises per op -- eager and captured, full-batch (one graph) and minibatched (two graphs), and
-    with an inner layer on the float64 stage-1 route (its Lm^-1 and z~ images must survive the short precompute)."""
+    with an inner layer on the float64 stage-1 route (its Lm^-1 and z~ images must survive the short precompute).
+    inline_prepare_*: with IWVI_BW_PREPARE=inline the adjoint's operands come from each evaluation's own factorisation, so the default
+    trainer factorises per op as well (it used to raise: ``q_moved`` is refused with that route) -- the two trainers are the same step."""
     from dgps_with_iwvi_amd import synthetic, settings
     from dgps_with_iwvi_amd.training import Trainer
     graph = not case.endswith("eager")
+    if case.startswith("inline_prepare"):
+        monkeypatch.setenv("IWVI_BW_PREPARE", "inline")
     if case == "f64_route_graph":
         spec = synthetic.make_spec(L=2, M=32, B=64, K=5, with_lv=False, seed=31, Dx=2)
     elif case == "minibatch_graph":
