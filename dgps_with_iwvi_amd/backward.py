@@ -462,7 +462,7 @@ def _heads(model, saved, Y, mode_vi, gauss, fused_heads, exchange, K_total, cur,
         lse_g = _abi.dev_tensor(exchange(ms).to(settings.float_type).contiguous(), "lse_global")
     if not (gauss and fused_heads):
         # (the two entries differ in one place: a likelihood descriptor in front, or the Gaussian's variance behind the KLs)
-        moments = (_abi.ptr(fin.mean), _abi.ptr(fin.var), _abi.ptr(Y), Y.shape[1], klp, kld, len(kls), B, K)
+        moments = (_abi.ptr(fin.mean), _abi.ptr(fin.var), _abi.ptr(Y), adj["d_mean"].shape[1], klp, kld, len(kls), B, K)
         tail = (float(model.num_data) / float(B), 1 if mode_vi else 0, _abi.ptr(adj["w"]), _abi.ptr(adj["d_mean"]), _abi.ptr(adj["d_var"]),
                 glob_p, glob_n, len(glob), _abi.ptr(lse_g), int(K_total or K),
                 ctypes.c_void_p(adj["sums"].data_ptr()), ctypes.c_void_p(ws.data_ptr()), _abi.stream_ptr())
@@ -578,10 +578,11 @@ def iw_elbo_and_gradients(model, zs=None, mode_vi=None, exchange=None, K_total=N
     oracle/grad_oracle.py: 'l<i>.Z', 'l<i>.ls', 'l<i>.var', 'l<i>.q_mu', 'l<i>.q_sqrt', 'l<i>.W', 'l<i>.mfA' (layers with
     a mixing matrix / linear mean function), 'l<i>.encW<j>', 'l<i>.encb<j>', 'lik_var'.  ``zs``: one noise tensor per layer ([B, K, dim]) or None -> drawn.
 
-    A likelihood other than the Gaussian (``likelihoods.Bernoulli`` / ``StudentT``): the heads never come out of the layer launch
+    A likelihood other than the Gaussian (``likelihoods.Bernoulli`` / ``StudentT`` / ``MultiClass``): the heads never come out of the layer launch
     (``fuse_heads`` is off) but from ``iwvi_lik_elbo_backward`` on the final layer's moments; the layer adjoints are the same.  The
-    likelihood's gradient is named by its ``grad_name`` ('lik_scale' for the Student-t; the Bernoulli has none)."""
-    from .likelihoods import is_gaussian
+    likelihood's gradient is named by its ``grad_name`` ('lik_scale' for the Student-t; the Bernoulli and MultiClass have none).  With
+    ``MultiClass`` Y is one column of labels and the heads are [T, C]."""
+    from .likelihoods import is_gaussian, output_dim
     from .models import DGP_IWVI
     dev, ft = model.X.device, settings.float_type
     B, K = model.X.shape[0], model.num_samples
@@ -594,8 +595,9 @@ def iw_elbo_and_gradients(model, zs=None, mode_vi=None, exchange=None, K_total=N
     XY = model._xy_minibatch() if any(isinstance(l, LatentVariableLayer) for l in model.layers) else None
     cur = torch.cuda.current_stream()
     prepared, prep_stream = _prepare(model, T, cur, overlap, final_q, inline, q_moved)
-    adj = dict(w=torch.empty(T, dtype=ft, device=dev), d_mean=torch.empty(T, Y.shape[1], dtype=ft, device=dev),
-               d_var=torch.empty(T, Y.shape[1], dtype=ft, device=dev), sums=torch.empty(3, dtype=torch.float64, device=dev))
+    Dy = output_dim(model.likelihood, Y.shape[1])                # (MultiClass: one column of labels against C outputs and heads)
+    adj = dict(w=torch.empty(T, dtype=ft, device=dev), d_mean=torch.empty(T, Dy, dtype=ft, device=dev),
+               d_var=torch.empty(T, Dy, dtype=ft, device=dev), sums=torch.empty(3, dtype=torch.float64, device=dev))
     try_fused = fuse_heads and gauss and (not mode_vi) and exchange is None and (K_total is None or int(K_total) == K)
     saved, fused_heads = _saving_forward(model, X, zs, mode_vi, try_fused, final_q, adj)
     elbo, grads = _heads(model, saved, Y, mode_vi, gauss, fused_heads, exchange, K_total, cur, prep_stream, adj)

@@ -120,7 +120,9 @@ def attach_train_op(model, ARGS):
 def likelihood_state(lik):
     """A Gaussian is stored as ever ('likelihood.variance'); any other likelihood under 'likelihood.type' (its class name) and
     'likelihood.params' (its parameters in the order of the constructor)."""
-    from .likelihoods import Bernoulli, StudentT
+    from .likelihoods import Bernoulli, MultiClass, StudentT
+    if isinstance(lik, MultiClass):
+        return {"likelihood.type": np.str_("MultiClass"), "likelihood.params": np.array([lik.num_classes, lik.epsilon], dtype=np.float64)}
     if isinstance(lik, StudentT):
         return {"likelihood.type": np.str_("StudentT"), "likelihood.params": np.array([lik.scale, lik.df], dtype=np.float64)}
     if isinstance(lik, Bernoulli):
@@ -131,14 +133,19 @@ def likelihood_state(lik):
 def load_likelihood_state(lik, state):
     """Into the model's own likelihood object (a trainer's device master is bound to it).  A file without 'likelihood.type' was written
     for a Gaussian -- every file from before the other likelihoods existed."""
-    from .likelihoods import Bernoulli, StudentT
+    from .likelihoods import Bernoulli, MultiClass, RobustMax, StudentT
     kind = str(state["likelihood.type"]) if "likelihood.type" in state else "Gaussian"
-    have = "StudentT" if isinstance(lik, StudentT) else "Bernoulli" if isinstance(lik, Bernoulli) else "Gaussian"   # (as likelihood_state: subclasses count)
+    have = "MultiClass" if isinstance(lik, MultiClass) else "StudentT" if isinstance(lik, StudentT) else "Bernoulli" if isinstance(lik, Bernoulli) else "Gaussian"   # (as likelihood_state: subclasses count)
     if kind != have:
         raise ValueError("the checkpoint holds a %s likelihood, the model a %s" % (kind, type(lik).__name__))
     if kind == "StudentT":
         scale, df = (float(v) for v in np.asarray(state["likelihood.params"]).reshape(-1))
         lik.scale, lik.df = scale, df
+    elif kind == "MultiClass":
+        C, eps = (float(v) for v in np.asarray(state["likelihood.params"]).reshape(-1))
+        if int(C) != lik.num_classes:
+            raise ValueError("the checkpoint holds a MultiClass over %d classes, the model one over %d" % (int(C), lik.num_classes))
+        lik.invlink = RobustMax(lik.num_classes, eps)
     elif kind == "Gaussian":
         lik.variance = float(state["likelihood.variance"])
 

@@ -1,0 +1,62 @@
+// What csrc/likelihood_tail.hip and csrc/likelihood_multiclass.hip share: the Gauss-Hermite tables, the kernel-argument structs of the
+// iwvi_lik_* entry points and the segment reductions (moved here verbatim from likelihood_tail.hip), and the launchers of the
+// multi-class kernels, which the entry points of likelihood_tail.hip call for IWVI_LIK_MULTICLASS.
+#pragma once
+#include "iwvi_common.h"
+
+namespace iwvi {
+
+// numpy.polynomial.hermite.hermgauss(20): the rule is symmetric, x_(19-i) = -x_i with equal weights -- the ten positive nodes, their
+// weights w_i / sqrt(pi) and the logarithms of those (log-space sums).  Rounded to float32 the twenty weights sum to 1 - 5e-9.
+__device__ __constant__ const float GH_X[10] = {2.453407083e-01f, 7.374737285e-01f, 1.234076215e+00f, 1.738537712e+00f, 2.254974002e+00f,
+                                                2.788806058e+00f, 3.347854567e+00f, 3.944764040e+00f, 4.603682450e+00f, 5.387480890e+00f};
+__device__ __constant__ const float GH_W[10] = {2.607930634e-01f, 1.617393340e-01f, 6.150637206e-02f, 1.399783745e-02f, 1.830103131e-03f,
+                                                1.288262800e-04f, 4.402121090e-06f, 6.127490260e-08f, 2.482062362e-10f, 1.257800672e-13f};
+__device__ __constant__ const float GH_LOGW[10] = {-1.344028046e+00f, -1.821769289e+00f, -2.788614499e+00f, -4.268852429e+00f, -6.303382958e+00f,
+                                                   -8.957045728e+00f, -1.233342407e+01f, -1.660789550e+01f, -2.211676112e+01f, -2.970424151e+01f};
+
+struct Lik { int type; float p0, p1, lgc; const float* p0_dev; };
+
+constexpr int LIK_MAX_GLOB = 16;
+struct LikReduceArgs {
+    Lik lik;
+    const float* fmean; const float* fvar; const float* Y;
+    const float* kl[IWVI_MAX_KL]; int kl_dims[IWVI_MAX_KL]; int n_kl;
+    long long B, stride_b, stride_k; int K, Dy, K_total, mode_vi;
+    float* ms; float* logp;
+    double* elbo; unsigned long long* ticket; double scale;
+    const double* klg[LIK_MAX_GLOB]; int klg_n[LIK_MAX_GLOB]; int n_glob;
+};
+
+template <int SEG>
+__device__ __forceinline__ float lseg_max(float v) {
+#pragma unroll
+    for (int o = SEG / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+template <int SEG>
+__device__ __forceinline__ double lseg_sum(double v) {
+#pragma unroll
+    for (int o = SEG / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+constexpr int LIK_THREADS = 256;
+
+struct LikBwdArgs {
+    Lik lik;
+    const float* fmean; const float* fvar; const float* Y; int Dy;
+    const float* kl[IWVI_MAX_KL]; int kl_dims[IWVI_MAX_KL]; int n_kl;
+    long long B; int K; double scale; int mode_vi;
+    const float* lse_global; int K_total;
+    float* w; float* d_mean; float* d_var; double* part;   // part[0..B) = lse - log K, part[B..2B) = d param[0] share
+};
+
+// ---- csrc/likelihood_multiclass.hip (IWVI_LIK_MULTICLASS: lik.p0 = epsilon, lik.p1 = Dy = the number of classes, Y one column of labels) ----
+int mc_launch_elbo(const LikReduceArgs& g, hipStream_t stream);                   // k_mc_elbo<SEG>
+int mc_launch_elbo_bwd(const LikBwdArgs& a, hipStream_t stream);                  // k_mc_elbo_bwd (the caller launches k_lik_finish behind it)
+// mode 0: variational_expectations, 1: predict_density (Fvar == NULL: logp) -> out [T]; 2: predict_mean_and_var -> out, out2 [T, C]
+int mc_launch_elem(const char* what, int mode, const Lik& L, const float* Fmu, const float* Fvar, const float* Y, long long T, int C,
+                   long long row_div, long long row_mod, float* out, float* out2, hipStream_t stream);
+
+}  // namespace iwvi

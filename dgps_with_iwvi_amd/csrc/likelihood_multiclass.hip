@@ -1,0 +1,288 @@
+// GPflow 1.x MultiClass(num_classes) with the RobustMax link (include/iwvi_hip.h: IWVI_LIK_MULTICLASS), behind the iwvi_lik_* entry
+// points of csrc/likelihood_tail.hip.  Unlike the likelihoods there, the expectation couples all C outputs of a sample, and the targets
+// are ONE column of class labels:
+//   p = prob_is_largest(y; mu, v) = sum_i w_i prod_{c != y} Phi~((X_i - mu_c) / sqrt(max(v_c, 1e-10))),  X_i = mu_y + x_i sqrt(max(2 v_y, 1e-10)),
+//   Phi~(d) = Phi(d) (1 - 2e-4) + 1e-4      -- the 20-point rule of likelihood_common.h; clips and jitter are GPflow's, part of the definition
+//   variational_expectations = p log(1 - eps) + (1 - p) log(eps / (C - 1)).
+// C is a runtime value: the class loop is OUTSIDE and the (unrolled) node loop inside, so the twenty running products live in registers
+// and per class mu_c and 1 / sigma_c are loaded once -- a per-class array would be indexed dynamically and land in scratch.
+#include "likelihood_common.h"
+
+namespace iwvi {
+
+constexpr float MC_CLIP = 1e-10f;                // tf.clip_by_value(., 1e-10, inf) on 2 v_y and on v_c
+constexpr float MC_JIT = 1e-4f;                  // the cdf jitter of prob_is_largest
+
+// Phi(d) = erfc(-d / sqrt 2) / 2: neither tail cancels
+__device__ __forceinline__ float mc_cdf(float d) { return 0.5f * erfcf(-d * 0.70710678118654752f) * (1.f - 2.f * MC_JIT) + MC_JIT; }
+
+// a label as the kernels index with it: kept inside [0, C) whatever the float holds (the Python side refuses other targets on the host)
+__device__ __forceinline__ int mc_label(float y, int C) { return min(max((int)y, 0), C - 1); }
+
+// p for label y of one sample (mu, var: its C moments); pa[j] / pb[j]: the products at the nodes +x_j / -x_j, a = sqrt(max(2 v_y, clip))
+__device__ __forceinline__ float mc_prob(const float* __restrict__ mu, const float* __restrict__ var, int C, int y,
+                                         float (&pa)[10], float (&pb)[10], float& a) {
+    const float mu_y = mu[y];
+    a = sqrtf(fmaxf(2.f * var[y], MC_CLIP));
+#pragma unroll
+    for (int j = 0; j < 10; ++j) pa[j] = pb[j] = 1.f;
+    for (int c = 0; c < C; ++c) {
+        if (c == y) continue;
+        const float dm = mu_y - mu[c], rs = 1.f / sqrtf(fmaxf(var[c], MC_CLIP));
+#pragma unroll
+        for (int j = 0; j < 10; ++j) {
+            const float xa = a * GH_X[j];
+            pa[j] *= mc_cdf((dm + xa) * rs);
+            pb[j] *= mc_cdf((dm - xa) * rs);
+        }
+    }
+    float p = 0.f;
+#pragma unroll
+    for (int j = 0; j < 10; ++j) p = fmaf(GH_W[j], pa[j] + pb[j], p);
+    return p;
+}
+
+// l0 = log eps_1, l1 = log(1 - eps).  The expectation is formed as p l1 + (1 - p) l0, not l0 + p (l1 - l0): near p = 1 the result is ~ -eps and
+// the second form would carry the rounding of |l0| ~ 9; its derivative with respect to p is l1 - l0 either way.
+__device__ __forceinline__ void mc_logs(const Lik& L, int C, float& l0, float& l1) {
+    l0 = logf(L.p0 / (float)(C - 1));
+    l1 = log1pf(-L.p0);
+}
+__device__ __forceinline__ float mc_ve(float p, float l0, float l1) { return fmaf(p, l1, (1.f - p) * l0); }
+
+// gs * dp/dmu_c -> dmean[c], gs * dp/dv_c -> dvar[c] for all C classes: a second pass over the classes that recomputes d_ci and Phi~_ci and
+// divides the full product P_i by it (Phi~ >= 1e-4).  Through an active clip the derivative is zero, as tf.clip_by_value gives.
+__device__ __forceinline__ void mc_heads(const float* __restrict__ mu, const float* __restrict__ var, int C, int y, float gs,
+                                         float* __restrict__ dmean, float* __restrict__ dvar) {
+    float pa[10], pb[10], a;
+    mc_prob(mu, var, C, y, pa, pb, a);
+#pragma unroll
+    for (int j = 0; j < 10; ++j) {                 // w_i P_i (1 - 2 jit) / sqrt(2 pi)
+        const float w = GH_W[j] * (1.f - 2.f * MC_JIT) * 0.3989422804014327f;
+        pa[j] *= w; pb[j] *= w;
+    }
+    const float mu_y = mu[y];
+    float gmy = 0.f, gvy = 0.f;
+    for (int c = 0; c < C; ++c) {
+        if (c == y) continue;
+        const float vc = var[c];
+        const float dm = mu_y - mu[c], rs = 1.f / sqrtf(fmaxf(vc, MC_CLIP));
+        float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll
+        for (int j = 0; j < 10; ++j) {
+            const float xa = a * GH_X[j];
+            const float da = (dm + xa) * rs, db = (dm - xa) * rs;
+            const float ra = pa[j] * __expf(-0.5f * da * da) / mc_cdf(da);
+            const float rb = pb[j] * __expf(-0.5f * db * db) / mc_cdf(db);
+            s1 += ra + rb;
+            s2 = fmaf(ra, da, fmaf(rb, db, s2));
+            s3 = fmaf(GH_X[j], ra - rb, s3);
+        }
+        if (dmean) dmean[c] = -gs * s1 * rs;
+        if (dvar) dvar[c] = vc >= MC_CLIP ? -gs * s2 * 0.5f * rs * rs : 0.f;
+        gmy = fmaf(s1, rs, gmy);
+        gvy = fmaf(s3, rs, gvy);
+    }
+    if (dmean) dmean[y] = gs * gmy;
+    if (dvar) dvar[y] = 2.f * var[y] >= MC_CLIP ? gs * gvy / a : 0.f;
+}
+
+// ------------------------------------------------------------------------------------------
+// The reduction: k_lik_elbo (csrc/likelihood_tail.hip) with the coupled expectation in place of the per-output quadrature.  SEG lanes per
+// data point, one lane per sample; float32 inside a sample, the log-sum-exp over K and the sum over the points in float64; the same
+// release / ticket / acquire epilogue.
+// ------------------------------------------------------------------------------------------
+template <int SEG>
+__global__ __launch_bounds__(LIK_THREADS) void k_mc_elbo(LikReduceArgs g) {
+    __shared__ double red[LIK_THREADS];
+    __shared__ int is_last;
+    const int tid = threadIdx.x, sl = tid % SEG, sg = tid / SEG;
+    constexpr int PPP = LIK_THREADS / SEG;
+    const int K = g.K, C = g.Dy;
+    float l0, l1;
+    mc_logs(g.lik, C, l0, l1);
+    {
+        const long long b = (long long)blockIdx.x * PPP + sg;
+        const bool live = b < g.B;                    // uniform within a segment
+        const int y = live ? mc_label(g.Y[b], C) : 0;
+        float m = -INFINITY;
+        double ssum = 0.0, lsum = 0.0;
+        for (int k0 = 0; k0 < K; k0 += SEG) {
+            const int k = k0 + sl;
+            const bool on = live && k < K;
+            float L = -INFINITY;
+            if (on) {
+                const long long t = b * g.stride_b + k * g.stride_k;
+                float pa[10], pb[10], a;
+                float acc = mc_ve(mc_prob(g.fmean + t * C, g.fvar + t * C, C, y, pa, pb, a), l0, l1);
+                for (int i = 0; i < g.n_kl; ++i)
+                    for (int d = 0; d < g.kl_dims[i]; ++d) acc -= g.kl[i][t * g.kl_dims[i] + d];
+                L = acc;
+            }
+            if (g.mode_vi) { lsum += lseg_sum<SEG>(on ? (double)L : 0.0); continue; }
+            const float nm = fmaxf(m, lseg_max<SEG>(L));
+            const double cs = lseg_sum<SEG>(on ? (double)__expf(L - nm) : 0.0);
+            ssum = (m == -INFINITY ? 0.0 : ssum * (double)__expf(m - nm)) + cs;
+            m = nm;
+        }
+        if (live && sl == 0) {
+            if (g.mode_vi) {
+                if (g.logp) g.logp[b] = (float)(lsum / (double)K);                                   // models.py:84
+            } else {
+                if (g.ms) { g.ms[2 * b] = m; g.ms[2 * b + 1] = (float)ssum; }
+                if (g.logp) g.logp[b] = (float)((double)m + log(ssum) - log((double)g.K_total));     // models.py:148
+            }
+        }
+    }
+    if (!g.elbo) return;
+    // ---- publish this workgroup's logp, draw a ticket, the last arriver sums everything ----
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned long long t = __hip_atomic_fetch_add(g.ticket, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = (t == (unsigned long long)gridDim.x - 1);
+        if (last) {
+            __hip_atomic_store(g.ticket, 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next call
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        is_last = last;
+    }
+    __syncthreads();
+    if (!is_last) return;
+    double acc = 0.0;
+    for (long long b = tid; b < g.B; b += LIK_THREADS) acc += (double)g.logp[b];
+    red[tid] = acc;
+    __syncthreads();
+    for (int s2 = LIK_THREADS / 2; s2 > 0; s2 >>= 1) {
+        if (tid < s2) red[tid] += red[tid + s2];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double kl = 0.0;
+        for (int i = 0; i < g.n_glob; ++i)
+            for (int c = 0; c < g.klg_n[i]; ++c) kl += g.klg[i][c];
+        *g.elbo = red[0] * g.scale - kl;                                                              // models.py:150
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Heads of the bound's adjoint: k_lik_elbo_bwd with the coupled expectation.  One wave per data point, lanes over its K samples striding
+// by 64.  Pass 1: L_nk and the running (max, sum exp); pass 2: the weights and the 2 C heads of every sample.  There is no trained
+// parameter: part[B..2B) = 0.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_mc_elbo_bwd(LikBwdArgs a) {
+    const int lane = threadIdx.x & 63;
+    const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= a.B) return;
+    const int C = a.Dy;
+    const int y = mc_label(a.Y[b], C);
+    float l0, l1;
+    mc_logs(a.lik, C, l0, l1);
+    const float dl = l1 - l0;
+    auto logw = [&](long long t) {
+        float pa[10], pb[10], aa;
+        float l = mc_ve(mc_prob(a.fmean + t * C, a.fvar + t * C, C, y, pa, pb, aa), l0, l1);
+        for (int i = 0; i < a.n_kl; ++i)
+            for (int q = 0; q < a.kl_dims[i]; ++q) l -= a.kl[i][t * a.kl_dims[i] + q];
+        return l;
+    };
+    const bool one = a.K <= 64;                          // every lane holds its only sample's L_nk: no second evaluation
+    float Lc = -INFINITY, mx = -INFINITY;
+    double se = 0.0;
+    if (a.mode_vi) {                                    // models.py:84: mean over the samples -> uniform weights
+        for (int k = lane; k < a.K; k += 64) se += (double)logw(b * a.K + k);
+        for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
+    } else {
+        for (int k = lane; k < a.K; k += 64) { Lc = logw(b * a.K + k); mx = fmaxf(mx, Lc); }
+        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+        if (a.lse_global) {                             // weights against the whole job's normaliser: exp(L - LSE)
+            mx = a.lse_global[b]; se = 1.0;
+        } else {
+            for (int k = lane; k < a.K; k += 64) se += (double)__expf((one ? Lc : logw(b * a.K + k)) - mx);
+            for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
+        }
+    }
+    for (int k = lane; k < a.K; k += 64) {
+        const long long t = b * a.K + k;
+        float wt;
+        if (a.mode_vi) wt = (float)(a.scale / (double)a.K);
+        else wt = (float)(a.scale * (double)__expf((one ? Lc : logw(t)) - mx) / se);
+        if (a.w) a.w[t] = wt;
+        if (a.d_mean || a.d_var)
+            mc_heads(a.fmean + t * C, a.fvar + t * C, C, y, wt * dl, a.d_mean ? a.d_mean + t * C : nullptr, a.d_var ? a.d_var + t * C : nullptr);
+    }
+    if (lane == 0) {
+        a.part[b] = a.mode_vi ? se / (double)a.K : (double)mx + log(se) - log((double)(a.lse_global ? a.K_total : a.K));
+        a.part[a.B + b] = 0.0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Elementwise callables.  MODE 0: variational_expectations, 1: predict_density (Fvar == NULL: logp) -- n = T rows, out [T];
+// MODE 2: predict_mean_and_var -- n = T C elements, the rule once per candidate class, out / out2 [T, C].
+// ------------------------------------------------------------------------------------------
+template <int MODE>
+__global__ __launch_bounds__(256) void k_mc_elem(Lik L, const float* __restrict__ Fmu, const float* __restrict__ Fvar,
+                                                 const float* __restrict__ Y, long long n, int C, long long row_div, long long row_mod,
+                                                 float* __restrict__ out, float* __restrict__ out2) {
+    const float eps = L.p0, eps1 = eps / (float)(C - 1);
+    float l0, l1;
+    mc_logs(L, C, l0, l1);
+    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < n; idx += (long long)gridDim.x * blockDim.x) {
+        float pa[10], pb[10], a;
+        if (MODE == 2) {
+            const long long t = idx / C;
+            const float p = mc_prob(Fmu + t * C, Fvar + t * C, C, (int)(idx - t * C), pa, pb, a);
+            const float P = fmaf(p, 1.f - eps - eps1, eps1);
+            out[idx] = P; out2[idx] = P - P * P;
+            continue;
+        }
+        const int y = mc_label(Y[(idx / row_div) % row_mod], C);
+        const float* mu = Fmu + idx * C;
+        if (MODE == 1 && !Fvar) {                       // logp: the FIRST maximum wins, as tf.argmax
+            int best = 0;
+            float fb = mu[0];
+            for (int c = 1; c < C; ++c) { const float f = mu[c]; if (f > fb) { fb = f; best = c; } }
+            out[idx] = best == y ? l1 : l0;
+            continue;
+        }
+        const float p = mc_prob(mu, Fvar + idx * C, C, y, pa, pb, a);
+        out[idx] = MODE == 0 ? mc_ve(p, l0, l1) : logf(fmaf(p, 1.f - eps - eps1, eps1));
+    }
+}
+
+template <int SEG>
+static int launch_mc_elbo(const LikReduceArgs& g, hipStream_t stream) {
+    constexpr int PPP = LIK_THREADS / SEG;
+    const long long blocks = (g.B + PPP - 1) / PPP;
+    hipLaunchKernelGGL(k_mc_elbo<SEG>, dim3((unsigned)blocks), dim3(LIK_THREADS), 0, stream, g);
+    return check_launch("k_mc_elbo");
+}
+
+int mc_launch_elbo(const LikReduceArgs& g, hipStream_t stream) {
+    if (g.K <= 4) return launch_mc_elbo<4>(g, stream);
+    if (g.K <= 8) return launch_mc_elbo<8>(g, stream);
+    if (g.K <= 16) return launch_mc_elbo<16>(g, stream);
+    if (g.K <= 32) return launch_mc_elbo<32>(g, stream);
+    return launch_mc_elbo<64>(g, stream);
+}
+
+int mc_launch_elbo_bwd(const LikBwdArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(k_mc_elbo_bwd, dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, stream, a);
+    return check_launch("k_mc_elbo_bwd");
+}
+
+int mc_launch_elem(const char* what, int mode, const Lik& L, const float* Fmu, const float* Fvar, const float* Y, long long T, int C,
+                   long long row_div, long long row_mod, float* out, float* out2, hipStream_t stream) {
+    const long long n = mode == 2 ? T * C : T;
+    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    if (mode == 0) hipLaunchKernelGGL(k_mc_elem<0>, dim3(blocks), dim3(256), 0, stream, L, Fmu, Fvar, Y, n, C, row_div, row_mod, out, out2);
+    else if (mode == 1) hipLaunchKernelGGL(k_mc_elem<1>, dim3(blocks), dim3(256), 0, stream, L, Fmu, Fvar, Y, n, C, row_div, row_mod, out, out2);
+    else hipLaunchKernelGGL(k_mc_elem<2>, dim3(blocks), dim3(256), 0, stream, L, Fmu, Fvar, Y, n, C, row_div, row_mod, out, out2);
+    return check_launch(what);
+}
+
+}  // namespace iwvi

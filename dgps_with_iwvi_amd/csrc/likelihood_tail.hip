@@ -2,26 +2,15 @@
 // likelihood's methods as elementwise callables.  The reference passes any GPflow-1.x likelihood to its models (models.py:66,105,134);
 // the non-conjugate ones -- Bernoulli with the probit link, Student-t -- integrate by GPflow's ndiagquad: Gauss-Hermite, 20 points.
 // The layer stack is untouched: these kernels read the final layer's moments (and the local regularisers) the layer launch left in HBM.
-#include "iwvi_common.h"
+#include "likelihood_common.h"   // the node tables GH_X / GH_W / GH_LOGW, Lik, the argument structs, lseg_*
 
 namespace iwvi {
-
-// numpy.polynomial.hermite.hermgauss(20): the rule is symmetric, x_(19-i) = -x_i with equal weights -- the ten positive nodes, their
-// weights w_i / sqrt(pi) and the logarithms of those (log-space sums).  Rounded to float32 the twenty weights sum to 1 - 5e-9.
-__device__ __constant__ const float GH_X[10] = {2.453407083e-01f, 7.374737285e-01f, 1.234076215e+00f, 1.738537712e+00f, 2.254974002e+00f,
-                                                2.788806058e+00f, 3.347854567e+00f, 3.944764040e+00f, 4.603682450e+00f, 5.387480890e+00f};
-__device__ __constant__ const float GH_W[10] = {2.607930634e-01f, 1.617393340e-01f, 6.150637206e-02f, 1.399783745e-02f, 1.830103131e-03f,
-                                                1.288262800e-04f, 4.402121090e-06f, 6.127490260e-08f, 2.482062362e-10f, 1.257800672e-13f};
-__device__ __constant__ const float GH_LOGW[10] = {-1.344028046e+00f, -1.821769289e+00f, -2.788614499e+00f, -4.268852429e+00f, -6.303382958e+00f,
-                                                   -8.957045728e+00f, -1.233342407e+01f, -1.660789550e+01f, -2.211676112e+01f, -2.970424151e+01f};
 
 // dE/dv = sum_i w_i g'(f_i) x_i / sqrt(2 v) is 0/0 at v = 0 (the forward clamps a float32 variance that undershot at exactly 0); its limit is
 // g''(mu) / 2.  The variance is floored here, for the value and the heads alike (the heads stay the gradient of the value that is
 // computed): sqrt(2 v) >= 1.4e-4, which moves E by g'' 5e-9 -- below float32 resolution -- and leaves the quotient finite.
 constexpr float LIK_V_FLOOR = 1e-8f;
 constexpr float LIK_JIT = 1e-3f;                  // GPflow's inv_probit jitter: p = Phi(f) (1 - 2 jit) + jit
-
-struct Lik { int type; float p0, p1, lgc; const float* p0_dev; };
 
 // g(f) = logp(f, y);  GRAD: also g'(f) and d g / d param[0]
 template <bool GRAD>
@@ -83,35 +72,9 @@ __device__ __forceinline__ float lik_quad(const Lik& L, float p0, float mu, floa
 // per sample walking its Dy outputs; float32 inside a sample, the log-sum-exp over K and the sum over the points in float64; the last
 // workgroup to arrive (agent-scope release / ticket / acquire) adds the points up in a fixed order.
 // ------------------------------------------------------------------------------------------
-constexpr int LIK_MAX_GLOB = 16;
-struct LikReduceArgs {
-    Lik lik;
-    const float* fmean; const float* fvar; const float* Y;
-    const float* kl[IWVI_MAX_KL]; int kl_dims[IWVI_MAX_KL]; int n_kl;
-    long long B, stride_b, stride_k; int K, Dy, K_total, mode_vi;
-    float* ms; float* logp;
-    double* elbo; unsigned long long* ticket; double scale;
-    const double* klg[LIK_MAX_GLOB]; int klg_n[LIK_MAX_GLOB]; int n_glob;
-};
-
-template <int SEG>
-__device__ __forceinline__ float lseg_max(float v) {
-#pragma unroll
-    for (int o = SEG / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-template <int SEG>
-__device__ __forceinline__ double lseg_sum(double v) {
-#pragma unroll
-    for (int o = SEG / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // A workgroup takes ONE pass of LIK_THREADS / SEG points (k_elbo takes 64 points in several passes: its per-sample work is a handful of
 // FMAs; here a sample costs 20 x Dy evaluations of erfc / log, and 64 points per workgroup left configs[2] -- B = 1024 -- on 16 of the
 // chip's 256 CUs: a Bernoulli evaluation took 101.6 us against 66.0 with the points spread -- profiles/likelihood_tail_time.json)
-constexpr int LIK_THREADS = 256;
-
 template <int SEG>
 __global__ __launch_bounds__(LIK_THREADS) void k_lik_elbo(LikReduceArgs g) {
     __shared__ double red[LIK_THREADS];
@@ -191,14 +154,6 @@ __global__ __launch_bounds__(LIK_THREADS) void k_lik_elbo(LikReduceArgs g) {
 // Heads of the bound's adjoint (csrc/backward.hip: k_elbo_bwd with the quadrature): one wave per data point, lanes over its K samples.
 // Pass 1: L_nk and the running (max, sum exp); pass 2: the weights and, per output, the heads.
 // ------------------------------------------------------------------------------------------
-struct LikBwdArgs {
-    Lik lik;
-    const float* fmean; const float* fvar; const float* Y; int Dy;
-    const float* kl[IWVI_MAX_KL]; int kl_dims[IWVI_MAX_KL]; int n_kl;
-    long long B; int K; double scale; int mode_vi;
-    const float* lse_global; int K_total;
-    float* w; float* d_mean; float* d_var; double* part;   // part[0..B) = lse - log K, part[B..2B) = d param[0] share
-};
 __global__ __launch_bounds__(256) void k_lik_elbo_bwd(LikBwdArgs a) {
     const int lane = threadIdx.x & 63;
     const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -338,6 +293,12 @@ __global__ __launch_bounds__(256) void k_lik_elem(Lik L, const float* __restrict
 }
 
 // descriptor -> kernel argument; what: the entry point's name for the error text; need_df2: predict_mean_and_var of the Student-t
+// IWVI_LIK_MULTICLASS: the moments have one column per class (Dy = param[1]) while Y has ONE column of labels
+static int mc_check_classes(const Lik& L, int Dy, const char* what) {
+    if (Dy != (int)L.p1) { set_error("%s: MultiClass with %d classes needs Dy = %d, got %d", what, (int)L.p1, (int)L.p1, Dy); return IWVI_ERR_ARG; }
+    return IWVI_OK;
+}
+
 static int take_lik(const iwvi_lik_desc* d, Lik& L, const char* what, bool need_df2 = false) {
     if (!d) { set_error("%s: null likelihood descriptor", what); return IWVI_ERR_ARG; }
     L.type = d->type; L.p0 = d->param[0]; L.p1 = d->param[1]; L.lgc = d->lgc; L.p0_dev = d->param0_dev;
@@ -353,6 +314,21 @@ static int take_lik(const iwvi_lik_desc* d, Lik& L, const char* what, bool need_
             if (!(d->param[1] > 0.f)) { set_error("%s: Student-t df must be positive", what); return IWVI_ERR_ARG; }
             if (need_df2 && !(d->param[1] > 2.f)) { set_error("%s: the Student-t variance needs df > 2 (got %g)", what, (double)d->param[1]); return IWVI_ERR_ARG; }
             return IWVI_OK;
+        case IWVI_LIK_MULTICLASS: {
+            // (type 3 was refused as unknown before this extension: the text says so to a caller whose 3 means something else)
+            const float eps = d->param[0], C = d->param[1];
+            if (!(eps > 0.f && eps < 1.f)) {
+                set_error("%s: MultiClass epsilon (param[0]) must lie in (0, 1), got %g -- a descriptor of an unknown likelihood type? "
+                          "Type %d is MultiClass: param[0] = epsilon, param[1] = the number of classes", what, (double)eps, d->type);
+                return IWVI_ERR_ARG;
+            }
+            if (!(C >= 2.f && C <= (float)IWVI_MAX_P) || C != (float)(int)C) {
+                set_error("%s: MultiClass needs an integral number of classes (param[1]) in 2..%d, got %g", what, IWVI_MAX_P, (double)C);
+                return IWVI_ERR_ARG;
+            }
+            L.p0_dev = nullptr;
+            return IWVI_OK;
+        }
         default:
             set_error("%s: unknown likelihood type %d", what, d->type); return IWVI_ERR_ARG;
     }
@@ -404,6 +380,10 @@ extern "C" int iwvi_lik_elbo_reduce(const iwvi_lik_desc* lik, const float* fmean
         }
         g.n_glob = n_glob;
     }
+    if (g.lik.type == IWVI_LIK_MULTICLASS) {
+        if ((rc = mc_check_classes(g.lik, Dy, "iwvi_lik_elbo_reduce")) != IWVI_OK) return rc;
+        return mc_launch_elbo(g, stream);
+    }
     if (K <= 4) return launch_lik_elbo<4>(g, stream);
     if (K <= 8) return launch_lik_elbo<8>(g, stream);
     if (K <= 16) return launch_lik_elbo<16>(g, stream);
@@ -439,7 +419,12 @@ extern "C" int iwvi_lik_elbo_backward(const iwvi_lik_desc* lik, const float* fme
     }
     a.B = B; a.K = K; a.scale = scale; a.mode_vi = mode_vi; a.lse_global = lse_global; a.K_total = K_total;
     a.w = out_w; a.d_mean = d_mean; a.d_var = d_var; a.part = ws;
-    hipLaunchKernelGGL(k_lik_elbo_bwd, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a);
+    if (a.lik.type == IWVI_LIK_MULTICLASS) {
+        if ((rc = mc_check_classes(a.lik, Dy, "iwvi_lik_elbo_backward")) != IWVI_OK) return rc;
+        if ((rc = mc_launch_elbo_bwd(a, st)) != IWVI_OK) return rc;
+    } else {
+        hipLaunchKernelGGL(k_lik_elbo_bwd, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a);
+    }
     hipLaunchKernelGGL(k_lik_finish, dim3(1), dim3(256), 0, st, fa);
     return check_launch("k_lik_elbo_bwd");
 }
@@ -451,8 +436,11 @@ static int lik_elementwise(const char* what, const iwvi_lik_desc* lik, const flo
     int rc;
     if ((rc = take_lik(lik, L, what, MODE == 2)) != IWVI_OK) return rc;
     if (T < 0 || Dy <= 0 || row_div <= 0 || row_mod <= 0) { set_error("%s: bad size", what); return IWVI_ERR_ARG; }
+    if (L.type == IWVI_LIK_MULTICLASS && (rc = mc_check_classes(L, Dy, what)) != IWVI_OK) return rc;
     if (T == 0) return IWVI_OK;
     if (!Fmu || !out || (MODE != 1 && !Fvar) || (MODE != 2 && !Y) || (MODE == 2 && !out2)) { set_error("%s: null pointer", what); return IWVI_ERR_ARG; }
+    if (L.type == IWVI_LIK_MULTICLASS)
+        return mc_launch_elem(what, MODE, L, Fmu, Fvar, Y, (long long)T, Dy, (long long)row_div, (long long)row_mod, out, out2, (hipStream_t)stream_);
     const long long n = (long long)T * Dy;
     const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
     hipLaunchKernelGGL(k_lik_elem<MODE>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, L, Fmu, Fvar, Y, n, Dy,
@@ -472,5 +460,13 @@ extern "C" int iwvi_lik_predict_density(const iwvi_lik_desc* lik, const float* F
 
 extern "C" int iwvi_lik_predict_mean_and_var(const iwvi_lik_desc* lik, const float* Fmu, const float* Fvar, int64_t n,
                                              float* out_mean, float* out_var, void* stream_) {
+    if (lik && lik->type == IWVI_LIK_MULTICLASS) {             // n = T C elements: rows of C = param[1] classes
+        Lik L{};
+        int rc;
+        if ((rc = take_lik(lik, L, "iwvi_lik_predict_mean_and_var")) != IWVI_OK) return rc;
+        const int C = (int)L.p1;
+        if (n < 0 || n % C != 0) { set_error("iwvi_lik_predict_mean_and_var: MultiClass takes n = T x %d elements, got %lld", C, (long long)n); return IWVI_ERR_ARG; }
+        return lik_elementwise<2>("iwvi_lik_predict_mean_and_var", lik, Fmu, Fvar, nullptr, n / C, C, 1, 1, out_mean, out_var, stream_);
+    }
     return lik_elementwise<2>("iwvi_lik_predict_mean_and_var", lik, Fmu, Fvar, nullptr, n, 1, 1, 1, out_mean, out_var, stream_);
 }

@@ -25,8 +25,10 @@ FIELDS = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_sp
           "group_segment_fixed_size", "max_flat_workgroup_size")
 
 # kernels whose instantiations must not touch scratch memory at all ...
-# (k_lik_*: csrc/likelihood_tail.hip -- twenty quadrature nodes unrolled per element: no scratch, and a VGPR ceiling each, MAX_VGPRS below)
-NO_SCRATCH = ("k_dgp_forward", "k_bw_chain", "k_sample_stats", "k_lik_elbo", "k_lik_elbo_bwd", "k_lik_elem", "k_lik_finish", "k_kde_grid")
+# (k_lik_*: csrc/likelihood_tail.hip -- twenty quadrature nodes unrolled per element: no scratch, and a VGPR ceiling each, MAX_VGPRS below;
+#  k_mc_*: csrc/likelihood_multiclass.hip -- twenty running products per sample, which must stay in registers)
+NO_SCRATCH = ("k_dgp_forward", "k_bw_chain", "k_sample_stats", "k_lik_elbo", "k_lik_elbo_bwd", "k_lik_elem", "k_lik_finish", "k_kde_grid",
+              "k_mc_elbo", "k_mc_elbo_bwd", "k_mc_elem")
 # ... except these (demangled-name substring -> bytes of scratch it is known to use; lower it when a kernel improves)
 ALLOWED_SCRATCH = {
     # round 6 (profiles/r06_kernel_resources.txt): every BIG variant (some layer with M > 128: configs[3] / [4]) and every float64-route
@@ -49,7 +51,8 @@ MAX_SPILLS = {
 # VGPR ceilings (kernel name before its template arguments -> most VGPRs any instantiation may use).  The likelihood-tail kernels are latency
 # chains of transcendental evaluations: 128 VGPRs keep four waves on a SIMD (512 per lane) to hide them.  Today: k_lik_elbo 80, k_lik_elbo_bwd 115,
 # k_lik_elem 19-65, k_lik_finish 12.
-MAX_VGPRS = {"k_lik_elbo": 128, "k_lik_elbo_bwd": 128, "k_lik_elem": 128, "k_lik_finish": 32}
+MAX_VGPRS = {"k_lik_elbo": 128, "k_lik_elbo_bwd": 128, "k_lik_elem": 128, "k_lik_finish": 32,
+             "k_mc_elbo": 128, "k_mc_elbo_bwd": 128, "k_mc_elem": 128}
 
 
 def csrc_hash():

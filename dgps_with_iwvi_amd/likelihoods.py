@@ -10,7 +10,11 @@ Gaussian tail and ``iwvi_lik_elbo_reduce`` / ``iwvi_lik_elbo_backward`` on the f
 
 Every likelihood answers ``lik_desc()`` (the ``iwvi_lik_desc`` of its current parameters), ``grad_name`` (the key of its trained scalar's
 gradient in ``backward.iw_elbo_and_gradients``, or None) and ``trained_scalar()`` (what a ``training.Trainer`` puts among its Adam
-scalars: (gradient name, value), or None)."""
+scalars: (gradient name, value), or None).
+
+``MultiClass`` (robust-max link; ``csrc/likelihood_multiclass.hip``) is the one likelihood whose targets are not as wide as the final
+layer: ``Y`` is ONE column of class labels 0 .. C-1 while the layer has C outputs.  Nothing equates the two widths directly: ``target_dim``
+/ ``output_dim`` below translate, and a likelihood says which it is by a ``num_classes`` attribute."""
 import math
 
 import torch
@@ -19,14 +23,26 @@ from . import _abi, settings
 from .kernels import DeviceScalarVariance
 
 
-def _moments(Fmu, Fvar, Y):
-    """(Fmu, Fvar or None, Y or None, T, Dy) as contiguous device tensors of Fmu's shape."""
+def target_dim(likelihood, Dy):
+    """Columns of Y for a final layer of ``Dy`` outputs: 1 for a likelihood over class labels (``num_classes``), else ``Dy``."""
+    return 1 if getattr(likelihood, "num_classes", None) is not None else Dy
+
+
+def output_dim(likelihood, y_dim):
+    """The other way round: outputs of the final layer (columns of its moments and of the heads) for targets of ``y_dim`` columns."""
+    C = getattr(likelihood, "num_classes", None)
+    return y_dim if C is None else C
+
+
+def _moments(Fmu, Fvar, Y, likelihood=None):
+    """(Fmu, Fvar or None, Y or None, T, Dy) as contiguous device tensors of Fmu's shape (Y: ``target_dim`` columns)."""
     Fmu = _abi.dev_tensor(torch.as_tensor(Fmu).contiguous(), "Fmu")
     if Fvar is not None:
         Fvar = _abi.dev_tensor(torch.as_tensor(Fvar, device=Fmu.device).expand_as(Fmu).contiguous(), "Fvar")
-    if Y is not None:
-        Y = _abi.dev_tensor(torch.as_tensor(Y, dtype=settings.float_type, device=Fmu.device).expand_as(Fmu).contiguous(), "Y")
     Dy = Fmu.shape[-1] if Fmu.dim() else 1
+    if Y is not None:
+        y_shape = tuple(Fmu.shape[:-1]) + (target_dim(likelihood, Dy),) if Fmu.dim() else ()
+        Y = _abi.dev_tensor(torch.as_tensor(Y, dtype=settings.float_type, device=Fmu.device).expand(y_shape).contiguous(), "Y")
     return Fmu, Fvar, Y, Fmu.numel() // max(Dy, 1), Dy
 
 
@@ -187,6 +203,97 @@ class StudentT(_QuadratureLikelihood, DeviceScalarVariance):
         if not self.df > 2.0:
             raise ValueError("StudentT.predict_mean_and_var: the variance needs df > 2 (df = %g)" % self.df)
         return super().predict_mean_and_var(Fmu, Fvar)
+
+
+class RobustMax:
+    """gpflow 1.x ``RobustMax(num_classes, epsilon=1e-3)``: the link of ``MultiClass`` -- 1 - epsilon on the largest latent, epsilon / (C - 1)
+    on each other."""
+
+    def __init__(self, num_classes, epsilon=1e-3):
+        if int(num_classes) != num_classes or not 2 <= int(num_classes) <= _abi.MAX_P:
+            raise ValueError("RobustMax: num_classes must be an integer in 2..%d, got %r" % (_abi.MAX_P, num_classes))
+        if not 0.0 < float(epsilon) < 1.0:
+            raise ValueError("RobustMax: epsilon must lie in (0, 1), got %r" % (epsilon,))
+        self.num_classes = int(num_classes)
+        self.epsilon = float(epsilon)
+
+
+class MultiClass:
+    """gpflow 1.x ``MultiClass(num_classes)`` with the ``RobustMax`` link (its default).  ``Y`` is ONE column of class labels 0 .. C-1; ``F``,
+    ``Fmu`` and ``Fvar`` have C columns.  With p = prob_is_largest(Y; Fmu, Fvar) by the 20-point rule over the label's own latent
+    (``csrc/likelihood_multiclass.hip``; clips and the 1e-4 cdf jitter as GPflow's) and eps_1 = epsilon / (C - 1):
+    ``variational_expectations`` = p log(1 - epsilon) + (1 - p) log eps_1 and ``predict_density`` = log(p (1 - epsilon) + (1 - p) eps_1), both
+    [..., 1]; ``logp`` = log(1 - epsilon) where argmax F == Y (the first maximum wins) else log eps_1, [..., 1]; ``predict_mean_and_var`` =
+    (P, P - P^2) [..., C], P_k the predictive probability of class k.  Nothing is trained."""
+
+    def __init__(self, num_classes, invlink=None, name=None):
+        if invlink is None:
+            invlink = RobustMax(num_classes)
+        if not isinstance(invlink, RobustMax):
+            shown = invlink if isinstance(invlink, str) else getattr(invlink, "__name__", type(invlink).__name__)
+            raise NotImplementedError("MultiClass(invlink=%r): only the robust-max link (GPflow's default, RobustMax) is implemented" % (shown,))
+        if invlink.num_classes != num_classes:
+            raise ValueError("MultiClass(%r) with a RobustMax over %d classes" % (num_classes, invlink.num_classes))
+        self.num_classes = invlink.num_classes
+        self.invlink = invlink
+        self.name = name
+
+    epsilon = property(lambda self: self.invlink.epsilon)
+
+    def lik_desc(self):
+        d = _abi.LikDesc()
+        d.type = _abi.LIK_MULTICLASS
+        d.param[0], d.param[1] = self.invlink.epsilon, float(self.num_classes)
+        return d
+
+    grad_name = None
+
+    def trained_scalar(self):
+        return None
+
+    def check_targets(self, Y):
+        """Y must be [N, 1] with integral values in [0, C): the kernels index the final layer's outputs with it.  The models call this once
+        on the host when they are built."""
+        import numpy as np
+        Yh = Y.detach().cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
+        if Yh.ndim != 2 or Yh.shape[1] != 1:
+            raise ValueError("MultiClass: targets must be one column of class labels [N, 1], got shape %s" % (tuple(Yh.shape),))
+        bad = ~((Yh >= 0) & (Yh < self.num_classes) & (Yh == np.floor(Yh)))
+        if bad.any():
+            raise ValueError("MultiClass: targets must be integers in [0, %d); %d of %d are not (first: %r)"
+                             % (self.num_classes, int(bad.sum()), Yh.size, Yh[bad].ravel()[0]))
+
+    def check_output_dim(self, Dy):
+        """The final layer must have one output per class (the models call this when they are built)."""
+        if Dy != self.num_classes:
+            raise ValueError("MultiClass(%d) needs a final layer with %d outputs, got %s" % (self.num_classes, self.num_classes, Dy))
+
+    def _rows(self, entry, Fmu, Fvar, Y):
+        Fmu, Fvar, Y, T, C = _moments(Fmu, Fvar, Y, self)
+        if C != self.num_classes:
+            raise ValueError("MultiClass(%d): the moments need %d columns, got %d" % (self.num_classes, self.num_classes, C))
+        out = torch.empty(*Fmu.shape[:-1], 1, dtype=Fmu.dtype, device=Fmu.device)
+        _abi.check(getattr(_abi.lib(), entry)(self.lik_desc(), _abi.ptr(Fmu), _abi.ptr(Fvar), _abi.ptr(Y), T, C, 1, max(T, 1), _abi.ptr(out),
+                                              _abi.stream_ptr()))
+        return out
+
+    def variational_expectations(self, Fmu, Fvar, Y):
+        return self._rows("iwvi_lik_var_exp", Fmu, Fvar, Y)
+
+    def logp(self, F, Y):
+        return self._rows("iwvi_lik_predict_density", F, None, Y)
+
+    def predict_density(self, Fmu, Fvar, Y):
+        return self._rows("iwvi_lik_predict_density", Fmu, Fvar, Y)
+
+    def predict_mean_and_var(self, Fmu, Fvar):
+        Fmu, Fvar, _, _, C = _moments(Fmu, Fvar, None)
+        if C != self.num_classes:
+            raise ValueError("MultiClass(%d): the moments need %d columns, got %d" % (self.num_classes, self.num_classes, C))
+        m, v = torch.empty_like(Fmu), torch.empty_like(Fmu)
+        _abi.check(_abi.lib().iwvi_lik_predict_mean_and_var(self.lik_desc(), _abi.ptr(Fmu), _abi.ptr(Fvar), Fmu.numel(), _abi.ptr(m), _abi.ptr(v),
+                                                            _abi.stream_ptr()))
+        return m, v
 
 
 def is_gaussian(likelihood):

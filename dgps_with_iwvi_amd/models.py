@@ -9,9 +9,10 @@ encoders of the latent-variable layers) and ``iwvi_dgp_forward``, whose workgrou
 tiling of X/Y over K, every layer, the Gaussian variational expectation and the local regularisers in LDS; the last workgroup
 to finish does the log-sum-exp over K, the scaled sum and subtracts the global KLs.
 
-A likelihood other than the Gaussian (``likelihoods.Bernoulli`` / ``StudentT``) takes THREE: the layer launch runs without its tail and leaves
+A likelihood other than the Gaussian (``likelihoods.Bernoulli`` / ``StudentT`` / ``MultiClass``) takes THREE: the layer launch runs without its tail and leaves
 the final layer's moments and the local regularisers, ``iwvi_lik_elbo_reduce`` does the rest (Gauss-Hermite variational expectations, the
-log-sum-exp, the bound).  For a Gaussian nothing differs from the two-launch form.
+log-sum-exp, the bound).  For a Gaussian nothing differs from the two-launch form.  ``MultiClass`` alone has targets narrower than the
+final layer -- Y is one column of class labels, the layer has one output per class --: ``likelihoods.target_dim`` / ``output_dim`` translate.
 
 Differences from the reference, all documented in DESIGN.md:
   * ``zs`` (one N(0,1) array or None per layer) injects the noise tf.random_normal draws in-graph; None
@@ -31,7 +32,7 @@ import torch
 
 from . import _abi, settings
 from .layers import GPLayer, LatentVariableLayer, RegularizerType
-from .likelihoods import is_gaussian
+from .likelihoods import is_gaussian, output_dim, target_dim
 from .temp_workaround import draw_normal, precompute_states
 
 
@@ -45,6 +46,9 @@ class DGP_VI:
         self.likelihood = likelihood
         if hasattr(likelihood, "check_targets"):                      # (a Bernoulli refuses labels other than 0 / 1 here, once, on the host)
             likelihood.check_targets(Y)
+        self.layers = list(layers)
+        if hasattr(likelihood, "check_output_dim"):                   # (MultiClass: one output of the final layer per class)
+            likelihood.check_output_dim(self._output_dim() if self.layers else None)
         self.num_data = X.shape[0]                                    # models.py:18
         self.num_samples = num_samples
         self._X_all, self._Y_all = _data(X), _data(Y)
@@ -55,7 +59,6 @@ class DGP_VI:
         self.X, self.Y = self._X_all, self._Y_all
         if minibatch_size is not None:
             self.next_minibatch()
-        self.layers = list(layers)
         self.name = name
         self.full_cov_over_samples = False
         # IW-ELBO only: evaluate a leading latent-variable layer inside the precompute launch (beside the
@@ -376,7 +379,7 @@ class DGP_VI:
                 want_ms=False, K_total=None, ms_out=None, elbo_out=None):
         """``iwvi_iw_elbo_reduce`` on explicit final-layer moments (the layer-by-layer path)."""
         dev = fmean.device
-        Dy = Y.shape[-1]
+        Dy = output_dim(self.likelihood, Y.shape[-1])                # (MultiClass: Y is one column of labels, the moments have C)
         fmean = _abi.dev_tensor(fmean.contiguous(), "final mean")
         fvar = _abi.dev_tensor(fvar.contiguous(), "final var")
         Y = _abi.dev_tensor(Y.contiguous(), "Y")
@@ -495,8 +498,9 @@ class DGP_VI:
         if X.dim() != 2 or X.shape[1] != self._input_dim():
             raise ValueError("X must be [N, %s], got %s" % (self._input_dim(), tuple(X.shape)))
         Dy = self._output_dim()
-        if Y.dim() != 2 or Y.shape[0] != X.shape[0] or Y.shape[1] != Dy:
-            raise ValueError("Y must be [%d, %s], got %s" % (X.shape[0], Dy, tuple(Y.shape)))
+        Yd = target_dim(self.likelihood, Dy)
+        if Y.dim() != 2 or Y.shape[0] != X.shape[0] or Y.shape[1] != Yd:
+            raise ValueError("Y must be [%d, %s], got %s" % (X.shape[0], Yd, tuple(Y.shape)))
         N = X.shape[0]
         if not is_gaussian(self.likelihood):
             # logsumexp_s sum_d predict_density(m_s, v_s, Y) - log S over predict_f_multisample's draws (layer-by-layer launches; the
@@ -509,7 +513,7 @@ class DGP_VI:
             for lo in range(0, N, bs):
                 hi = min(N, lo + bs)
                 m, v = self.predict_f_multisample(X[lo:hi], S, zs=[None if z is None else _data(z)[:, lo:hi] for z in zs])
-                lp = self.likelihood.predict_density(m, v, Y[None, lo:hi].expand_as(m)).sum(-1)
+                lp = self.likelihood.predict_density(m, v, Y[None, lo:hi].expand(m.shape[0], -1, -1)).sum(-1)
                 out[lo:hi] = torch.logsumexp(lp, 0) - float(np.log(S))
             return out
         zs = self._check_predict_noise("predict_log_density", S, N, zs)

@@ -663,8 +663,23 @@ int iwvi_kde_density_grid(const float* samples, int64_t sample_stride, int64_t p
  *   STUDENT_T  lgc - log s - 1/2 log(nu pi) - (nu + 1)/2 log1p(((Y - F)/s)^2 / nu)    param[0] = s (scale), param[1] = nu (df),
  *              lgc = lgamma((nu + 1)/2) - lgamma(nu/2), computed by the HOST (it depends on nu alone, and nu is not trained)
  * param0_dev: optional device scalar read instead of param[0] when the launch runs (a trained variance / scale), as lik_variance_dev.
+ *
+ *   MULTICLASS GPflow's MultiClass(C) with the RobustMax(C, epsilon) link (csrc/likelihood_multiclass.hip).  param[0] = epsilon in (0, 1),
+ *              param[1] = C, integral, 2 <= C <= IWVI_MAX_P; lgc and param0_dev are unused; nothing is trained.  It is the one type whose
+ *              targets are NOT as wide as the moments: Y is ONE column of class labels 0 .. C-1 stored as floats ([B, 1]; [rows, 1] for
+ *              the elementwise entries), the moments have one column per class, and every entry must be given Dy = C.
+ *                logp(F, Y) = log(1 - epsilon) if argmax_c F_c == Y (ties: the first maximum) else log(epsilon / (C - 1)).
+ *              Its expectation couples the C outputs of a sample, by the same 20-point rule over the label's own output:
+ *                X_i = mu_y + x_i sqrt(max(2 v_y, 1e-10)),  p = sum_i w_i prod_{c != y} [Phi((X_i - mu_c) / sqrt(max(v_c, 1e-10))) (1 - 2e-4) + 1e-4]
+ *              (clips and jitter are GPflow's and part of the definition), and
+ *                variational expectation = p log(1 - epsilon) + (1 - p) log(epsilon / (C - 1))               ONE value per (point, sample);
+ *                predict_density         = log(p (1 - epsilon) + (1 - p) epsilon / (C - 1));
+ *                predict_mean_and_var    = (P, P - P^2) [T, C],  P_k = that mixture with p evaluated for label k.
+ *              iwvi_lik_var_exp and iwvi_lik_predict_density therefore write out [T, 1], iwvi_lik_predict_mean_and_var takes n = T C (a
+ *              multiple of C) and writes [T, C] twice; iwvi_lik_elbo_backward writes d_mean, d_var [T, C] -- the gradient of the value
+ *              as computed: zero through an active clip -- and out_sums[1] = 0.  A label outside 0 .. C-1 is read as the nearest class.
  * ---------------------------------------------------------------------- */
-enum { IWVI_LIK_GAUSSIAN = 0, IWVI_LIK_BERNOULLI_PROBIT = 1, IWVI_LIK_STUDENT_T = 2 };
+enum { IWVI_LIK_GAUSSIAN = 0, IWVI_LIK_BERNOULLI_PROBIT = 1, IWVI_LIK_STUDENT_T = 2, IWVI_LIK_MULTICLASS = 3 };
 typedef struct iwvi_lik_desc {
     int32_t type;
     float param[2];
