@@ -118,12 +118,15 @@ extern "C" int iwvi_unwhiten(const void* state, int M, int R, const float* f, co
     const StateLayout s = state_layout(M, R);
     const double* Linv = reinterpret_cast<const double*>(static_cast<const char*>(state) + s.off_Linv);
     const int nt = (M + 15) / 16;
+    // column tiles: M columns of a q_sqrt batch, R columns of the f batch -- R may exceed M rounded up to 16 (a tile beyond a batch's
+    // columns returns at once)
+    const int ntf = (R + 15) / 16, ntx = nt > ntf ? nt : ntf;
     // batches 0..R-1 = q_sqrt rows (skipped when q_sqrt == NULL by launching only batch R)
     if (q_sqrt) {
-        hipLaunchKernelGGL(k_unwhiten, dim3(nt, nt, R + 1), dim3(256), 0, (hipStream_t)stream_, Linv, s.Mp, M, R, R,
+        hipLaunchKernelGGL(k_unwhiten, dim3(ntx, nt, R + 1), dim3(256), 0, (hipStream_t)stream_, Linv, s.Mp, M, R, R,
                            f, q_sqrt, f_w, q_sqrt_w);
     } else {
-        hipLaunchKernelGGL(k_unwhiten, dim3(nt, nt, 1), dim3(256), 0, (hipStream_t)stream_, Linv, s.Mp, M, R, 0,
+        hipLaunchKernelGGL(k_unwhiten, dim3(ntf, nt, 1), dim3(256), 0, (hipStream_t)stream_, Linv, s.Mp, M, R, 0,
                            f, (const float*)nullptr, f_w, (float*)nullptr);
     }
     return check_launch("iwvi_unwhiten");

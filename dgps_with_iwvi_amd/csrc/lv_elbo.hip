@@ -180,7 +180,7 @@ __global__ __launch_bounds__(1024) void k_elbo_final(FinalArgs g) {
 template <bool DEVCTR>
 __global__ void k_fill_normal(float* out, long long n, uint64_t seed, uint64_t offset, unsigned long long* state) {
     const long long nq = (n + 3) / 4;
-    if (DEVCTR) offset = state[0];            // every block reads the counter before any block can bump it
+    if (DEVCTR) offset = state[0];            // every block reads the counter before it takes its ticket, so before the last one bumps it
     for (long long q = blockIdx.x * (long long)blockDim.x + threadIdx.x; q < nq;
          q += (long long)gridDim.x * blockDim.x) {
         uint64_t ctr = offset + (uint64_t)q;
@@ -191,11 +191,15 @@ __global__ void k_fill_normal(float* out, long long n, uint64_t seed, uint64_t o
         for (int e = 0; e < 4; ++e) if (4 * q + e < n) out[4 * q + e] = v[e];
     }
     if (DEVCTR) {
-        // the last block of THIS launch to get here advances the counter for the next launch/replay
+        // the last block of THIS launch to get here (ticket gridDim.x - 1: every block has read the counter by then) re-zeroes the
+        // ticket, as k_elbo does with its own, and advances the counter for the next launch/replay -- whatever that launch's grid is
         __syncthreads();
         if (threadIdx.x == 0) {
-            unsigned long long t = atomicAdd(&state[1], 1ULL);
-            if ((t + 1) % gridDim.x == 0) atomicAdd(&state[0], (unsigned long long)nq);
+            const unsigned long long t = __hip_atomic_fetch_add(&state[1], 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (t == (unsigned long long)gridDim.x - 1) {
+                __hip_atomic_store(&state[1], 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_add(&state[0], (unsigned long long)nq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
         }
     }
 }

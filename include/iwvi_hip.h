@@ -730,9 +730,11 @@ int iwvi_unwhiten(const void* state, int M, int R, const float* f, const float* 
 
 /* counter-based N(0,1) fill (Philox4x32-10 + Box-Muller); stream documented in DESIGN.md */
 int iwvi_fill_normal(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream);
-/* same stream, but the counter lives on the device: state[0] = counter (read by the launch, then advanced
- * by ceil(n/4) by its last block), state[1] = internal ticket; zero both once. Lets a captured hipGraph
- * draw fresh noise on every replay. */
+/* same stream, but the counter lives on the device: state[0] = counter (read by every block of the launch, then advanced by
+ * ceil(n/4) by the last block to finish), state[1] = the launch's arrival ticket (every block adds to it once, the last one
+ * leaves it at 0); zero both once.  Launches of any sizes may share one state as long as they cannot overlap in time (one
+ * stream, or ordered by events): launch i then draws the stream from the sum of the earlier ceil(n/4).  Lets a captured
+ * hipGraph draw fresh noise on every replay. */
 int iwvi_fill_normal_dev(float* out, int64_t n, uint64_t seed, uint64_t* state, void* stream);
 
 /* Diagnostic / development route switches (NOT part of the drop-in surface, like iwvi_debug_set_stamps): the library itself never reads
