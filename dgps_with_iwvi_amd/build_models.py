@@ -117,35 +117,45 @@ def attach_train_op(model, ARGS):
 
 
 # ---- checkpoint / resume of the parameters (reference: gpflow Saver, run_conditional_density_estimation.py:95-125) ----
+def _likelihood_kind(lik):
+    """The checkpoint type of a likelihood: the name of the class of likelihoods.py it is or derives from (subclasses count)."""
+    from . import likelihoods
+    for kind in ("Poisson", "Exponential", "Gamma", "MultiClass", "StudentT", "Bernoulli"):
+        if isinstance(lik, getattr(likelihoods, kind)):
+            return kind
+    return "Gaussian"
+
+
 def likelihood_state(lik):
     """A Gaussian is stored as ever ('likelihood.variance'); any other likelihood under 'likelihood.type' (its class name) and
     'likelihood.params' (its parameters in the order of the constructor)."""
-    from .likelihoods import Bernoulli, MultiClass, StudentT
-    if isinstance(lik, MultiClass):
-        return {"likelihood.type": np.str_("MultiClass"), "likelihood.params": np.array([lik.num_classes, lik.epsilon], dtype=np.float64)}
-    if isinstance(lik, StudentT):
-        return {"likelihood.type": np.str_("StudentT"), "likelihood.params": np.array([lik.scale, lik.df], dtype=np.float64)}
-    if isinstance(lik, Bernoulli):
-        return {"likelihood.type": np.str_("Bernoulli"), "likelihood.params": np.zeros(0, dtype=np.float64)}
-    return {"likelihood.variance": np.float64(lik.variance)}
+    kind = _likelihood_kind(lik)
+    if kind == "Gaussian":
+        return {"likelihood.variance": np.float64(lik.variance)}
+    params = {"MultiClass": lambda: [lik.num_classes, lik.epsilon], "StudentT": lambda: [lik.scale, lik.df], "Bernoulli": lambda: [],
+              "Poisson": lambda: [lik.binsize], "Exponential": lambda: [], "Gamma": lambda: [lik.shape]}[kind]()
+    return {"likelihood.type": np.str_(kind), "likelihood.params": np.array(params, dtype=np.float64)}
 
 
 def load_likelihood_state(lik, state):
     """Into the model's own likelihood object (a trainer's device master is bound to it).  A file without 'likelihood.type' was written
     for a Gaussian -- every file from before the other likelihoods existed."""
-    from .likelihoods import Bernoulli, MultiClass, RobustMax, StudentT
+    from .likelihoods import RobustMax
     kind = str(state["likelihood.type"]) if "likelihood.type" in state else "Gaussian"
-    have = "MultiClass" if isinstance(lik, MultiClass) else "StudentT" if isinstance(lik, StudentT) else "Bernoulli" if isinstance(lik, Bernoulli) else "Gaussian"   # (as likelihood_state: subclasses count)
-    if kind != have:
+    if kind != _likelihood_kind(lik):
         raise ValueError("the checkpoint holds a %s likelihood, the model a %s" % (kind, type(lik).__name__))
+    params = [float(v) for v in np.asarray(state["likelihood.params"]).reshape(-1)] if kind != "Gaussian" else None
     if kind == "StudentT":
-        scale, df = (float(v) for v in np.asarray(state["likelihood.params"]).reshape(-1))
-        lik.scale, lik.df = scale, df
+        lik.scale, lik.df = params
     elif kind == "MultiClass":
-        C, eps = (float(v) for v in np.asarray(state["likelihood.params"]).reshape(-1))
+        C, eps = params
         if int(C) != lik.num_classes:
             raise ValueError("the checkpoint holds a MultiClass over %d classes, the model one over %d" % (int(C), lik.num_classes))
         lik.invlink = RobustMax(lik.num_classes, eps)
+    elif kind == "Poisson":
+        lik.binsize, = params
+    elif kind == "Gamma":
+        lik.shape, = params
     elif kind == "Gaussian":
         lik.variance = float(state["likelihood.variance"])
 

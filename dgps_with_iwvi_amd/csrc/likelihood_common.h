@@ -1,6 +1,7 @@
-// What csrc/likelihood_tail.hip and csrc/likelihood_multiclass.hip share: the Gauss-Hermite tables, the kernel-argument structs of the
-// iwvi_lik_* entry points and the segment reductions (moved here verbatim from likelihood_tail.hip), and the launchers of the
-// multi-class kernels, which the entry points of likelihood_tail.hip call for IWVI_LIK_MULTICLASS.
+// What csrc/likelihood_tail.hip, csrc/likelihood_multiclass.hip and csrc/likelihood_explink.hip share: the Gauss-Hermite tables, the
+// kernel-argument structs of the iwvi_lik_* entry points and the segment reductions (moved here verbatim from likelihood_tail.hip), and the
+// launchers of the multi-class and the exp-link kernels, which the entry points of likelihood_tail.hip call for IWVI_LIK_MULTICLASS and for
+// IWVI_LIK_POISSON / _EXPONENTIAL / _GAMMA.
 #pragma once
 #include "iwvi_common.h"
 
@@ -57,6 +58,14 @@ int mc_launch_elbo(const LikReduceArgs& g, hipStream_t stream);                 
 int mc_launch_elbo_bwd(const LikBwdArgs& a, hipStream_t stream);                  // k_mc_elbo_bwd (the caller launches k_lik_finish behind it)
 // mode 0: variational_expectations, 1: predict_density (Fvar == NULL: logp) -> out [T]; 2: predict_mean_and_var -> out, out2 [T, C]
 int mc_launch_elem(const char* what, int mode, const Lik& L, const float* Fmu, const float* Fvar, const float* Y, long long T, int C,
+                   long long row_div, long long row_mod, float* out, float* out2, hipStream_t stream);
+
+// ---- csrc/likelihood_explink.hip (IWVI_LIK_POISSON: lik.p0 = binsize; _EXPONENTIAL: no parameter; _GAMMA: lik.p0 / *lik.p0_dev = shape) ----
+inline bool xl_type(int type) { return type >= IWVI_LIK_POISSON && type <= IWVI_LIK_GAMMA; }
+int xl_launch_elbo(const LikReduceArgs& g, hipStream_t stream);                   // k_xl_elbo<SEG>
+int xl_launch_elbo_bwd(const LikBwdArgs& a, hipStream_t stream);                  // k_xl_elbo_bwd (the caller launches k_lik_finish behind it)
+// mode 0: variational_expectations, 1: predict_density (Fvar == NULL: logp), 2: predict_mean_and_var (out, out2) -- all [T, Dy]
+int xl_launch_elem(const char* what, int mode, const Lik& L, const float* Fmu, const float* Fvar, const float* Y, long long T, int Dy,
                    long long row_div, long long row_mod, float* out, float* out2, hipStream_t stream);
 
 }  // namespace iwvi

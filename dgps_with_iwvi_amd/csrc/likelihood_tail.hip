@@ -1,6 +1,8 @@
 // The bound's tail and the heads of its adjoint for likelihoods other than the Gaussian (include/iwvi_hip.h: iwvi_lik_*), and the
 // likelihood's methods as elementwise callables.  The reference passes any GPflow-1.x likelihood to its models (models.py:66,105,134);
 // the non-conjugate ones -- Bernoulli with the probit link, Student-t -- integrate by GPflow's ndiagquad: Gauss-Hermite, 20 points.
+// The entry points at the end of this file serve every type of include/iwvi_hip.h: Gaussian, Bernoulli and Student-t by the kernels here,
+// MultiClass by csrc/likelihood_multiclass.hip, Poisson / Exponential / Gamma (exp link, closed-form expectations) by csrc/likelihood_explink.hip.
 // The layer stack is untouched: these kernels read the final layer's moments (and the local regularisers) the layer launch left in HBM.
 #include "likelihood_common.h"   // the node tables GH_X / GH_W / GH_LOGW, Lik, the argument structs, lseg_*
 
@@ -329,6 +331,16 @@ static int take_lik(const iwvi_lik_desc* d, Lik& L, const char* what, bool need_
             L.p0_dev = nullptr;
             return IWVI_OK;
         }
+        case IWVI_LIK_POISSON:
+            if (!(d->param[0] > 0.f)) { set_error("%s: Poisson binsize (param[0]) must be positive, got %g", what, (double)d->param[0]); return IWVI_ERR_ARG; }
+            L.p0_dev = nullptr;                              // binsize is a fixed host parameter
+            return IWVI_OK;
+        case IWVI_LIK_EXPONENTIAL:
+            L.p0 = 1.f; L.p0_dev = nullptr;
+            return IWVI_OK;
+        case IWVI_LIK_GAMMA:
+            if (!(d->param[0] > 0.f)) { set_error("%s: Gamma shape (param[0]) must be positive, got %g", what, (double)d->param[0]); return IWVI_ERR_ARG; }
+            return IWVI_OK;
         default:
             set_error("%s: unknown likelihood type %d", what, d->type); return IWVI_ERR_ARG;
     }
@@ -384,6 +396,7 @@ extern "C" int iwvi_lik_elbo_reduce(const iwvi_lik_desc* lik, const float* fmean
         if ((rc = mc_check_classes(g.lik, Dy, "iwvi_lik_elbo_reduce")) != IWVI_OK) return rc;
         return mc_launch_elbo(g, stream);
     }
+    if (xl_type(g.lik.type)) return xl_launch_elbo(g, stream);
     if (K <= 4) return launch_lik_elbo<4>(g, stream);
     if (K <= 8) return launch_lik_elbo<8>(g, stream);
     if (K <= 16) return launch_lik_elbo<16>(g, stream);
@@ -422,6 +435,8 @@ extern "C" int iwvi_lik_elbo_backward(const iwvi_lik_desc* lik, const float* fme
     if (a.lik.type == IWVI_LIK_MULTICLASS) {
         if ((rc = mc_check_classes(a.lik, Dy, "iwvi_lik_elbo_backward")) != IWVI_OK) return rc;
         if ((rc = mc_launch_elbo_bwd(a, st)) != IWVI_OK) return rc;
+    } else if (xl_type(a.lik.type)) {
+        if ((rc = xl_launch_elbo_bwd(a, st)) != IWVI_OK) return rc;
     } else {
         hipLaunchKernelGGL(k_lik_elbo_bwd, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a);
     }
@@ -441,6 +456,8 @@ static int lik_elementwise(const char* what, const iwvi_lik_desc* lik, const flo
     if (!Fmu || !out || (MODE != 1 && !Fvar) || (MODE != 2 && !Y) || (MODE == 2 && !out2)) { set_error("%s: null pointer", what); return IWVI_ERR_ARG; }
     if (L.type == IWVI_LIK_MULTICLASS)
         return mc_launch_elem(what, MODE, L, Fmu, Fvar, Y, (long long)T, Dy, (long long)row_div, (long long)row_mod, out, out2, (hipStream_t)stream_);
+    if (xl_type(L.type))
+        return xl_launch_elem(what, MODE, L, Fmu, Fvar, Y, (long long)T, Dy, (long long)row_div, (long long)row_mod, out, out2, (hipStream_t)stream_);
     const long long n = (long long)T * Dy;
     const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
     hipLaunchKernelGGL(k_lik_elem<MODE>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, L, Fmu, Fvar, Y, n, Dy,

@@ -14,7 +14,10 @@ scalars: (gradient name, value), or None).
 
 ``MultiClass`` (robust-max link; ``csrc/likelihood_multiclass.hip``) is the one likelihood whose targets are not as wide as the final
 layer: ``Y`` is ONE column of class labels 0 .. C-1 while the layer has C outputs.  Nothing equates the two widths directly: ``target_dim``
-/ ``output_dim`` below translate, and a likelihood says which it is by a ``num_classes`` attribute."""
+/ ``output_dim`` below translate, and a likelihood says which it is by a ``num_classes`` attribute.
+
+``Poisson``, ``Exponential`` and ``Gamma`` (exp link, GPflow's default; ``csrc/likelihood_explink.hip``) have closed-form variational
+expectations -- one ``exp`` per element, no quadrature --; ``Gamma.shape`` is the one trained scalar (``grad_name`` 'lik_shape')."""
 import math
 
 import torch
@@ -294,6 +297,120 @@ class MultiClass:
         _abi.check(_abi.lib().iwvi_lik_predict_mean_and_var(self.lik_desc(), _abi.ptr(Fmu), _abi.ptr(Fvar), Fmu.numel(), _abi.ptr(m), _abi.ptr(v),
                                                             _abi.stream_ptr()))
         return m, v
+
+
+def _exp_link_only(cls_name, invlink):
+    if invlink is not None and getattr(invlink, "__name__", invlink) != "exp":
+        raise NotImplementedError("%s(invlink=%r): only the exp link (GPflow's default) is implemented"
+                                  % (cls_name, getattr(invlink, "__name__", invlink)))
+
+
+def _host_targets(Y):
+    import numpy as np
+    return Y.detach().cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
+
+
+def _refuse_targets(cls_name, what, Yh, bad):
+    if bad.any():
+        raise ValueError("%s: targets must be %s; %d of %d are not (first: %r)" % (cls_name, what, int(bad.sum()), Yh.size, Yh[bad].ravel()[0]))
+
+
+class Poisson(_QuadratureLikelihood):
+    """gpflow 1.x ``Poisson(invlink=exp, binsize=1.0)``: Y ~ Poisson(binsize exp(F)), logp = Y log(binsize exp(F)) - binsize exp(F) -
+    lgamma(Y + 1).  ``variational_expectations`` is the closed form Y mu - binsize exp(mu + v / 2) - lgamma(Y + 1) + Y log binsize;
+    ``predict_density`` / ``predict_mean_and_var`` are GPflow's defaults by the 20-point rule.  ``binsize`` is fixed; nothing is trained."""
+
+    def __init__(self, invlink=None, binsize=1.0, name=None):
+        _exp_link_only("Poisson", invlink)
+        if not float(binsize) > 0.0:
+            raise ValueError("Poisson: binsize must be positive, got %r" % (binsize,))
+        self.binsize = float(binsize)
+        self.name = name
+
+    def lik_desc(self):
+        d = _abi.LikDesc()
+        d.type = _abi.LIK_POISSON
+        d.param[0] = self.binsize
+        return d
+
+    grad_name = None
+
+    def trained_scalar(self):
+        return None
+
+    def check_targets(self, Y):
+        """Counts: finite integers >= 0 (the models call this once on the host when they are built)."""
+        import numpy as np
+        Yh = _host_targets(Y)
+        _refuse_targets("Poisson", "finite integers >= 0", Yh, ~(np.isfinite(Yh) & (Yh >= 0) & (Yh == np.floor(Yh))))
+
+
+class Exponential(_QuadratureLikelihood):
+    """gpflow 1.x ``Exponential(invlink=exp)``: Y ~ Exponential with scale exp(F), logp = -Y exp(-F) - F.  ``variational_expectations`` is the
+    closed form -Y exp(-mu + v / 2) - mu; ``predict_density`` / ``predict_mean_and_var`` are GPflow's defaults by the 20-point rule.
+    No parameter."""
+
+    def __init__(self, invlink=None, name=None):
+        _exp_link_only("Exponential", invlink)
+        self.name = name
+
+    def lik_desc(self):
+        d = _abi.LikDesc()
+        d.type = _abi.LIK_EXPONENTIAL
+        return d
+
+    grad_name = None
+
+    def trained_scalar(self):
+        return None
+
+    def check_targets(self, Y):
+        """Finite and >= 0 (the models call this once on the host when they are built)."""
+        import numpy as np
+        Yh = _host_targets(Y)
+        _refuse_targets("Exponential", "finite and >= 0", Yh, ~(np.isfinite(Yh) & (Yh >= 0)))
+
+
+class Gamma(_QuadratureLikelihood, DeviceScalarVariance):
+    """gpflow 1.x ``Gamma(invlink=exp, shape=1.0)``: Y ~ Gamma(shape, scale exp(F)), logp = -shape F - lgamma(shape) + (shape - 1) log Y -
+    Y exp(-F).  ``variational_expectations`` is the closed form with exp(-mu + v / 2) in place of exp(-F); ``predict_density`` /
+    ``predict_mean_and_var`` are GPflow's defaults by the 20-point rule.  ``shape`` is trainable (positive): lgamma and digamma of it are
+    evaluated on the device from the value a launch reads."""
+    # the one trained scalar: the lazily refreshed host copy / device master of DeviceScalarVariance, as StudentT.scale
+    shape = property(DeviceScalarVariance.host_value, DeviceScalarVariance.variance.fset)
+
+    def __init__(self, invlink=None, shape=1.0, name=None):
+        _exp_link_only("Gamma", invlink)
+        if not float(shape) > 0.0:
+            raise ValueError("Gamma: shape must be positive, got %r" % (shape,))
+        self.shape = float(shape)
+        self.name = name
+
+    @property
+    def variance(self):
+        raise AttributeError("Gamma has no 'variance': its parameter is 'shape'")
+
+    def lik_desc(self):
+        d = _abi.LikDesc()
+        d.type = _abi.LIK_GAMMA
+        d.param[0], d.param0_dev = self.desc_variance()
+        return d
+
+    grad_name = "lik_shape"
+
+    def trained_scalar(self):
+        return self.grad_name, self.shape
+
+    def check_targets(self, Y):
+        """Finite and > 0: log Y enters the density (the models call this once on the host when they are built)."""
+        import numpy as np
+        Yh = _host_targets(Y)
+        _refuse_targets("Gamma", "finite and > 0", Yh, ~(np.isfinite(Yh) & (Yh > 0)))
+
+
+def exp(x):
+    """GPflow's default link of ``Poisson`` / ``Exponential`` / ``Gamma`` on torch tensors (the name their ``invlink=...`` accepts)."""
+    return torch.exp(x)
 
 
 def is_gaussian(likelihood):

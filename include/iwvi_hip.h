@@ -678,8 +678,32 @@ int iwvi_kde_density_grid(const float* samples, int64_t sample_stride, int64_t p
  *              iwvi_lik_var_exp and iwvi_lik_predict_density therefore write out [T, 1], iwvi_lik_predict_mean_and_var takes n = T C (a
  *              multiple of C) and writes [T, C] twice; iwvi_lik_elbo_backward writes d_mean, d_var [T, C] -- the gradient of the value
  *              as computed: zero through an active clip -- and out_sums[1] = 0.  A label outside 0 .. C-1 is read as the nearest class.
+ *
+ *   POISSON, EXPONENTIAL, GAMMA   GPflow's Poisson(binsize), Exponential() and Gamma(shape) with their default exp link, lambda = exp(F)
+ *              (csrc/likelihood_explink.hip).  With that link the variational expectation is a CLOSED FORM, GPflow's own branch -- no
+ *              quadrature, one exp per element, no variance floor (nothing divides by sqrt(v)):
+ *                              logp(F, Y)                                          variational_expectations(mu, v, Y)
+ *                POISSON       Y log(b l) - b l - lgamma(Y + 1)                    Y mu - b exp(mu + v/2) - lgamma(Y + 1) + Y log b
+ *                EXPONENTIAL   -Y / l - log l                                      -Y exp(-mu + v/2) - mu
+ *                GAMMA         -a log l - lgamma(a) + (a - 1) log Y - Y / l        -a mu - lgamma(a) + (a - 1) log Y - Y exp(-mu + v/2)
+ *                conditional mean, variance:  POISSON b l, b l;  EXPONENTIAL l, l^2;  GAMMA a l, a l^2.
+ *              POISSON: param[0] = b = binsize > 0, a fixed host value (param0_dev is ignored).  EXPONENTIAL: no parameter.  GAMMA:
+ *              param[0] = a = shape > 0, param0_dev honoured (the one trained scalar); lgamma(a) and digamma(a) are evaluated on the
+ *              device, in float64, from the value the launch reads.  lgc is unused.  Heads (exact derivatives of the closed forms), with
+ *              e+ = exp(mu + v/2), e- = exp(-mu + v/2):
+ *                POISSON      dE/dmu = Y - b e+,   dE/dv = -b e+ / 2
+ *                EXPONENTIAL  dE/dmu = Y e- - 1,   dE/dv = -Y e- / 2
+ *                GAMMA        dE/dmu = Y e- - a,   dE/dv = -Y e- / 2,   dE/da = -mu - digamma(a) + log Y   (out_sums[1]; 0 for the other two)
+ *              iwvi_lik_predict_density and iwvi_lik_predict_mean_and_var are GPflow's base-class defaults by the 20-point rule above:
+ *                predict_density      = log sum_i exp(logp(f_i, Y) + log w_i)                          (Fvar == NULL: logp(Fmu, Y))
+ *                predict_mean_and_var = (E_y, E_y2 - E_y^2),  E_y = sum_i w_i mean(f_i),  E_y2 = sum_i w_i (var(f_i) + mean(f_i)^2);
+ *              the rule defines these, not exp(mu + v/2).  The terms of the targets alone (lgamma(Y + 1), Y log b, (a - 1) log Y - lgamma(a))
+ *              enter out_lse_ms[:, 0], so out_lse_ms[:, 0] + log out_lse_ms[:, 1] - log K is still the point's log p.  Targets: POISSON
+ *              integers >= 0, EXPONENTIAL >= 0, GAMMA > 0 (the caller's to check).  No clamp: where exp overflows float32 (|mu +- v/2| above
+ *              about 88) the formulas give +-inf or NaN, as GPflow's do in float64 at 709.
  * ---------------------------------------------------------------------- */
-enum { IWVI_LIK_GAUSSIAN = 0, IWVI_LIK_BERNOULLI_PROBIT = 1, IWVI_LIK_STUDENT_T = 2, IWVI_LIK_MULTICLASS = 3 };
+enum { IWVI_LIK_GAUSSIAN = 0, IWVI_LIK_BERNOULLI_PROBIT = 1, IWVI_LIK_STUDENT_T = 2, IWVI_LIK_MULTICLASS = 3,
+       IWVI_LIK_POISSON = 4, IWVI_LIK_EXPONENTIAL = 5, IWVI_LIK_GAMMA = 6 };
 typedef struct iwvi_lik_desc {
     int32_t type;
     float param[2];
