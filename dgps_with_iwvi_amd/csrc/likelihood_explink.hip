@@ -239,6 +239,45 @@ __global__ __launch_bounds__(256) void k_xl_elbo_bwd(LikBwdArgs a) {
 // Elementwise callables.  MODE 0: variational_expectations (the closed form); 1: predict_density (Fvar == NULL: logp); 2: predict_mean_and_var.
 // Modes 1 and 2 are the 20-point rule, f_i = mu +- a x_j with a = sqrt(2 v): the rule defines the result, not exp(mu + v / 2).
 // ------------------------------------------------------------------------------------------
+// predict_mean_and_var of one element (MODE 2 of k_xl_elem; k_xl_mix)
+__device__ __forceinline__ void xl_mean_var(const XlPar& P, float mu, float v, float& ey, float& ev) {
+    // M1 = sum_i w_i exp(f_i), M2 = sum_i w_i exp(2 f_i);  E_y = sum w mean(f_i), E_y2 = sum w (var(f_i) + mean(f_i)^2), var = E_y2 - E_y^2
+    const float a = sqrtf(2.f * fmaxf(v, 0.f));
+    float m1 = 0.f, m2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < 10; ++j) {
+        const float xa = a * GH_X[j];
+        const float ea = expf(mu + xa), eb = expf(mu - xa);
+        m1 = fmaf(GH_W[j], ea + eb, m1);
+        m2 = fmaf(GH_W[j], fmaf(ea, ea, eb * eb), m2);
+    }
+    float ey2;
+    if (P.type == IWVI_LIK_POISSON) { ey = P.beta * m1; ey2 = fmaf(P.beta * P.beta, m2, ey); }
+    else if (P.type == IWVI_LIK_EXPONENTIAL) { ey = m1; ey2 = 2.f * m2; }
+    else { const float sh = -P.cmu; ey = sh * m1; ey2 = fmaf(sh, sh, sh) * m2; }
+    ev = fmaf(-ey, ey, ey2);
+}
+
+// predict_density of one element WITHOUT c0(y) (MODE 1 of k_xl_elem with a variance, which adds c0; k_xl_mix, which adds a point's c0 once):
+// log sum_i exp(g(f_i) + log w_i), the largest term first, then the sum (g is evaluated twice; nothing is kept in scratch)
+__device__ __forceinline__ float xl_density(const XlPar& P, float mu, float v, float y) {
+    float e;
+    const float a = sqrtf(2.f * fmaxf(v, 0.f));
+    float mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 10; ++j) {
+        const float xa = a * GH_X[j];
+        mx = fmaxf(mx, GH_LOGW[j] + fmaxf(xl_g(P, y, mu + xa, 0.f, e), xl_g(P, y, mu - xa, 0.f, e)));
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 10; ++j) {
+        const float xa = a * GH_X[j];
+        s += expf(GH_LOGW[j] + xl_g(P, y, mu + xa, 0.f, e) - mx) + expf(GH_LOGW[j] + xl_g(P, y, mu - xa, 0.f, e) - mx);
+    }
+    return mx + logf(s);
+}
+
 template <int MODE>
 __global__ __launch_bounds__(256) void k_xl_elem(Lik L, const float* __restrict__ Fmu, const float* __restrict__ Fvar,
                                                  const float* __restrict__ Y, long long n, int Dy, long long row_div, long long row_mod,
@@ -248,21 +287,9 @@ __global__ __launch_bounds__(256) void k_xl_elem(Lik L, const float* __restrict_
         const float mu = Fmu[idx];
         float e;
         if (MODE == 2) {
-            // M1 = sum_i w_i exp(f_i), M2 = sum_i w_i exp(2 f_i);  E_y = sum w mean(f_i), E_y2 = sum w (var(f_i) + mean(f_i)^2), var = E_y2 - E_y^2
-            const float a = sqrtf(2.f * fmaxf(Fvar[idx], 0.f));
-            float m1 = 0.f, m2 = 0.f;
-#pragma unroll
-            for (int j = 0; j < 10; ++j) {
-                const float xa = a * GH_X[j];
-                const float ea = expf(mu + xa), eb = expf(mu - xa);
-                m1 = fmaf(GH_W[j], ea + eb, m1);
-                m2 = fmaf(GH_W[j], fmaf(ea, ea, eb * eb), m2);
-            }
-            float ey, ey2;
-            if (P.type == IWVI_LIK_POISSON) { ey = P.beta * m1; ey2 = fmaf(P.beta * P.beta, m2, ey); }
-            else if (P.type == IWVI_LIK_EXPONENTIAL) { ey = m1; ey2 = 2.f * m2; }
-            else { const float sh = -P.cmu; ey = sh * m1; ey2 = fmaf(sh, sh, sh) * m2; }
-            out[idx] = ey; out2[idx] = fmaf(-ey, ey, ey2);
+            float ey, ev;
+            xl_mean_var(P, mu, Fvar[idx], ey, ev);
+            out[idx] = ey; out2[idx] = ev;
             continue;
         }
         const long long t = idx / Dy;
@@ -272,22 +299,26 @@ __global__ __launch_bounds__(256) void k_xl_elem(Lik L, const float* __restrict_
         const float c0 = xl_c0(P, y, logy);
         if (MODE == 0) { out[idx] = xl_g(P, y, mu, 0.5f * Fvar[idx], e) + c0; continue; }
         if (!Fvar) { out[idx] = xl_g(P, y, mu, 0.f, e) + c0; continue; }
-        // log sum_i exp(g(f_i) + log w_i): the largest term first, then the sum (g is evaluated twice; nothing is kept in scratch)
-        const float a = sqrtf(2.f * fmaxf(Fvar[idx], 0.f));
-        float mx = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < 10; ++j) {
-            const float xa = a * GH_X[j];
-            mx = fmaxf(mx, GH_LOGW[j] + fmaxf(xl_g(P, y, mu + xa, 0.f, e), xl_g(P, y, mu - xa, 0.f, e)));
-        }
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < 10; ++j) {
-            const float xa = a * GH_X[j];
-            s += expf(GH_LOGW[j] + xl_g(P, y, mu + xa, 0.f, e) - mx) + expf(GH_LOGW[j] + xl_g(P, y, mu - xa, 0.f, e) - mx);
-        }
-        out[idx] = mx + logf(s) + c0;
+        out[idx] = xl_density(P, mu, Fvar[idx], y) + c0;
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// iwvi_lik_predict_mixture for the three exp-link types: the point loop of likelihood_common.h over the two functions above; a point's
+// sum_d c0(y_d) is formed once and added outside the log-sum-exp over its draws, as k_xl_elbo does.
+// ------------------------------------------------------------------------------------------
+struct XlMixOps {
+    static constexpr bool HAS_CONST = true;
+    const XlPar& P;
+    __device__ __forceinline__ float density(float mu, float v, float y) const { return xl_density(P, mu, v, y); }
+    __device__ __forceinline__ float target_const(float y) const { float ly; return xl_c0(P, y, ly); }
+    __device__ __forceinline__ void mean_var(float mu, float v, float& ey, float& ev) const { xl_mean_var(P, mu, v, ey, ev); }
+};
+template <int SEG>
+__global__ __launch_bounds__(LIK_THREADS) void k_xl_mix(LikMixArgs g) {
+    const XlPar P = xl_par<true, false>(g.lik);
+    const XlMixOps ops{P};
+    mix_points<SEG>(g, ops);
 }
 
 template <int SEG>
@@ -305,6 +336,20 @@ int xl_launch_elbo(const LikReduceArgs& g, hipStream_t stream) {
     if (g.K <= 16) return launch_xl_elbo<16>(g, stream);
     if (g.K <= 32) return launch_xl_elbo<32>(g, stream);
     return launch_xl_elbo<64>(g, stream);
+}
+
+template <int SEG>
+static int launch_xl_mix(const LikMixArgs& g, hipStream_t stream) {
+    hipLaunchKernelGGL(k_xl_mix<SEG>, dim3(mix_blocks(g.N, SEG)), dim3(LIK_THREADS), 0, stream, g);
+    return check_launch("k_xl_mix");
+}
+
+int xl_launch_mix(const LikMixArgs& g, hipStream_t stream) {
+    if (g.S <= 4) return launch_xl_mix<4>(g, stream);
+    if (g.S <= 8) return launch_xl_mix<8>(g, stream);
+    if (g.S <= 16) return launch_xl_mix<16>(g, stream);
+    if (g.S <= 32) return launch_xl_mix<32>(g, stream);
+    return launch_xl_mix<64>(g, stream);
 }
 
 int xl_launch_elbo_bwd(const LikBwdArgs& a, hipStream_t stream) {

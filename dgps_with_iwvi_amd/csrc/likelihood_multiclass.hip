@@ -224,6 +224,13 @@ __global__ __launch_bounds__(256) void k_mc_elbo_bwd(LikBwdArgs a) {
 // Elementwise callables.  MODE 0: variational_expectations, 1: predict_density (Fvar == NULL: logp) -- n = T rows, out [T];
 // MODE 2: predict_mean_and_var -- n = T C elements, the rule once per candidate class, out / out2 [T, C].
 // ------------------------------------------------------------------------------------------
+// P_k, the predictive probability of class k of one sample (MODE 2 of k_mc_elem; its logarithm at k = the label is MODE 1; k_mc_mix)
+__device__ __forceinline__ float mc_class_prob(const float* __restrict__ mu, const float* __restrict__ var, int C, int k, float eps, float eps1) {
+    float pa[10], pb[10], a;
+    const float p = mc_prob(mu, var, C, k, pa, pb, a);
+    return fmaf(p, 1.f - eps - eps1, eps1);
+}
+
 template <int MODE>
 __global__ __launch_bounds__(256) void k_mc_elem(Lik L, const float* __restrict__ Fmu, const float* __restrict__ Fvar,
                                                  const float* __restrict__ Y, long long n, int C, long long row_div, long long row_mod,
@@ -235,8 +242,7 @@ __global__ __launch_bounds__(256) void k_mc_elem(Lik L, const float* __restrict_
         float pa[10], pb[10], a;
         if (MODE == 2) {
             const long long t = idx / C;
-            const float p = mc_prob(Fmu + t * C, Fvar + t * C, C, (int)(idx - t * C), pa, pb, a);
-            const float P = fmaf(p, 1.f - eps - eps1, eps1);
+            const float P = mc_class_prob(Fmu + t * C, Fvar + t * C, C, (int)(idx - t * C), eps, eps1);
             out[idx] = P; out2[idx] = P - P * P;
             continue;
         }
@@ -249,8 +255,60 @@ __global__ __launch_bounds__(256) void k_mc_elem(Lik L, const float* __restrict_
             out[idx] = best == y ? l1 : l0;
             continue;
         }
-        const float p = mc_prob(mu, Fvar + idx * C, C, y, pa, pb, a);
-        out[idx] = MODE == 0 ? mc_ve(p, l0, l1) : logf(fmaf(p, 1.f - eps - eps1, eps1));
+        if (MODE == 1) { out[idx] = logf(mc_class_prob(mu, Fvar + idx * C, C, y, eps, eps1)); continue; }
+        out[idx] = mc_ve(mc_prob(mu, Fvar + idx * C, C, y, pa, pb, a), l0, l1);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// iwvi_lik_predict_mixture: k_mc_elbo's layout (SEG lanes per point striding over its S draws, LIK_THREADS / SEG points per pass, grid-strided
+// beyond MIX_MAX_BLOCKS workgroups).  The CLASSES are the outer loop: class k of every draw costs one rule, its P_k enters the two float64
+// moment sums of that class, and at k = the point's label log P_k IS the draw's density -- the C probabilities of a draw are evaluated once.
+// With the density alone asked for, only k = the label runs.  The log-sum-exp step is taken by every segment in every class pass (the cross-lane
+// reductions stay outside divergent control flow); for a segment whose label is another class it is the exact no-op lseg_lse_step documents.
+// ------------------------------------------------------------------------------------------
+template <int SEG>
+__global__ __launch_bounds__(LIK_THREADS) void k_mc_mix(LikMixArgs g) {
+    const int tid = threadIdx.x, sl = tid % SEG, sg = tid / SEG;
+    constexpr int PPP = LIK_THREADS / SEG;
+    const int S = g.S, C = g.Dy;
+    const float eps = g.lik.p0, eps1 = eps / (float)(C - 1);
+    const int passes = g.mean ? C : 1;
+    for (long long b0 = (long long)blockIdx.x * PPP; b0 < g.N; b0 += (long long)gridDim.x * PPP) {   // (uniform in the workgroup)
+        const long long b = b0 + sg;
+        const bool live = b < g.N;                    // uniform within a segment
+        const int y = (live && g.logp) ? mc_label(g.Y[b], C) : 0;
+        float m = -INFINITY;
+        double ssum = 0.0;
+        for (int ci = 0; ci < passes; ++ci) {
+            const int k = g.mean ? ci : y;
+            const bool hit = g.logp && k == y;
+            double se = 0.0, se2 = 0.0;                  // sum_s P_k, sum_s ((P_k - P_k^2) + P_k^2)
+            for (int s0 = 0; s0 < S; s0 += SEG) {
+                const int s = s0 + sl;
+                const bool on = live && s < S;
+                float L = -INFINITY;
+                if (on) {
+                    const long long t = (b * g.stride_n + s * g.stride_s) * C;
+                    const float P = mc_class_prob(g.fmean + t, g.fvar + t, C, k, eps, eps1);
+                    const float V = P - P * P;
+                    se += (double)P;
+                    se2 += (double)V + (double)P * (double)P;
+                    if (hit) L = logf(P);
+                }
+                if (g.logp) lseg_lse_step<SEG>(L, on && hit, m, ssum);
+            }
+            if (g.mean) {
+                se = lseg_sum<SEG>(se);
+                se2 = lseg_sum<SEG>(se2);
+                if (live && sl == 0) {
+                    const double mn = se / (double)S;
+                    g.mean[b * C + k] = (float)mn;
+                    g.var[b * C + k] = (float)(se2 / (double)S - mn * mn);
+                }
+            }
+        }
+        if (g.logp && live && sl == 0) g.logp[b] = (float)((double)m + log(ssum) - log((double)S));
     }
 }
 
@@ -268,6 +326,20 @@ int mc_launch_elbo(const LikReduceArgs& g, hipStream_t stream) {
     if (g.K <= 16) return launch_mc_elbo<16>(g, stream);
     if (g.K <= 32) return launch_mc_elbo<32>(g, stream);
     return launch_mc_elbo<64>(g, stream);
+}
+
+template <int SEG>
+static int launch_mc_mix(const LikMixArgs& g, hipStream_t stream) {
+    hipLaunchKernelGGL(k_mc_mix<SEG>, dim3(mix_blocks(g.N, SEG)), dim3(LIK_THREADS), 0, stream, g);
+    return check_launch("k_mc_mix");
+}
+
+int mc_launch_mix(const LikMixArgs& g, hipStream_t stream) {
+    if (g.S <= 4) return launch_mc_mix<4>(g, stream);
+    if (g.S <= 8) return launch_mc_mix<8>(g, stream);
+    if (g.S <= 16) return launch_mc_mix<16>(g, stream);
+    if (g.S <= 32) return launch_mc_mix<32>(g, stream);
+    return launch_mc_mix<64>(g, stream);
 }
 
 int mc_launch_elbo_bwd(const LikBwdArgs& a, hipStream_t stream) {

@@ -233,6 +233,55 @@ __global__ __launch_bounds__(256) void k_lik_finish(LikFinishArgs a) {
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ float inv_probit(float x) { return 0.5f * erfcf(-x * 0.70710678118654752f) * (1.f - 2.f * LIK_JIT) + LIK_JIT; }
 
+// predict_mean_and_var of one element (MODE 2 of k_lik_elem, and the moments of k_lik_mix)
+__device__ __forceinline__ void lik_mean_var(const Lik& L, float p0, float mu, float v, float& em, float& ev) {
+    if (L.type == IWVI_LIK_BERNOULLI_PROBIT) {
+        const float p = inv_probit(mu * rsqrtf(1.f + v));
+        em = p; ev = p - p * p;
+    } else if (L.type == IWVI_LIK_STUDENT_T) {
+        // m = E[F] = mu (the nodes are symmetric); E[s^2 nu / (nu - 2) + F^2] - m^2 by the rule in its centred form: f_i^2 - mu^2 =
+        // (a x_i)(2 mu + a x_i), and the node pair +-x_i adds 2 (a x_i)^2 -- mu^2 never enters, so nothing cancels
+        const float a = sqrtf(2.f * fmaxf(v, 0.f)), c = p0 * p0 * L.p1 / (L.p1 - 2.f);
+        float m2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < 10; ++j) {
+            const float xa = a * GH_X[j];
+            m2 = fmaf(GH_W[j], 2.f * xa * xa, m2);
+        }
+        em = mu; ev = c + m2;
+    } else {
+        em = mu; ev = v + p0;
+    }
+}
+
+// predict_density of one element (MODE 1 of k_lik_elem with a variance, and the densities of k_lik_mix)
+__device__ __forceinline__ float lik_density(const Lik& L, float p0, float mu, float v, float y) {
+    float d0, d1;
+    if (L.type == IWVI_LIK_BERNOULLI_PROBIT) {
+        const float x = mu * rsqrtf(1.f + v);
+        return logf(y == 1.f ? inv_probit(x) : 0.5f * erfcf(x * 0.70710678118654752f) * (1.f - 2.f * LIK_JIT) + LIK_JIT);
+    }
+    if (L.type == IWVI_LIK_STUDENT_T) {
+        // log sum_i exp(g(f_i) + log w_i): the largest term first, then the sum (g is evaluated twice; nothing is kept in scratch)
+        const float a = sqrtf(2.f * fmaxf(v, 0.f));
+        float mx = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < 10; ++j) {
+            const float xa = a * GH_X[j];
+            mx = fmaxf(mx, GH_LOGW[j] + fmaxf(lik_eval<false>(L, p0, mu + xa, y, d0, d1), lik_eval<false>(L, p0, mu - xa, y, d0, d1)));
+        }
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < 10; ++j) {
+            const float xa = a * GH_X[j];
+            s += __expf(GH_LOGW[j] + lik_eval<false>(L, p0, mu + xa, y, d0, d1) - mx) + __expf(GH_LOGW[j] + lik_eval<false>(L, p0, mu - xa, y, d0, d1) - mx);
+        }
+        return mx + logf(s);
+    }
+    const float e = y - mu, s = v + p0;
+    return -0.5f * logf(6.283185307179586f * s) - 0.5f * e * e / s;
+}
+
 template <int MODE>
 __global__ __launch_bounds__(256) void k_lik_elem(Lik L, const float* __restrict__ Fmu, const float* __restrict__ Fvar,
                                                   const float* __restrict__ Y, long long n, int Dy, long long row_div, long long row_mod,
@@ -242,24 +291,9 @@ __global__ __launch_bounds__(256) void k_lik_elem(Lik L, const float* __restrict
         const float mu = Fmu[idx];
         float d0, d1, d2;
         if (MODE == 2) {
-            const float v = Fvar[idx];
-            if (L.type == IWVI_LIK_BERNOULLI_PROBIT) {
-                const float p = inv_probit(mu * rsqrtf(1.f + v));
-                out[idx] = p; out2[idx] = p - p * p;
-            } else if (L.type == IWVI_LIK_STUDENT_T) {
-                // m = E[F] = mu (the nodes are symmetric); E[s^2 nu / (nu - 2) + F^2] - m^2 by the rule in its centred form: f_i^2 - mu^2 =
-                // (a x_i)(2 mu + a x_i), and the node pair +-x_i adds 2 (a x_i)^2 -- mu^2 never enters, so nothing cancels
-                const float a = sqrtf(2.f * fmaxf(v, 0.f)), c = p0 * p0 * L.p1 / (L.p1 - 2.f);
-                float m2 = 0.f;
-#pragma unroll
-                for (int j = 0; j < 10; ++j) {
-                    const float xa = a * GH_X[j];
-                    m2 = fmaf(GH_W[j], 2.f * xa * xa, m2);
-                }
-                out[idx] = mu; out2[idx] = c + m2;
-            } else {
-                out[idx] = mu; out2[idx] = v + p0;
-            }
+            float em, ev;
+            lik_mean_var(L, p0, mu, Fvar[idx], em, ev);
+            out[idx] = em; out2[idx] = ev;
             continue;
         }
         const long long t = idx / Dy;
@@ -267,31 +301,24 @@ __global__ __launch_bounds__(256) void k_lik_elem(Lik L, const float* __restrict
         const float y = Y[((t / row_div) % row_mod) * Dy + d];
         if (MODE == 0) { out[idx] = lik_quad<false>(L, p0, mu, Fvar[idx], y, d0, d1, d2); continue; }
         if (!Fvar) { out[idx] = lik_eval<false>(L, p0, mu, y, d0, d1); continue; }
-        const float v = Fvar[idx];
-        if (L.type == IWVI_LIK_BERNOULLI_PROBIT) {
-            const float x = mu * rsqrtf(1.f + v);
-            out[idx] = logf(y == 1.f ? inv_probit(x) : 0.5f * erfcf(x * 0.70710678118654752f) * (1.f - 2.f * LIK_JIT) + LIK_JIT);
-        } else if (L.type == IWVI_LIK_STUDENT_T) {
-            // log sum_i exp(g(f_i) + log w_i): the largest term first, then the sum (g is evaluated twice; nothing is kept in scratch)
-            const float a = sqrtf(2.f * fmaxf(v, 0.f));
-            float mx = -INFINITY;
-#pragma unroll
-            for (int j = 0; j < 10; ++j) {
-                const float xa = a * GH_X[j];
-                mx = fmaxf(mx, GH_LOGW[j] + fmaxf(lik_eval<false>(L, p0, mu + xa, y, d0, d1), lik_eval<false>(L, p0, mu - xa, y, d0, d1)));
-            }
-            float s = 0.f;
-#pragma unroll
-            for (int j = 0; j < 10; ++j) {
-                const float xa = a * GH_X[j];
-                s += __expf(GH_LOGW[j] + lik_eval<false>(L, p0, mu + xa, y, d0, d1) - mx) + __expf(GH_LOGW[j] + lik_eval<false>(L, p0, mu - xa, y, d0, d1) - mx);
-            }
-            out[idx] = mx + logf(s);
-        } else {
-            const float e = y - mu, s = v + p0;
-            out[idx] = -0.5f * logf(6.283185307179586f * s) - 0.5f * e * e / s;
-        }
+        out[idx] = lik_density(L, p0, mu, Fvar[idx], y);
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// iwvi_lik_predict_mixture for the Gaussian, the Bernoulli and the Student-t: the point loop of likelihood_common.h over the two functions above.
+// ------------------------------------------------------------------------------------------
+struct LikMixOps {
+    static constexpr bool HAS_CONST = false;
+    const Lik& L; float p0;
+    __device__ __forceinline__ float density(float mu, float v, float y) const { return lik_density(L, p0, mu, v, y); }
+    __device__ __forceinline__ float target_const(float) const { return 0.f; }
+    __device__ __forceinline__ void mean_var(float mu, float v, float& em, float& ev) const { lik_mean_var(L, p0, mu, v, em, ev); }
+};
+template <int SEG>
+__global__ __launch_bounds__(LIK_THREADS) void k_lik_mix(LikMixArgs g) {
+    const LikMixOps ops{g.lik, g.lik.p0_dev ? *g.lik.p0_dev : g.lik.p0};
+    mix_points<SEG>(g, ops);
 }
 
 // descriptor -> kernel argument; what: the entry point's name for the error text; need_df2: predict_mean_and_var of the Student-t
@@ -352,6 +379,12 @@ static int launch_lik_elbo(const LikReduceArgs& g, hipStream_t stream) {
     const long long blocks = (g.B + PPP - 1) / PPP;
     hipLaunchKernelGGL(k_lik_elbo<SEG>, dim3((unsigned)blocks), dim3(LIK_THREADS), 0, stream, g);
     return check_launch("k_lik_elbo");
+}
+
+template <int SEG>
+static int launch_lik_mix(const LikMixArgs& g, hipStream_t stream) {
+    hipLaunchKernelGGL(k_lik_mix<SEG>, dim3(mix_blocks(g.N, SEG)), dim3(LIK_THREADS), 0, stream, g);
+    return check_launch("k_lik_mix");
 }
 
 }  // namespace iwvi
@@ -486,4 +519,34 @@ extern "C" int iwvi_lik_predict_mean_and_var(const iwvi_lik_desc* lik, const flo
         return lik_elementwise<2>("iwvi_lik_predict_mean_and_var", lik, Fmu, Fvar, nullptr, n / C, C, 1, 1, out_mean, out_var, stream_);
     }
     return lik_elementwise<2>("iwvi_lik_predict_mean_and_var", lik, Fmu, Fvar, nullptr, n, 1, 1, 1, out_mean, out_var, stream_);
+}
+
+extern "C" int iwvi_lik_predict_mixture(const iwvi_lik_desc* lik, const float* fmean, const float* fvar, const float* Y,
+                                        int64_t N, int S, int Dy, int64_t stride_n, int64_t stride_s,
+                                        float* out_logp, float* out_mean, float* out_var, void* stream_) {
+    const char* what = "iwvi_lik_predict_mixture";
+    hipStream_t stream = (hipStream_t)stream_;
+    LikMixArgs g{};
+    int rc;
+    if ((rc = take_lik(lik, g.lik, what, out_mean != nullptr)) != IWVI_OK) return rc;
+    if (N < 0) { set_error("%s: N = %lld", what, (long long)N); return IWVI_ERR_ARG; }
+    if (S < 1) { set_error("%s: S = %d draws (at least 1)", what, S); return IWVI_ERR_ARG; }
+    if (Dy < 1 || Dy > IWVI_MAX_P) { set_error("%s: Dy = %d outside 1..%d", what, Dy, IWVI_MAX_P); return IWVI_ERR_ARG; }
+    if (g.lik.type == IWVI_LIK_MULTICLASS && (rc = mc_check_classes(g.lik, Dy, what)) != IWVI_OK) return rc;
+    if (stride_n < 0 || stride_s < 0) { set_error("%s: negative stride", what); return IWVI_ERR_ARG; }
+    if (!out_logp && !out_mean && !out_var) { set_error("%s: no output asked for", what); return IWVI_ERR_ARG; }
+    if ((out_mean == nullptr) != (out_var == nullptr)) { set_error("%s: out_mean and out_var go together", what); return IWVI_ERR_ARG; }
+    if ((out_logp == nullptr) != (Y == nullptr)) { set_error("%s: out_logp needs Y, and Y is read for out_logp alone: both or neither", what); return IWVI_ERR_ARG; }
+    if (N == 0) return IWVI_OK;
+    if (!fmean || !fvar) { set_error("%s: null moments", what); return IWVI_ERR_ARG; }
+    g.fmean = fmean; g.fvar = fvar; g.Y = Y;
+    g.N = N; g.S = S; g.Dy = Dy; g.stride_n = stride_n; g.stride_s = stride_s;
+    g.logp = out_logp; g.mean = out_mean; g.var = out_var;
+    if (g.lik.type == IWVI_LIK_MULTICLASS) return mc_launch_mix(g, stream);
+    if (xl_type(g.lik.type)) return xl_launch_mix(g, stream);
+    if (S <= 4) return launch_lik_mix<4>(g, stream);
+    if (S <= 8) return launch_lik_mix<8>(g, stream);
+    if (S <= 16) return launch_lik_mix<16>(g, stream);
+    if (S <= 32) return launch_lik_mix<32>(g, stream);
+    return launch_lik_mix<64>(g, stream);
 }

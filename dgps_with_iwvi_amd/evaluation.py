@@ -12,7 +12,11 @@ Shapiro-Wilk W and any quantiles from it -- with one read-back at the end.
 
 ``kde_log_density_grid`` / ``predictive_density_grid`` evaluate each point's estimate on a whole GRID of levels in one
 ``iwvi_kde_density_grid`` launch: the conditional density picture of the reference's experiments/demo.py (200 inputs x 10 000 samples x
-200 levels), with Silverman's bandwidth or a fixed one; ``evaluate(on_device=True, density_levels=...)`` adds it from the same samples."""
+200 levels), with Silverman's bandwidth or a fixed one; ``evaluate(on_device=True, density_levels=...)`` adds it from the same samples.
+
+``evaluate_mixture`` is the evaluation for ANY likelihood -- class labels, counts, several target columns, where a KDE of
+``m + z sqrt(v)`` samples means nothing --: the Monte Carlo log predictive density, and the error / accuracy of the predictive mixture's
+mean (``model.predict_mixture``: per batch the layer launch and one ``iwvi_lik_predict_mixture`` launch), with one read-back at the end."""
 import ctypes
 
 import numpy as np
@@ -291,4 +295,42 @@ def evaluate(model, X_test, Y_test, num_predict_samples=2000, predict_batch_size
     if mc_loglik:
         lp = model.predict_log_density(X_test, Y_test.reshape(N, -1), num_predict_samples, batch_size=predict_batch_size)
         res["test_loglik_mc"] = float(lp.double().mean())
+    return res
+
+
+def evaluate_mixture(model, X_test, Y_test, num_predict_samples=2000, predict_batch_size=1000, return_predictions=False):
+    """-> dict from ``model.predict_mixture(X_test, num_predict_samples, Y_test)``, any likelihood, any number of target columns:
+    ``test_loglik_mc``, the mean Monte Carlo log predictive density (taken in float64); ``test_rmse``, the mixture mean against Y (every
+    likelihood but ``MultiClass``); ``test_accuracy``: ``Bernoulli`` -- mixture mean > 1/2 against Y --, ``MultiClass`` -- the arg-max of the
+    mixture's class probabilities against the label, the first maximum on ties.  ``return_predictions``: also ``mean`` and ``var``
+    [N, Dout] (NumPy).  One read-back at the end."""
+    from .likelihoods import Bernoulli
+    dev = model.X.device
+    X_test = torch.as_tensor(np.asarray(X_test, dtype=np.float32), device=dev) if not isinstance(X_test, torch.Tensor) else X_test.to(dev, settings.float_type)
+    Y_host = None if isinstance(Y_test, torch.Tensor) else np.asarray(Y_test, dtype=np.float32)
+    Y_test = torch.as_tensor(Y_host, device=dev) if Y_host is not None else Y_test.to(dev, settings.float_type)
+    N = X_test.shape[0]
+    if N == 0 or Y_test.dim() != 2 or Y_test.shape[0] != N:
+        raise ValueError("X_test has %d rows, Y_test must be [%d, columns], got %s" % (N, N, tuple(Y_test.shape)))
+    # (targets given on the host are checked there, by predict_mixture, without a read-back)
+    pm = model.predict_mixture(X_test, num_predict_samples, Y=Y_test if Y_host is None else Y_host, batch_size=predict_batch_size)
+    stats = [pm["log_density"].double().mean()]
+    names = ["test_loglik_mc"]
+    if getattr(model.likelihood, "num_classes", None) is not None:
+        # torch.argmax does not promise the first maximum: the smallest index at which the row's maximum is attained
+        C = pm["mean"].shape[1]
+        idx = torch.arange(C, device=dev).expand_as(pm["mean"])
+        first = torch.where(pm["mean"] == pm["mean"].max(1, keepdim=True).values, idx, torch.full_like(idx, C)).min(1).values
+        stats.append((first == Y_test[:, 0].to(torch.int64)).double().mean())
+        names.append("test_accuracy")
+    else:
+        stats.append(((pm["mean"] - Y_test).double() ** 2).mean().sqrt())
+        names.append("test_rmse")
+        if isinstance(model.likelihood, Bernoulli):
+            stats.append(((pm["mean"] > 0.5) == (Y_test == 1)).double().mean())
+            names.append("test_accuracy")
+    vals = torch.stack(stats).cpu().numpy()                          # the one read-back of the scalars
+    res = {k: float(v) for k, v in zip(names, vals)}
+    if return_predictions:
+        res["mean"], res["var"] = pm["mean"].cpu().numpy(), pm["var"].cpu().numpy()
     return res

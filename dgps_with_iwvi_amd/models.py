@@ -13,6 +13,8 @@ A likelihood other than the Gaussian (``likelihoods.Bernoulli`` / ``StudentT`` /
 the final layer's moments and the local regularisers, ``iwvi_lik_elbo_reduce`` does the rest (Gauss-Hermite variational expectations -- closed
 forms for the exp-link three --, the log-sum-exp, the bound).  For a Gaussian nothing differs from the two-launch form.  ``MultiClass`` alone has targets narrower than the
 final layer -- Y is one column of class labels, the layer has one output per class --: ``likelihoods.target_dim`` / ``output_dim`` translate.
+``predict_mixture`` evaluates a trained model of any likelihood the same way: the layer launch, then one ``iwvi_lik_predict_mixture`` launch gives
+the mean, variance and log density of the Monte Carlo predictive mixture over S draws (``predict_log_density`` of a non-Gaussian model is its density).
 
 Differences from the reference, all documented in DESIGN.md:
   * ``zs`` (one N(0,1) array or None per layer) injects the noise tf.random_normal draws in-graph; None
@@ -490,7 +492,8 @@ class DGP_VI:
         """Monte Carlo log predictive density [N]: log (1/S) sum_s prod_d N(y_nd; m_snd, v_snd + variance), the final layer's moments of
         S draws through the inner layers (drawn as in ``predict_f_multisample``; ``zs``: one [S, N, dim] array or None per layer).  One
         precompute, then per batch of ``batch_size`` points one ``iwvi_dgp_predict_density`` call (the fused forward with a predictive
-        tail, and the merge of its per-point partials): no per-layer sample, moment or log-weight reaches memory."""
+        tail, and the merge of its per-point partials): no per-layer sample, moment or log-weight reaches memory.  A likelihood other than
+        the Gaussian: ``predict_mixture(X, S, Y)["log_density"]`` -- sum_d of ITS predict_density in place of the Gaussian's."""
         X, Y = _data(X), _data(Y)
         S = int(S)
         if S < 1:
@@ -502,20 +505,8 @@ class DGP_VI:
         if Y.dim() != 2 or Y.shape[0] != X.shape[0] or Y.shape[1] != Yd:
             raise ValueError("Y must be [%d, %s], got %s" % (X.shape[0], Yd, tuple(Y.shape)))
         N = X.shape[0]
-        if not is_gaussian(self.likelihood):
-            # logsumexp_s sum_d predict_density(m_s, v_s, Y) - log S over predict_f_multisample's draws (layer-by-layer launches; the
-            # one-launch route is the Gaussian's)
-            zs = self._check_predict_noise("predict_log_density", S, N, zs)
-            bs = int(batch_size or max(N, 1))
-            if bs < 1:
-                raise ValueError("batch_size must be >= 1")
-            out = torch.empty(N, dtype=settings.float_type, device=X.device)
-            for lo in range(0, N, bs):
-                hi = min(N, lo + bs)
-                m, v = self.predict_f_multisample(X[lo:hi], S, zs=[None if z is None else _data(z)[:, lo:hi] for z in zs])
-                lp = self.likelihood.predict_density(m, v, Y[None, lo:hi].expand(m.shape[0], -1, -1)).sum(-1)
-                out[lo:hi] = torch.logsumexp(lp, 0) - float(np.log(S))
-            return out
+        if not is_gaussian(self.likelihood):                         # three launches per batch: precompute, layers, iwvi_lik_predict_mixture
+            return self.predict_mixture(X, S, Y=Y, zs=zs, batch_size=batch_size, _moments=False)["log_density"]
         zs = self._check_predict_noise("predict_log_density", S, N, zs)
         bs = batch_size or max(1, self._PREDICT_ROWS // S)
         if bs < 1:
@@ -531,6 +522,86 @@ class DGP_VI:
             self._fused_forward(nb * S, S, nb, (nb * S,), zs=zb, want_logw=False, use_encoder=False,
                                 X=X[lo:hi], Y=Y[lo:hi], predict=dict(S=S, out=out[lo:hi]))
         return out
+
+    def _predict_log_density_layerwise(self, X, Y, S, zs=None, batch_size=None):
+        """``predict_log_density`` of a non-Gaussian likelihood as it ran before ``predict_mixture`` existed, kept as the route the tests and
+        scripts/time_predict_mixture.py compare with: per batch the layer-by-layer launches of ``predict_f_multisample``, Y expanded to
+        [S, N, .], one elementwise ``iwvi_lik_predict_density`` launch, then a torch ``logsumexp``."""
+        X, Y = _data(X), _data(Y)
+        S, N = int(S), X.shape[0]
+        zs = self._check_predict_noise("predict_log_density", S, N, zs)
+        bs = int(batch_size or max(N, 1))
+        if bs < 1:
+            raise ValueError("batch_size must be >= 1")
+        out = torch.empty(N, dtype=settings.float_type, device=X.device)
+        for lo in range(0, N, bs):
+            hi = min(N, lo + bs)
+            m, v = self.predict_f_multisample(X[lo:hi], S, zs=[None if z is None else _data(z)[:, lo:hi] for z in zs])
+            lp = self.likelihood.predict_density(m, v, Y[None, lo:hi].expand(m.shape[0], -1, -1)).sum(-1)
+            out[lo:hi] = torch.logsumexp(lp, 0) - float(np.log(S))
+        return out
+
+    def predict_mixture(self, X, S, Y=None, zs=None, batch_size=None, _moments=True):
+        """The Monte Carlo predictive MIXTURE over S draws through the inner layers (drawn as in ``predict_f_multisample``; ``zs``: one
+        [S, N, dim] array or None per layer) -> dict of device tensors: ``mean`` [N, Dout] = (1/S) sum_s E_s[y] and ``var`` [N, Dout] =
+        (1/S) sum_s (Var_s[y] + E_s[y]^2) - mean^2, with (E_s, Var_s) the likelihood's ``predict_mean_and_var`` at draw s -- for
+        ``MultiClass`` the class probabilities averaged over the draws --, and with ``Y`` also ``log_density`` [N] = logsumexp_s sum_d
+        predict_density(m_s, v_s, Y) - log S.  Any likelihood.  Per batch of ``batch_size`` points: one precompute, the layer launch without
+        a tail (it leaves the final layer's moments, rows n S + s, and nothing else) and ONE ``iwvi_lik_predict_mixture`` launch."""
+        X = _data(X)
+        S = int(S)
+        if S < 1:
+            raise ValueError("S must be >= 1, got %d" % S)
+        if X.dim() != 2 or X.shape[1] != self._input_dim():
+            raise ValueError("X must be [N, %s], got %s" % (self._input_dim(), tuple(X.shape)))
+        Dy = self._output_dim()
+        if Dy is None:
+            raise ValueError("predict_mixture needs a GP layer as the last layer")
+        N = X.shape[0]
+        if Y is not None:
+            Y_given, Y = Y, _data(Y)
+            Yd = target_dim(self.likelihood, Dy)
+            if Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] != Yd:
+                raise ValueError("Y must be [%d, %s], got %s" % (N, Yd, tuple(Y.shape)))
+            # (the check reads the targets on the host: from the array as given, and not at all while a graph is being captured)
+            if hasattr(self.likelihood, "check_targets") and not (Y.is_cuda and torch.cuda.is_current_stream_capturing()):
+                self.likelihood.check_targets(Y_given)
+        elif not _moments:
+            raise ValueError("nothing asked for: no Y and no moments")
+        zs = self._check_predict_noise("predict_mixture", S, N, zs)
+        bs = max(1, self._PREDICT_ROWS // S) if batch_size is None else int(batch_size)
+        if bs < 1:
+            raise ValueError("batch_size must be >= 1")
+        dev = X.device
+        desc = self.likelihood.lik_desc() if hasattr(self.likelihood, "lik_desc") else None
+        if desc is None:                                             # (an object that only quacks like the Gaussian: is_gaussian)
+            desc = _abi.LikDesc()
+            desc.type = _abi.LIK_GAUSSIAN
+            desc.param[0], desc.param0_dev = self.likelihood.desc_variance()
+        if _moments and desc.type == _abi.LIK_STUDENT_T and not desc.param[1] > 2.0:
+            raise ValueError("predict_mixture: the Student-t variance needs df > 2 (df = %g); predict_log_density gives the density alone" % desc.param[1])
+        res = {}
+        if _moments:
+            res["mean"], res["var"] = (torch.empty(N, Dy, dtype=settings.float_type, device=dev) for _ in range(2))
+        if Y is not None:
+            res["log_density"] = torch.empty(N, dtype=settings.float_type, device=dev)
+        if N == 0:
+            return res
+        self.precompute()
+        last = len(self.layers) - 1
+        for lo in range(0, N, bs):
+            hi = min(N, lo + bs)
+            nb = hi - lo
+            zb = [None if z is None else _data(z)[:, lo:hi].transpose(0, 1).reshape(nb * S, -1) for z in zs]   # point-major rows n S + s
+            _, outs, _ = self._fused_forward(nb * S, S, nb, (nb * S,), zs=zb, sampled_kl=False, want_layers=True, want_logw=False,
+                                             use_encoder=False, X=X[lo:hi], outputs_for={last})
+            fm, fv = outs[last]["mean"], outs[last]["var"]
+            yb = None if Y is None else _abi.dev_tensor(Y[lo:hi].contiguous(), "Y")
+            _abi.check(_abi.lib().iwvi_lik_predict_mixture(
+                desc, _abi.ptr(fm), _abi.ptr(fv), _abi.ptr(yb), nb, S, Dy, S, 1,
+                None if Y is None else _abi.ptr(res["log_density"][lo:hi]),
+                _abi.ptr(res["mean"][lo:hi]) if _moments else None, _abi.ptr(res["var"][lo:hi]) if _moments else None, _abi.stream_ptr()))
+        return res
 
     def _check_predict_noise(self, what, S, N, zs):
         """``zs`` of the fused predictive routes: one [S, N, dim] array or None per layer; no fed latent-variable placeholders."""
@@ -553,8 +624,9 @@ class DGP_VI:
         ``predict_y_samples(X, S, zs, z_y)``; what is not given is drawn in the kernel.  The result is a transposed view of the kernel's
         [N, S, Dy], in which a point's S samples are contiguous (what ``evaluation.sample_stats`` reads fastest)."""
         if not is_gaussian(self.likelihood):
-            raise NotImplementedError("predict_y_samples_fused adds Gaussian noise in the launch's tail; with %s use predict_y_samples "
-                                      "(layer by layer, the likelihood's predict_mean_and_var)" % type(self.likelihood).__name__)
+            raise NotImplementedError("predict_y_samples_fused adds Gaussian noise in the launch's tail; with %s use predict_mixture (the "
+                                      "predictive mixture's moments and log density over S draws) or predict_y_samples (layer by layer, "
+                                      "the likelihood's predict_mean_and_var)" % type(self.likelihood).__name__)
         X = _data(X)
         S = int(S)
         if S < 1:

@@ -28,7 +28,7 @@ extern "C" {
 #endif
 
 /* 19, with additive extensions: iwvi_dgp_predict_samples and iwvi_sample_stats, then the iwvi_lik_* entry points (likelihoods other than
- * the Gaussian), were added without a change to any existing entry point or struct, so the number did not move and a caller built against
+ * the Gaussian; iwvi_lik_predict_mixture, their Monte Carlo predictive mixture, last), were added without a change to any existing entry point or struct, so the number did not move and a caller built against
  * 19 keeps working.  A C caller that wants the new symbols looks them up (dlsym), Python asks hasattr(lib, ...). */
 #define IWVI_ABI_VERSION 19
 
@@ -742,6 +742,28 @@ int iwvi_lik_predict_density(const iwvi_lik_desc* lik, const float* Fmu, const f
                              int64_t T, int Dy, int64_t row_div, int64_t row_mod, float* out, void* stream);
 int iwvi_lik_predict_mean_and_var(const iwvi_lik_desc* lik, const float* Fmu, const float* Fvar, int64_t n,
                                   float* out_mean, float* out_var, void* stream);
+
+/* The Monte Carlo predictive MIXTURE of a test point over S draws through the inner layers, on the final layer's moments of those draws
+ * (additive extension of ABI 19).  Per test point n, over its S draws s (moments row n*stride_n + s*stride_s, Dy columns):
+ *   out_logp[n]    = logsumexp_s( sum_d predict_density(fmean, fvar, Y[n, d]) ) - log S        (Y, out_logp: both or neither)
+ *   out_mean[n, d] = (1/S) sum_s E_s[y_d]
+ *   out_var [n, d] = (1/S) sum_s (Var_s[y_d] + E_s[y_d]^2) - out_mean[n, d]^2                  (law of total variance)
+ * predict_density and (E_s, Var_s) = predict_mean_and_var are exactly what the elementwise entries above compute for the type (the same
+ * device functions).  MULTICLASS: Dy = C, Y is [N, 1] of labels, out_mean = the class probabilities averaged over the draws, out_var =
+ * P - P^2 of those; the C probabilities of a draw are evaluated once and the label's density is the logarithm of its own.
+ * Layouts: point-major rows n S + s (stride_n = S, stride_s = 1) or sample-major rows s N + n (stride_n = 1, stride_s = N); strides >= 0.
+ * ONE launch, no workspace, no ticket, no host synchronisation: capturable in a hipGraph.  Arithmetic: float32 inside a draw; the
+ * log-sum-exp is shifted by the running float32 maximum and summed in float64 (a point whose every draw has density -inf gives -inf, not
+ * NaN); sum_s E_s and sum_s (Var_s + E_s^2) accumulate in float64 and out_var is formed there and rounded once.  The exp-link types add a
+ * point's target-only terms (sum_d c0(y_d)) once, outside the log-sum-exp.
+ * Any output may be NULL, at least one must be given, out_mean and out_var go together.  All seven types are accepted -- the Gaussian's
+ * out_logp is what iwvi_dgp_predict_density computes from the same moments: a cross-check.  A Student-t with df <= 2 is refused only when
+ * the moments are asked for.  IWVI_ERR_ARG (with iwvi_last_error) before any launch for: a null or invalid descriptor, N < 0, S < 1, Dy
+ * outside 1..IWVI_MAX_P, MULTICLASS with Dy != C, out_logp without Y or Y without out_logp, out_mean without out_var or the reverse, no
+ * output at all.  N = 0: IWVI_OK, nothing is launched. */
+int iwvi_lik_predict_mixture(const iwvi_lik_desc* lik, const float* fmean, const float* fvar, const float* Y,
+                             int64_t N, int S, int Dy, int64_t stride_n, int64_t stride_s,
+                             float* out_logp, float* out_mean, float* out_var, void* stream);
 
 /* white=False (temp_workaround.py:63-65: "another backsubstitution in the unwhitened case").  The unwhitened
  * q(u) = N(f, q_sqrt q_sqrt^T) gives the same conditional as the whitened one with f_w = Lm^-1 f and
