@@ -119,6 +119,15 @@ class AdamTensor(ctypes.Structure):
                 ("n", c_int64), ("transform", ctypes.c_int32)]
 
 
+SGHMC_MAX_TENSORS = 8
+
+
+class SghmcTensor(ctypes.Structure):
+    """struct iwvi_sghmc_tensor (include/iwvi_hip.h)."""
+    _fields_ = [("theta", c_void_p), ("grad", c_void_p), ("xi", c_void_p), ("g", c_void_p), ("g2", c_void_p), ("p", c_void_p),
+                ("theta64", c_void_p), ("noise", c_void_p), ("noise_out", c_void_p), ("n", c_int64)]
+
+
 # name -> (restype, argtypes); every symbol include/iwvi_hip.h declares
 PROTOTYPES = {
     "iwvi_version": (c_int, []),
@@ -247,6 +256,8 @@ PROTOTYPES = {
     "iwvi_unwhiten": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "iwvi_fill_normal": (c_int, [c_void_p, c_int64, ctypes.c_uint64, ctypes.c_uint64, c_void_p]),
     "iwvi_fill_normal_dev": (c_int, [c_void_p, c_int64, ctypes.c_uint64, c_void_p, c_void_p]),
+    "iwvi_sghmc_step": (c_int, [ctypes.POINTER(SghmcTensor), c_int, c_double, c_double, c_double, c_int, ctypes.c_uint64, c_void_p, c_void_p]),
+    "iwvi_neg_log_prior": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
 }
 
 DEBUG_OPTIONS = ("IWVI_BW_FUSED", "IWVI_CHAIN_EXIT", "IWVI_FW_SLOW_TAIL", "IWVI_FW_MAX_NS", "IWVI_NATGRAD_UNFUSED", "IWVI_NG_ONE_WG", "IWVI_NG_STOP", "IWVI_DEBUG_STOP", "IWVI_PRE_STAMP_P",

@@ -112,7 +112,7 @@ def _param_desc(layer, dense_state=None):
     M, R = layer.num_inducing, layer.num_outputs
     kern = layer._base_kern()
     b = _abi.GpBwdDesc()
-    Z, q_mu, q_sqrt = (_abi.dev_tensor(t.contiguous(), n) for t, n in ((layer._Z(), "Z"), (layer.q_mu, "q_mu"), (layer.q_sqrt, "q_sqrt")))
+    Z, q_mu, q_sqrt = (_abi.dev_tensor(t.contiguous(), n) for t, n in ((layer._Z(), "Z"), (layer.q_mu, "q_mu"), (layer.q_sqrt_operand(), "q_sqrt")))
     b.state = (dense_state or layer.state()).buf.data_ptr()
     b.Z, b.lengthscales = Z.data_ptr(), kern.lengthscales.data_ptr()
     b.q_mu, b.q_sqrt = q_mu.data_ptr(), q_sqrt.data_ptr()
@@ -483,6 +483,8 @@ def _final_q_gradients(model, fin, adj, kl_weight, prefactor, cur):
         done = torch.cuda.Event()                                # AFTER its update: the first successor captured behind these launches keeps their
         done.record(cur)                                         # hardware queue, and that has to be the update, not the side work
         model._prefactor_after = done
+    if model.layers[i].q_sqrt is None:
+        return {"l%d.q_mu" % i: g["dq_mu"]}
     return {"l%d.q_mu" % i: g["dq_mu"], "l%d.q_sqrt" % i: g["dq_sqrt"]}
 
 
@@ -531,7 +533,7 @@ def _reverse_sweep(model, saved, prepared, XY, adj, mode_vi, kl_weight, overlap,
                             side_stream2=cur if i == split else None)
             for k_out, k_name in (("dZ", "Z"), ("dls", "ls"), ("dvariance", "var"), ("dq_mu", "q_mu"), ("dq_sqrt", "q_sqrt"),
                                   ("dW", "W"), ("dmf_A", "mfA")):
-                if k_out in g:
+                if k_out in g and not (k_out == "dq_sqrt" and layer.q_sqrt is None):     # (q_sqrt = None: there is no such parameter)
                     grads["l%d.%s" % (i, k_name)] = g[k_out]
             dF = g.get("dF")
             if pending is not None:
@@ -618,7 +620,9 @@ def parameter_list(model):
             for j, (w, b) in enumerate(zip(l.encoder.Ws, l.encoder.bs)):
                 out += [("l%d.encW%d" % (i, j), w), ("l%d.encb%d" % (i, j), b)]
         elif isinstance(l, GPLayer):
-            out += [("l%d.Z" % i, l._Z()), ("l%d.ls" % i, l._base_kern().lengthscales), ("l%d.q_mu" % i, l.q_mu), ("l%d.q_sqrt" % i, l.q_sqrt)]
+            out += [("l%d.Z" % i, l._Z()), ("l%d.ls" % i, l._base_kern().lengthscales), ("l%d.q_mu" % i, l.q_mu)]
+            if l.q_sqrt is not None:
+                out.append(("l%d.q_sqrt" % i, l.q_sqrt))
             if isinstance(l.kern, SharedMixedMok):
                 out.append(("l%d.W" % i, l.kern.W))
             if l.mean_function.mf_type == _abi.MF_LINEAR:

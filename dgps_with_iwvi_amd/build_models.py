@@ -5,8 +5,8 @@
 ``'G5_G5'`` ('G<r>': a GP layer of r latent GPs mixed to the input width, 'L<d>': a latent-variable layer of d
 dimensions), ``ARGS.M`` inducing points, ``ARGS.likelihood_variance``, ``ARGS.minibatch_size``,
 ``ARGS.num_IW_samples``.  The training op the reference attaches (``model.train_op``: natural gradient + Adam,
-:270-304) is ``attach_train_op`` over ``training.Trainer`` (row F1); SGHMC and the CVAE baseline are out of scope
-and raise.
+:270-304) is ``attach_train_op`` over ``training.Trainer`` (row F1).  ``build_sghmc_model`` builds the reference's third mode, ``'SGHMC'`` (``q_sqrt = None`` layers,
+the sampler of ``sghmc.SGHMC`` as the train op); ``build_model`` itself raises for it and for the CVAE baseline, which is out of scope.
 
 Initial values follow the reference: first-layer inducing inputs by k-means of X (or X padded with N(0,1) rows when
 N <= M), deeper layers N(0,1) with their first columns taken from them (:218-219, :239-240); RBF-ARD kernels with
@@ -75,8 +75,9 @@ def build_layers(configuration, X, M, rng=None):
 
 def build_model(ARGS, X, Y, apply_name=True, device=None):
     if ARGS.mode not in ("VI", "IWAE"):
-        raise NotImplementedError("mode %r: the VI / IWAE models (with their NatGrad + Adam train_op) are built here; SGHMC "
-                                  "and the CVAE baseline are outside the scope of this port (SURVEY.md section 8)" % (ARGS.mode,))
+        raise NotImplementedError("mode %r: the VI / IWAE models (with their NatGrad + Adam train_op) are built here; an SGHMC model "
+                                  "(with its sampler + Adam train_op) by build_sghmc_model; the CVAE baseline is outside the scope "
+                                  "of this port (SURVEY.md section 8)" % (ARGS.mode,))
     layers = build_layers(ARGS.configuration, X, ARGS.M)
     lik = Gaussian(ARGS.likelihood_variance)
     name = "Model" if apply_name else None
@@ -91,6 +92,42 @@ def build_model(ARGS, X, Y, apply_name=True, device=None):
         # cluster: an 8-D layer is not well-conditioned by its dimension alone); the Trainer repeats it at every staircase epoch
         model.f64_route_report = model.autotune_f64()
     attach_train_op(model, ARGS)
+    return model
+
+
+def build_sghmc_model(ARGS, X, Y, apply_name=True, device=None):
+    """The reference's ``mode == 'SGHMC'`` model (build_models.py:252-261, :306-335): the same layer stack with ``q_sqrt = None`` on every
+    GP layer (no 1e-5 scaling: there is nothing to scale) in a ``DGP_VI``, and the reference's attributes on it, none of which takes a
+    session: ``model.sghmc_optimizer`` (``sghmc.SGHMC``, window of 100, Adam at ``ARGS.lr`` without decay), ``model.init_op()`` (the
+    update step at epsilon = 0.01, mdecay = 0.05; global_step = 0), ``model.train_op()`` (global_step += 1, ``sghmc_step``,
+    ``train_hypers``) and ``model.global_step``.  Configurations with a latent-variable layer are refused (the reference's grid runs
+    '', 'G5' and 'G5_G5' this way)."""
+    if any(kind == "L" for kind, _ in parse_configuration(ARGS.configuration)):
+        raise NotImplementedError("SGHMC: configurations with a latent-variable layer are not covered (%r)" % (ARGS.configuration,))
+    layers = build_layers(ARGS.configuration, X, ARGS.M)
+    for layer in layers:
+        layer.q_sqrt = None                                          # :253-257; q_mu belongs to the sampler
+    model = DGP_VI(X, Y, layers, Gaussian(ARGS.likelihood_variance), minibatch_size=ARGS.minibatch_size,
+                   name="Model" if apply_name else None)
+    model = model.to(device or settings.default_device())
+    if model.X.is_cuda and settings.f64_stage1 == "auto" and getattr(ARGS, "autotune_f64", True):
+        model.f64_route_report = model.autotune_f64()
+    from .sghmc import SGHMC
+    opt = SGHMC(model, window_size=100, lr=getattr(ARGS, "lr", 5e-3), fix_linear=getattr(ARGS, "fix_linear", True),
+                use_graph=bool(getattr(ARGS, "use_graph", False)))
+    model.sghmc_optimizer = opt
+    model.global_step = 0
+
+    def init_op():
+        opt.generate_update_step(0.01, 0.05)                         # :326-329
+        model.global_step = 0
+
+    def train_op():                                                  # :318-321
+        model.global_step += 1
+        opt.sghmc_step()
+        return opt.train_hypers()
+
+    model.init_op, model.train_op = init_op, train_op
     return model
 
 
@@ -171,7 +208,10 @@ def state_dict(model):
             out[p + "lengthscales"] = torch.as_tensor(kern.lengthscales).detach().cpu().numpy()
             out[p + "variance"] = np.float64(kern.variance)
             out[p + "q_mu"] = layer.q_mu.detach().cpu().numpy()
-            out[p + "q_sqrt"] = layer.q_sqrt.detach().cpu().numpy()
+            if layer.q_sqrt is None:                                  # the SGHMC mode: no such parameter; the mode itself is recorded
+                out[p + "q_sqrt_none"] = np.int64(1)
+            else:
+                out[p + "q_sqrt"] = layer.q_sqrt.detach().cpu().numpy()
             if isinstance(layer.kern, SharedMixedMok):
                 out[p + "W"] = layer.kern.W.detach().cpu().numpy()
             if layer.mean_function.A is not None:                     # Linear: trainable when fix_linear=False (:224-227)
@@ -221,7 +261,12 @@ def load_state_dict(model, state):
             put(kern, "lengthscales", state[p + "lengthscales"])
             kern.variance = float(state[p + "variance"])
             put(layer, "q_mu", state[p + "q_mu"])
-            put(layer, "q_sqrt", state[p + "q_sqrt"])
+            if p + "q_sqrt_none" in state:
+                layer.q_sqrt = None
+            elif layer.q_sqrt is None:
+                layer.q_sqrt = t(state[p + "q_sqrt"])
+            else:
+                put(layer, "q_sqrt", state[p + "q_sqrt"])
             if isinstance(layer.kern, SharedMixedMok):
                 put(layer.kern, "W", state[p + "W"])
             if layer.mean_function.A is not None and p + "mf_A" in state:

@@ -16,7 +16,9 @@ Shapiro-Wilk W and any quantiles from it -- with one read-back at the end.
 
 ``evaluate_mixture`` is the evaluation for ANY likelihood -- class labels, counts, several target columns, where a KDE of
 ``m + z sqrt(v)`` samples means nothing --: the Monte Carlo log predictive density, and the error / accuracy of the predictive mixture's
-mean (``model.predict_mixture``: per batch the layer launch and one ``iwvi_lik_predict_mixture`` launch), with one read-back at the end."""
+mean (``model.predict_mixture``: per batch the layer launch and one ``iwvi_lik_predict_mixture`` launch), with one read-back at the end.
+
+``evaluate_sghmc`` is the evaluation of an SGHMC model over its collected posterior samples: one fused y-sample per kept theta and test point."""
 import ctypes
 
 import numpy as np
@@ -295,6 +297,81 @@ def evaluate(model, X_test, Y_test, num_predict_samples=2000, predict_batch_size
     if mc_loglik:
         lp = model.predict_log_density(X_test, Y_test.reshape(N, -1), num_predict_samples, batch_size=predict_batch_size)
         res["test_loglik_mc"] = float(lp.double().mean())
+    return res
+
+
+def evaluate_sghmc(model, posterior_samples, X_test, Y_test, predict_batch_size=1000, quantiles=None, zs=None, z_y=None,
+                   return_samples=False):
+    """The reference's evaluation of an SGHMC model (run_conditional_density_estimation.py:136-156): the predictive sample set of a test
+    point is ONE ``predict_y_samples(x, 1)`` per kept theta.  ``posterior_samples``: per GP layer a device tensor [S, M, R]
+    (``sghmc.SGHMC.collect_samples``).  Every K_uu is factorised once; per kept theta only the layers' q(u) images are re-packed
+    (``precompute(q_moved=...)``: IWVI_GP_REUSE_FACTOR) and per batch of points one fused y-sample launch (``iwvi_dgp_predict_samples``,
+    S = 1) writes row j of an [S, N] buffer -- column j of its [N, S] transpose --; then one ``iwvi_sample_stats`` pass per batch reads
+    each point's S samples through the strides.  Same result keys as ``evaluate(on_device=True)``.  The model's q_mu are restored.
+    ``zs`` (per layer [S, N, dim] or None) / ``z_y`` [S, N, Dy]: injected noise (tests); ``return_samples``: also ``samples`` [N, S]."""
+    from .layers import GPLayer
+    from .likelihoods import is_gaussian
+    if not is_gaussian(model.likelihood):
+        raise NotImplementedError("evaluate_sghmc adds Gaussian noise in the sampling launch's tail")
+    if not model.layers or not all(isinstance(l, GPLayer) for l in model.layers):
+        raise NotImplementedError("evaluate_sghmc: a stack of GP layers (no latent-variable layer under SGHMC)")
+    if quantiles is not None:
+        _check_probs(quantiles)
+    if len(posterior_samples) != len(model.layers):
+        raise ValueError("posterior_samples needs one [S, M, R] tensor per GP layer")
+    S = int(posterior_samples[0].shape[0])
+    for l, ps in zip(model.layers, posterior_samples):
+        _abi.dev_tensor(ps, "posterior_samples")
+        if tuple(ps.shape) != (S,) + tuple(l.q_mu.shape):
+            raise ValueError("posterior_samples: expected %s, got %s" % ((S,) + tuple(l.q_mu.shape), tuple(ps.shape)))
+    if S < 2 or S > MAX_SAMPLES:
+        raise ValueError("S=%d kept samples out of range (2..%d)" % (S, MAX_SAMPLES))
+    if model._output_dim() != 1:
+        raise ValueError("the reference's evaluation is for one output column")
+    dev = model.X.device
+    X_test = torch.as_tensor(np.asarray(X_test, dtype=np.float32), device=dev) if not isinstance(X_test, torch.Tensor) else X_test.to(dev, settings.float_type)
+    Y_test = torch.as_tensor(np.asarray(Y_test, dtype=np.float32), device=dev) if not isinstance(Y_test, torch.Tensor) else Y_test.to(dev, settings.float_type)
+    N = X_test.shape[0]
+    if N == 0 or Y_test.shape[0] != N or Y_test.numel() != N:
+        raise ValueError("X_test has %d rows, Y_test must be one column of as many, got %s" % (N, tuple(Y_test.shape)))
+    if X_test.dim() != 2 or X_test.shape[1] != model._input_dim():
+        raise ValueError("X_test must be [N, %s], got %s" % (model._input_dim(), tuple(X_test.shape)))
+    bs = int(predict_batch_size)
+    if bs < 1:
+        raise ValueError("predict_batch_size must be >= 1")
+    zs = model._check_predict_noise("evaluate_sghmc", S, N, zs)
+    if z_y is not None and tuple(z_y.shape) != (S, N, 1):
+        raise ValueError("z_y must be [S, N, 1] = %s, got %s" % ((S, N, 1), tuple(z_y.shape)))
+    X_test = X_test.contiguous()
+    buf = torch.empty(S, N, dtype=settings.float_type, device=dev)
+    moved = set(range(len(model.layers)))
+    chain = [l.q_mu.clone() for l in model.layers]
+    try:
+        model.precompute()                                           # the one factorisation
+        for j in range(S):
+            for l, ps in zip(model.layers, posterior_samples):
+                l.q_mu.copy_(ps[j])
+            model.precompute(q_moved=moved)
+            for lo in range(0, N, bs):
+                hi = min(N, lo + bs)
+                nb = hi - lo
+                zb = [None if z is None else z[j, lo:hi].to(dev, settings.float_type).reshape(nb, -1).contiguous() for z in zs]
+                zyb = None if z_y is None else _abi.dev_tensor(z_y[j, lo:hi].to(dev, settings.float_type).reshape(nb, 1).contiguous(), "z_y")
+                model._fused_forward(nb, 1, nb, (nb,), zs=zb, want_logw=False, use_encoder=False, X=X_test[lo:hi],
+                                     predict=dict(S=1, out_y=buf[j, lo:hi].view(nb, 1, 1), z_y=zyb))
+    finally:
+        for l, t in zip(model.layers, chain):
+            l.q_mu.copy_(t)
+    parts = [sample_stats(buf[:, lo:lo + bs], Y_test.reshape(-1)[lo:lo + bs], shapiro=True, quantiles=quantiles) for lo in range(0, N, bs)]
+    cat = {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+    W = cat["W"].double().sort().values
+    med = 0.5 * (W[(W.numel() - 1) // 2] + W[W.numel() // 2])
+    vals = torch.stack([cat["logp"].double().mean(), cat["sqerr"].double().mean().sqrt(), med]).cpu().numpy()   # the one read-back
+    res = {"test_loglik": float(vals[0]), "test_rmse": float(vals[1]), "test_shapiro_W_median": float(vals[2])}
+    if quantiles is not None:
+        res["test_quantiles"] = cat["quantiles"].cpu().numpy()
+    if return_samples:
+        res["samples"] = buf.t()
     return res
 
 

@@ -4,7 +4,7 @@ The layer kernel's hot variants sit at the 256-VGPR limit: a source change anywh
 scratch, and a variant that only the large configs take then regresses unnoticed (round 4: the five-sub-tile large-M variant went
 216 B into scratch, configs[3] 1.27 -> 1.43 ms, for four commits).  ``check()`` is run by ``__graft_entry__.build()`` and by
 tests/test_kernel_resources.py: it fails when a ``k_dgp_forward`` or ``k_bw_chain`` instantiation (the predictive and sampling variants of the
-forward included), ``k_sample_stats``, ``k_kde_grid`` or a likelihood-tail kernel (every ``k_lik_*``, ``k_mc_*``, ``k_xl_*``, the ``*_mix`` kernels of the predictive mixture included) uses scratch memory
+forward included), ``k_sample_stats``, ``k_kde_grid`` or a likelihood-tail kernel (every ``k_lik_*``, ``k_mc_*``, ``k_xl_*``, the ``*_mix`` kernels of the predictive mixture included) or the SGHMC update ``k_sghmc_step`` uses scratch memory
 (``.private_segment_fixed_size`` > 0) beyond what ``ALLOWED_SCRATCH`` lists, when a listed spill count grows, or when a kernel listed in ``MAX_VGPRS`` exceeds its VGPR ceiling.
 
   python -m dgps_with_iwvi_amd.kernel_resources [--write profiles/<tag>_kernel_resources.txt]
@@ -30,7 +30,8 @@ FIELDS = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_sp
 #  k_xl_*: csrc/likelihood_explink.hip -- closed forms, and a float64 lgamma / digamma of the shape per wave)
 NO_SCRATCH = ("k_dgp_forward", "k_bw_chain", "k_sample_stats", "k_lik_elbo", "k_lik_elbo_bwd", "k_lik_elem", "k_lik_finish", "k_kde_grid",
               "k_mc_elbo", "k_mc_elbo_bwd", "k_mc_elem", "k_xl_elbo", "k_xl_elbo_bwd", "k_xl_elem",
-              "k_lik_mix", "k_mc_mix", "k_xl_mix")
+              "k_lik_mix", "k_mc_mix", "k_xl_mix",
+              "k_sghmc_step")          # csrc/sghmc.hip: the sampler's update, replayed 10 000 times per evaluation (56 VGPRs today)
 # ... except these (demangled-name substring -> bytes of scratch it is known to use; lower it when a kernel improves)
 ALLOWED_SCRATCH = {
     # round 6 (profiles/r06_kernel_resources.txt): every BIG variant (some layer with M > 128: configs[3] / [4]) and every float64-route
@@ -58,7 +59,8 @@ MAX_SPILLS = {
 MAX_VGPRS = {"k_lik_elbo": 128, "k_lik_elbo_bwd": 128, "k_lik_elem": 128, "k_lik_finish": 32,
              "k_mc_elbo": 128, "k_mc_elbo_bwd": 128, "k_mc_elem": 128,
              "k_xl_elbo": 96, "k_xl_elbo_bwd": 72, "k_xl_elem": 64,
-             "k_lik_mix": 128, "k_mc_mix": 128, "k_xl_mix": 96}
+             "k_lik_mix": 128, "k_mc_mix": 128, "k_xl_mix": 96,
+             "k_sghmc_step": 64}
 
 
 def csrc_hash():

@@ -40,7 +40,8 @@ class GPLayer:
         dev = self._Z().device
         self.q_mu = torch.zeros(self.num_inducing, num_outputs, dtype=settings.float_type, device=dev)
         # full [R, M, M] storage; like gpflow's LowerTriangular transform only the lower band is used
-        self.q_sqrt = torch.eye(self.num_inducing, dtype=settings.float_type, device=dev).repeat(num_outputs, 1, 1)
+        self._q_sqrt = torch.eye(self.num_inducing, dtype=settings.float_type, device=dev).repeat(num_outputs, 1, 1)
+        self._q_sqrt_zero = self._nlp = None                      # ``q_sqrt = None`` (the SGHMC mode): the zero operand and the prior term
         self.kern = kern.to(dev)
         self.mean_function = (mean_function or Zero()).to(dev)
         self.num_outputs = num_outputs
@@ -65,9 +66,54 @@ class GPLayer:
         self.feature.to(device)
         self.kern.to(device)
         self.mean_function.to(device)
-        self.q_mu, self.q_sqrt = self.q_mu.to(device), self.q_sqrt.to(device)
+        self.q_mu = self.q_mu.to(device)
+        if self._q_sqrt is not None:
+            self._q_sqrt = self._q_sqrt.to(device)
+        self._q_sqrt_zero = self._nlp = None
         self._state = None
         return self
+
+    # -- q_sqrt = None: the SGHMC mode's layer (reference build_models.py:252-257) ----------
+    @property
+    def q_sqrt(self):
+        return self._q_sqrt
+
+    @q_sqrt.setter
+    def q_sqrt(self, value):
+        self._q_sqrt = value
+
+    @q_sqrt.deleter
+    def q_sqrt(self):                                             # the reference's ``del layer.q_sqrt; layer.q_sqrt = None``
+        self._q_sqrt = None
+
+    def q_sqrt_operand(self):
+        """What the kernels are handed as q_sqrt [R, M, M]: the parameter, or -- ``q_sqrt is None`` -- an all-zero operand owned by the
+        layer: the conditional then has no q(u) covariance term, var = sigma^2 - |a|^2 (temp_workaround.py:59, :70-85 skipped)."""
+        if self._q_sqrt is not None:
+            return self._q_sqrt
+        z = getattr(self, "_q_sqrt_zero", None)
+        shape = (self.num_outputs, self.num_inducing, self.num_inducing)
+        if z is None or z.device != self.q_mu.device or tuple(z.shape) != shape:
+            z = self._q_sqrt_zero = torch.zeros(shape, dtype=settings.float_type, device=self.q_mu.device)
+        return z
+
+    def global_regulariser_parts(self):
+        """The layer's global regulariser as the reductions read it (float64 device tensor, summed by the reader): the R per-GP shares of
+        KL[q(u) || p(u)] of the last precompute, or -- ``q_sqrt is None`` -- the one-element negative log prior of the whitened q_mu
+        (temp_workaround.py:167-184), written by ``iwvi_neg_log_prior`` beside the last precompute.  (The state's own kl slots are +inf
+        for a zero q_sqrt: they are never read in that mode.)"""
+        if self._q_sqrt is not None:
+            return self.state().kl_parts
+        if getattr(self, "_nlp", None) is None or self._nlp.device != self.q_mu.device:
+            self._neg_log_prior()
+        return self._nlp
+
+    def _neg_log_prior(self):
+        from .temp_workaround import neg_log_prior
+        cur = getattr(self, "_nlp", None)
+        if cur is None or cur.device != self.q_mu.device:
+            cur = self._nlp = torch.empty(1, dtype=torch.float64, device=self.q_mu.device)
+        neg_log_prior(self.q_mu, out=cur)                        # same buffer every evaluation (a captured graph keeps writing it)
 
     def state(self):
         dev = self.q_mu.device
@@ -88,7 +134,9 @@ class GPLayer:
     def state_desc(self, state=None):
         """``iwvi_gp_desc`` of this layer's current parameters (for a batched precompute); ``state``: the buffer to fill."""
         q_mu = _abi.dev_tensor(self.q_mu.contiguous(), "q_mu")
-        q_sqrt = _abi.dev_tensor(self.q_sqrt.contiguous(), "q_sqrt")
+        q_sqrt = _abi.dev_tensor(self.q_sqrt_operand().contiguous(), "q_sqrt")
+        if self._q_sqrt is None and state is None:               # the forward's own state: its regulariser is the prior term, formed here
+            self._neg_log_prior()
         if q_sqrt.shape != (self.num_outputs, self.num_inducing, self.num_inducing):
             raise ValueError("q_sqrt must be [R, M, M], got %s" % (tuple(q_sqrt.shape),))
         d = (state or self.state()).desc(_abi.dev_tensor(self._Z(), "Z"), self._base_kern(), q_mu, q_sqrt,
@@ -102,8 +150,8 @@ class GPLayer:
 
     @property
     def kl(self):
-        """KL[q(u)||p(u)] of the last precompute (0-dim float64 device tensor)."""
-        return self.state().kl
+        """KL[q(u)||p(u)] of the last precompute (0-dim float64 device tensor); ``q_sqrt is None``: the negative log prior of q_mu."""
+        return self.global_regulariser_parts().sum()
 
     def fused_desc(self, z=None, outputs=None, draw=True):
         """``iwvi_layer_desc`` of this layer for ``iwvi_dgp_forward`` (state must be precomputed).
@@ -151,12 +199,12 @@ class GPLayer:
         if not _precomputed:
             self.precompute()
         samples, mean, cov = multisample_sample_conditional(
-            F, self.feature, self.kern, self.q_mu, full_cov=full_cov, q_sqrt=self.q_sqrt, white=True,
+            F, self.feature, self.kern, self.q_mu, full_cov=full_cov, q_sqrt=self.q_sqrt_operand(), white=True,
             z=z, state=self.state(), mean_function=self.mean_function,      # layers.py:46-48 fused into the kernels
             precomputed=True, want_sample=_want_sample, f64_stage1=self.uses_f64_stage1())
         # layers.py:44 (computed by the precompute); _kl_parts hands the model the R per-GP shares
         # so that the ELBO reduction sums them without an extra launch
-        kl = self.state().kl_parts if _kl_parts else self.kl
+        kl = self.global_regulariser_parts() if _kl_parts else self.kl
         return samples, mean, cov, kl
 
 

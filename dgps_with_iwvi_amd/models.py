@@ -360,7 +360,9 @@ class DGP_VI:
         return self._xy_cache
 
     def _global_kls(self):
-        return [l.state().kl_parts for l in self.layers if l.regularizer_type is RegularizerType.GLOBAL]
+        # (a GP layer without q_sqrt -- the SGHMC mode -- hands over the negative log prior of its q_mu instead of the state's KL shares)
+        return [l.global_regulariser_parts() if isinstance(l, GPLayer) else l.state().kl_parts
+                for l in self.layers if l.regularizer_type is RegularizerType.GLOBAL]
 
     def _reduce_logw(self, logw, global_kls, B, K, stride_b, stride_k, mode_vi, want_ms=False, K_total=None):
         """``iwvi_logw_reduce``: logsumexp/mean over K + scaled sum - global KLs (models.py:138-150, :69-86)."""

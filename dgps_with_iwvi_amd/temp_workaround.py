@@ -324,9 +324,22 @@ def multisample_sample_conditional(Xnew, feat, kern, f, *, full_cov=False, full_
         f64_stage1=f64_stage1)
 
 
+def neg_log_prior(q_mu, out=None):
+    """The SGHMC branch of the reference's ``gauss_kl`` (:167-184, ``q_sqrt is None``, whitened): -log N(q_mu; 0, I) summed over all entries
+    = 1/2 |q_mu|_F^2 + 1/2 M R log 2 pi (``iwvi_neg_log_prior``).  Returns a 0-dim float64 device tensor; ``out``: a 1-element float64
+    device buffer to write instead of a fresh one."""
+    q_mu = _abi.dev_tensor(q_mu.contiguous(), "q_mu")
+    if q_mu.dim() != 2:
+        raise ValueError("q_mu must be [M, R], got %s" % (tuple(q_mu.shape),))
+    M, R = q_mu.shape
+    out = torch.empty(1, dtype=torch.float64, device=q_mu.device) if out is None else _abi.dev_tensor(out, "out", torch.float64)
+    _abi.check(_abi.lib().iwvi_neg_log_prior(_abi.ptr(q_mu), M, R, _abi.ptr(out), _abi.stream_ptr()))
+    return out[0]
+
+
 def gauss_kl(q_mu, q_sqrt, K=None):
     """Whitened KL[q(u) || p(u)] summed over outputs (reference :167-188, KL branch :186-188).
-    Returns a 0-dim float64 device tensor.  The SGHMC branch (q_sqrt None) is out of scope."""
+    Returns a 0-dim float64 device tensor.  The SGHMC branch (q_sqrt None) is ``neg_log_prior``."""
     if q_sqrt is None or K is not None:
         raise NotImplementedError("only the whitened KL branch is on the IW-ELBO path")
     q_mu = _abi.dev_tensor(q_mu.contiguous(), "q_mu")

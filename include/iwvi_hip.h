@@ -783,6 +783,33 @@ int iwvi_fill_normal(float* out, int64_t n, uint64_t seed, uint64_t offset, void
  * hipGraph draw fresh noise on every replay. */
 int iwvi_fill_normal_dev(float* out, int64_t n, uint64_t seed, uint64_t* state, void* stream);
 
+/* The SGHMC inference mode (experiments/sghmc.py; csrc/sghmc.hip).
+ * iwvi_neg_log_prior: -log N(q_mu; 0, I) of a whitened q_mu [M, R] = 1/2 |q_mu|_F^2 + 1/2 M R log 2 pi -> out [1] double: the global
+ * regulariser of a GP layer without q_sqrt (temp_workaround.py:167-184), in place of KL[q(u) || p(u)].
+ * iwvi_sghmc_step: one launch updates every sampled tensor (at most IWVI_SGHMC_MAX_TENSORS).  Per element, every right-hand side reading the
+ * values from BEFORE the step, with grad = -`grad` (`grad` holds d bound / d theta as the adjoints leave it; the sampler descends -bound):
+ *   r = 1 / (xi + 1);  g' = (1 - r) g + r grad;  g2' = (1 - r) g2 + r grad^2;  xi' = 1 + xi (1 - g^2 / (g2 + 1e-16));
+ *   Minv = 1 / (sqrt(g2 + 1e-16) + 1e-16);  sigma = sqrt(max(2 (epsilon / sqrt(num_data))^2 mdecay Minv, 1e-16));
+ *   p' = p - epsilon^2 Minv grad - mdecay p + sigma n;  theta' = theta + p'.
+ * burn_in != 0 writes xi', g', g2' as well as p' and theta' (the reference's burn_in_op), burn_in == 0 writes p' and theta' only
+ * (sample_op).  Arithmetic in float64 without contraction; theta64 is the float64 master of theta (set it to theta once), `theta` receives
+ * its float32 rounding.  Noise n ~ N(0, 1): `noise` [n] float32 if given, else drawn from Philox4x32-10 + Box-Muller with key `seed` and the
+ * counter on the device, rng_state = {counter, arrival ticket} as for iwvi_fill_normal_dev (zero both once; launches sharing a state must
+ * not overlap in time).  The tensors WITHOUT injected noise share the counter in descriptor order: with c = the counter before the launch
+ * and o_i = the sum of ceil(n_j / 4) over the drawing tensors j < i, tensor i draws exactly what iwvi_fill_normal(out, n_i, seed, c + o_i)
+ * writes; the launch advances the counter by the sum over all drawing tensors, so a captured hipGraph draws fresh noise on every replay.
+ * `noise_out` [n] (optional) receives the n that was used.  rng_state may be NULL when every tensor has injected noise.
+ * IWVI_ERR_ARG (with iwvi_last_error) before any HIP call for a null pointer, n <= 0, a tensor count outside 1 .. IWVI_SGHMC_MAX_TENSORS,
+ * epsilon <= 0, mdecay < 0, num_data <= 0, a non-finite scalar, or a drawing tensor without rng_state. */
+#define IWVI_SGHMC_MAX_TENSORS 8
+typedef struct iwvi_sghmc_tensor {
+    float* theta; const float* grad; double* xi; double* g; double* g2; double* p; double* theta64;
+    const float* noise; float* noise_out; int64_t n;
+} iwvi_sghmc_tensor;
+int iwvi_sghmc_step(const iwvi_sghmc_tensor* tensors_host, int n_tensors, double epsilon, double mdecay, double num_data,
+                    int burn_in, uint64_t seed, uint64_t* rng_state, void* stream);
+int iwvi_neg_log_prior(const float* q_mu, int M, int R, double* out, void* stream);
+
 /* Diagnostic / development route switches (NOT part of the drop-in surface, like iwvi_debug_set_stamps): the library itself never reads
  * the environment.  name = one of the IWVI_* route names listed in csrc/abi.hip (e.g. "IWVI_BW_FUSED", "IWVI_NATGRAD_UNFUSED"),
  * value 0 = default route.  Returns 0, or IWVI_ERR_ARG for an unknown name.  Process-wide; not for concurrent use with launches. */

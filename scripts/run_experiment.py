@@ -3,6 +3,7 @@ on a synthetic conditional-density problem (no dataset files travel to the GPU b
 configuration string, train with the reference's train_op (NatGrad + Adam), evaluate the test log-likelihood by KDE.
 
     python scripts/run_experiment.py --configuration L1_G5 --mode IWAE --iterations 500
+    python scripts/run_experiment.py --configuration G5 --mode SGHMC --iterations 500      (the sampler + Adam on the hyperparameters)
 """
 import argparse
 import os
@@ -25,6 +26,30 @@ def bimodal_data(n, rng):
     return x, y
 
 
+def run_sghmc(ARGS, X, Y, Xs, Ys, dev):
+    """--mode SGHMC (reference run_conditional_density_estimation.py:128-156 with build_models.py:306-335): train with sghmc_step +
+    train_hypers, collect ``num_predict_samples`` posterior samples ``--sghmc_spacing`` sample ops apart, evaluate over them."""
+    model = build_models.build_sghmc_model(ARGS, X.astype(np.float32), Y.astype(np.float32), device=dev)
+    model.init_op()
+    t0 = time.perf_counter()
+    for it in range(ARGS.iterations):
+        elbo = model.train_op()
+        if it % max(1, ARGS.iterations // 10) == 0:
+            print("iteration %5d  bound %.2f" % (it, float(elbo)), flush=True)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    t1 = time.perf_counter()
+    samples = model.sghmc_optimizer.collect_samples(ARGS.num_predict_samples, ARGS.sghmc_spacing)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    res = evaluation.evaluate_sghmc(model, samples, Xs, Ys, ARGS.predict_batch_size)
+    res.update(train_seconds=dt, ms_per_iteration=dt / max(ARGS.iterations, 1) * 1e3, collect_seconds=t2 - t1,
+               evaluate_seconds=time.perf_counter() - t2)
+    res.update(ARGS.__dict__)
+    print(res)
+    return res
+
+
 def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--mode", default="IWAE")
@@ -44,6 +69,8 @@ def main(argv=None):
     p.add_argument("--n_train", type=int, default=2000)
     p.add_argument("--n_test", type=int, default=500)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--sghmc_spacing", type=int, default=5, help="--mode SGHMC: sample ops between two kept posterior samples")
+    p.add_argument("--use_graph", type=int, default=1, help="replay the ops of a step from captured graphs")
     p.add_argument("--device_eval", action="store_true", help="evaluate on the device: fused y-samples + iwvi_sample_stats (evaluate(on_device=True))")
     ARGS = p.parse_args(argv)
     ARGS.fix_linear = bool(ARGS.fix_linear)
@@ -54,6 +81,8 @@ def main(argv=None):
     mu, sd = Y.mean(), Y.std()
     Y, Ys = (Y - mu) / sd, (Ys - mu) / sd
     dev = torch.device("cuda:0")
+    if ARGS.mode == "SGHMC":
+        return run_sghmc(ARGS, X, Y, Xs, Ys, dev)
     model = build_models.build_model(ARGS, X.astype(np.float32), Y.astype(np.float32), device=dev)
     before = evaluation.evaluate(model, Xs, Ys, ARGS.num_predict_samples, ARGS.predict_batch_size)
     t0 = time.perf_counter()
