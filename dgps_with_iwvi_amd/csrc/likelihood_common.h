@@ -1,8 +1,11 @@
 // What csrc/likelihood_tail.hip, csrc/likelihood_multiclass.hip and csrc/likelihood_explink.hip share: the Gauss-Hermite tables, the
 // kernel-argument structs of the iwvi_lik_* entry points and the segment reductions (moved here verbatim from likelihood_tail.hip), the
-// point loop of iwvi_lik_predict_mixture for the types whose outputs are independent (mix_points), and the launchers of the multi-class and the exp-link kernels, which the entry points of likelihood_tail.hip call for IWVI_LIK_MULTICLASS and for
-// IWVI_LIK_POISSON / _EXPONENTIAL / _GAMMA.
+// point loop of iwvi_lik_predict_mixture for the types whose outputs are independent (mix_points), the bound's reduction and the heads of its
+// adjoint for every type (elbo_points, elbo_bwd_point: one core each over a small compile-time policy per family), the SEG and the mode
+// dispatch of the launchers, and the launchers of the multi-class and the exp-link kernels, which the entry points of likelihood_tail.hip
+// call for IWVI_LIK_MULTICLASS and for IWVI_LIK_POISSON / _EXPONENTIAL / _GAMMA.
 #pragma once
+#include <type_traits>
 #include "iwvi_common.h"
 
 namespace iwvi {
@@ -35,8 +38,8 @@ __device__ __forceinline__ float lseg_max(float v) {
     for (int o = SEG / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
 }
-template <int SEG>
-__device__ __forceinline__ double lseg_sum(double v) {
+template <int SEG, class T>
+__device__ __forceinline__ T lseg_sum(T v) {                  // float64 for the sums over samples, float32 for a point's constant
 #pragma unroll
     for (int o = SEG / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
@@ -44,13 +47,14 @@ __device__ __forceinline__ double lseg_sum(double v) {
 
 constexpr int LIK_THREADS = 256;
 
-// One chunk of a segment's running log-sum-exp (k_lik_elbo's own): L is the lane's term, -inf where the lane has none (on = false).  The shift is
+// One chunk of a segment's running log-sum-exp: L is the lane's term, -inf where the lane has none (on = false).  The shift is
 // the running float maximum, the sum float64.  A chunk whose every term is -inf adds nothing (no exp(-inf + inf)), and a lane set that calls
 // this with no term at all leaves (m, ssum) exactly as they were: nm = m, and exp(m - nm) = exp(0) = 1 exactly.
-template <int SEG>
+// GUARD = false is the bound's step (elbo_points): bit-equal while any term so far is finite; with every term at -inf it gives NaN, not -inf.
+template <int SEG, bool GUARD = true>
 __device__ __forceinline__ void lseg_lse_step(float L, bool on, float& m, double& ssum) {
     const float nm = fmaxf(m, lseg_max<SEG>(L));
-    const double cs = lseg_sum<SEG>(on && nm != -INFINITY ? (double)__expf(L - nm) : 0.0);
+    const double cs = lseg_sum<SEG>(on && (!GUARD || nm != -INFINITY) ? (double)__expf(L - nm) : 0.0);
     ssum = (m == -INFINITY ? 0.0 : ssum * (double)__expf(m - nm)) + cs;
     m = nm;
 }
@@ -124,8 +128,13 @@ __device__ __forceinline__ void mix_points(const LikMixArgs& g, const OPS& ops) 
     }
 }
 
+// the passes of LIK_THREADS / seg points that cover n points
+inline long long lik_passes(long long n, int seg) {
+    const long long ppp = LIK_THREADS / seg;
+    return (n + ppp - 1) / ppp;
+}
 inline unsigned mix_blocks(long long N, int seg) {
-    const long long ppp = LIK_THREADS / seg, passes = (N + ppp - 1) / ppp;
+    const long long passes = lik_passes(N, seg);
     return (unsigned)(passes < MIX_MAX_BLOCKS ? passes : MIX_MAX_BLOCKS);
 }
 
@@ -137,6 +146,185 @@ struct LikBwdArgs {
     const float* lse_global; int K_total;
     float* w; float* d_mean; float* d_var; double* part;   // part[0..B) = lse - log K, part[B..2B) = d param[0] share
 };
+
+// ------------------------------------------------------------------------------------------
+// The bound's reduction and the heads of its adjoint, ONE core each for every likelihood.  What differs between the families is a policy OPS
+// (LikQuadOps in likelihood_tail.hip, McOps in likelihood_multiclass.hip, XlOps in likelihood_explink.hip; no runtime branch on the type here):
+//   Point point<SEG, GRAD>(Y, b, live, sl)   a data point's state, formed once by the SEG lanes that own it: nothing (Gaussian, Bernoulli,
+//                                            Student-t), the clamped label (MultiClass), cb = sum_d c0(y_bd) in float32 (exp link; GRAD: also
+//                                            the point's part of d / d shape)
+//   HAS_CONST, point_const(pt)               whether the point carries a constant cb that stays OUTSIDE the log-sum-exp over the samples
+//   expect(pt, mu, var, Y, b)                one sample's expectation summed over its outputs, float32 (mu, var: the sample's row of moments)
+//   heads(pt, mu, var, Y, b, wt, dm, dv, ds) one sample's heads for its weight wt into dm / dv (its rows of d_mean / d_var; NULL: not asked
+//                                            for); returns the lane's float64 share ds of d param[0] with the sample's part added
+// ------------------------------------------------------------------------------------------
+// The last workgroup to arrive adds the published logp up in a fixed order: release / ticket / acquire, the only synchronisation between
+// workgroups in the likelihood files.  red: LIK_THREADS doubles of LDS, is_last: one LDS word.
+__device__ __forceinline__ void elbo_ticket_sum(const LikReduceArgs& g, double* red, int& is_last) {
+    if (!g.elbo) return;
+    const int tid = threadIdx.x;
+    // ---- publish this workgroup's logp, draw a ticket, the last arriver sums everything ----
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned long long t = __hip_atomic_fetch_add(g.ticket, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = (t == (unsigned long long)gridDim.x - 1);
+        if (last) {
+            __hip_atomic_store(g.ticket, 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next call
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        is_last = last;
+    }
+    __syncthreads();
+    if (!is_last) return;
+    double acc = 0.0;
+    for (long long b = tid; b < g.B; b += LIK_THREADS) acc += (double)g.logp[b];
+    red[tid] = acc;
+    __syncthreads();
+    for (int s2 = LIK_THREADS / 2; s2 > 0; s2 >>= 1) {
+        if (tid < s2) red[tid] += red[tid + s2];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double kl = 0.0;
+        for (int i = 0; i < g.n_glob; ++i)
+            for (int c = 0; c < g.klg_n[i]; ++c) kl += g.klg[i][c];
+        *g.elbo = red[0] * g.scale - kl;                                                              // models.py:150
+    }
+}
+
+// The reduction (csrc/lv_elbo.hip: k_elbo with the policy's expectation in place of the Gaussian closed form): SEG lanes per data point, one
+// lane per sample walking its outputs; float32 inside a sample, the log-sum-exp over K and the sum over the points in float64.  A workgroup
+// takes LIK_THREADS / SEG points per pass.  STRIDED: as many passes as the grid leaves it (k_xl_elbo, launched on up to XL_MAX_BLOCKS
+// workgroups); otherwise ONE pass, the launcher giving every pass a workgroup of its own (k_lik_elbo, k_mc_elbo).  The one-pass form is not
+// the loop run once: with the loop around the quadrature k_lik_elbo compiled to 106 VGPRs for 80 -- four waves on a SIMD for six -- and
+// k_mc_elbo to 111 for 108; without it both keep the resource rows they had (the time at configs[2] did not tell the two forms apart).
+// The measurements behind the two grids stand above those kernels.
+template <int SEG, bool STRIDED, class OPS>
+__device__ __forceinline__ void elbo_points(const LikReduceArgs& g, const OPS& ops) {
+    __shared__ double red[LIK_THREADS];
+    __shared__ int is_last;
+    const int tid = threadIdx.x, sl = tid % SEG, sg = tid / SEG;
+    constexpr int PPP = LIK_THREADS / SEG;           // points per pass
+    const int K = g.K, Dy = g.Dy;
+    auto pass = [&](long long b0) {                   // the PPP points from b0 on (b0: uniform in the workgroup)
+        const long long b = b0 + sg;
+        const bool live = b < g.B;                    // uniform within a segment
+        const auto pt = ops.template point<SEG, false>(g.Y, b, live, sl);
+        float m = -INFINITY;
+        double ssum = 0.0, lsum = 0.0;
+        for (int k0 = 0; k0 < K; k0 += SEG) {
+            const int k = k0 + sl;
+            const bool on = live && k < K;
+            float L = -INFINITY;
+            if (on) {
+                const long long t = b * g.stride_b + k * g.stride_k;
+                float acc = ops.expect(pt, g.fmean + t * Dy, g.fvar + t * Dy, g.Y, b);
+                for (int i = 0; i < g.n_kl; ++i)
+                    for (int d = 0; d < g.kl_dims[i]; ++d) acc -= g.kl[i][t * g.kl_dims[i] + d];
+                L = acc;
+            }
+            if (g.mode_vi) { lsum += lseg_sum<SEG>(on ? (double)L : 0.0); continue; }
+            lseg_lse_step<SEG, false>(L, on, m, ssum);
+        }
+        if (live && sl == 0) {
+            if (g.mode_vi) {
+                double lp = lsum / (double)K;                                                         // models.py:84
+                if constexpr (OPS::HAS_CONST) lp += (double)ops.point_const(pt);
+                if (g.logp) g.logp[b] = (float)lp;
+            } else {
+                if constexpr (OPS::HAS_CONST) m += ops.point_const(pt);                               // c0 outside the log-sum-exp
+                if (g.ms) { g.ms[2 * b] = m; g.ms[2 * b + 1] = (float)ssum; }
+                if (g.logp) g.logp[b] = (float)((double)m + log(ssum) - log((double)g.K_total));     // models.py:148
+            }
+        }
+    };
+    if constexpr (STRIDED) {
+        for (long long b0 = (long long)blockIdx.x * PPP; b0 < g.B; b0 += (long long)gridDim.x * PPP) pass(b0);
+    } else {
+        pass((long long)blockIdx.x * PPP);
+    }
+    elbo_ticket_sum(g, red, is_last);
+}
+
+// Heads of the bound's adjoint (csrc/backward.hip: k_elbo_bwd with the policy's expectation and heads): one wave per data point, lanes over
+// its K samples striding by 64.  Pass 1: L_nk (without the point's constant: it cancels in the weights) and the running (max, sum exp);
+// pass 2: the weights and the heads of every sample.
+template <class OPS>
+__device__ __forceinline__ void elbo_bwd_point(const LikBwdArgs& a, const OPS& ops) {
+    const int lane = threadIdx.x & 63;
+    const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= a.B) return;
+    const int Dy = a.Dy;
+    const auto pt = ops.template point<64, true>(a.Y, b, true, lane);
+    auto logw = [&](long long t) {
+        float l = ops.expect(pt, a.fmean + t * Dy, a.fvar + t * Dy, a.Y, b);
+        for (int i = 0; i < a.n_kl; ++i)
+            for (int q = 0; q < a.kl_dims[i]; ++q) l -= a.kl[i][t * a.kl_dims[i] + q];
+        return l;
+    };
+    const bool one = a.K <= 64;                          // every lane holds its only sample's L_nk: no second evaluation
+    float Lc = -INFINITY, mx = -INFINITY;
+    double se = 0.0;
+    if (a.mode_vi) {                                    // models.py:84: mean over the samples -> uniform weights
+        for (int k = lane; k < a.K; k += 64) se += (double)logw(b * a.K + k);
+        se = lseg_sum<64>(se);
+    } else {
+        for (int k = lane; k < a.K; k += 64) { Lc = logw(b * a.K + k); mx = fmaxf(mx, Lc); }
+        mx = lseg_max<64>(mx);
+        if (a.lse_global) {                             // weights against the whole job's normaliser, which carries the constant: exp(L - LSE)
+            mx = a.lse_global[b]; se = 1.0;
+            if constexpr (OPS::HAS_CONST) mx -= ops.point_const(pt);
+        } else {
+            for (int k = lane; k < a.K; k += 64) se += (double)__expf((one ? Lc : logw(b * a.K + k)) - mx);
+            se = lseg_sum<64>(se);
+        }
+    }
+    double ds = 0.0;
+    for (int k = lane; k < a.K; k += 64) {
+        const long long t = b * a.K + k;
+        float wt;
+        if (a.mode_vi) wt = (float)(a.scale / (double)a.K);
+        else wt = (float)(a.scale * (double)__expf((one ? Lc : logw(t)) - mx) / se);
+        if (a.w) a.w[t] = wt;
+        ds = ops.heads(pt, a.fmean + t * Dy, a.fvar + t * Dy, a.Y, b, wt, a.d_mean ? a.d_mean + t * Dy : nullptr,
+                       a.d_var ? a.d_var + t * Dy : nullptr, ds);
+    }
+    ds = lseg_sum<64>(ds);
+    if (lane == 0) {
+        double lp = a.mode_vi ? se / (double)a.K : (double)mx + log(se) - log((double)(a.lse_global ? a.K_total : a.K));
+        if constexpr (OPS::HAS_CONST) lp = (double)ops.point_const(pt) + lp;
+        a.part[b] = lp;
+        a.part[a.B + b] = ds;
+    }
+}
+
+// K (the reductions) or S (the mixtures) -> the narrowest segment that gives every sample a lane: f(integral_constant<int, SEG>)
+template <class F>
+inline int seg_dispatch(int n, F&& f) {
+    if (n <= 4) return f(std::integral_constant<int, 4>{});
+    if (n <= 8) return f(std::integral_constant<int, 8>{});
+    if (n <= 16) return f(std::integral_constant<int, 16>{});
+    if (n <= 32) return f(std::integral_constant<int, 32>{});
+    return f(std::integral_constant<int, 64>{});
+}
+
+// the elementwise kernels' grid: n elements, 256 a workgroup, grid-strided beyond 4096 workgroups
+inline int elem_blocks(long long n) { return (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096); }
+
+// the elementwise kernels' launch where the mode is a runtime value (the launchers of the multi-class and the exp-link files; lik_elementwise
+// of likelihood_tail.hip knows its MODE at compile time and launches directly): launch(integral_constant<int, MODE>, blocks)
+template <class F>
+inline int launch_elem_mode(const char* what, int mode, long long n, F&& launch) {
+    const int blocks = elem_blocks(n);
+    if (mode == 0) launch(std::integral_constant<int, 0>{}, blocks);
+    else if (mode == 1) launch(std::integral_constant<int, 1>{}, blocks);
+    else launch(std::integral_constant<int, 2>{}, blocks);
+    return check_launch(what);
+}
 
 // ---- csrc/likelihood_multiclass.hip (IWVI_LIK_MULTICLASS: lik.p0 = epsilon, lik.p1 = Dy = the number of classes, Y one column of labels) ----
 int mc_launch_elbo(const LikReduceArgs& g, hipStream_t stream);                   // k_mc_elbo<SEG>

@@ -68,171 +68,68 @@ __device__ __forceinline__ float xl_c0(const XlPar& P, float y, float& logy) {
     return 0.f;
 }
 
-template <int SEG>
-__device__ __forceinline__ float xl_seg_sum(float v) {
-#pragma unroll
-    for (int o = SEG / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // ------------------------------------------------------------------------------------------
-// The reduction: k_lik_elbo's contracts (ms / logp / elbo, the release / ticket / acquire epilogue).  SEG lanes per data point, one lane per
-// sample walking its Dy outputs; float32 inside a sample, the log-sum-exp over K and the sum over the points in float64.  A workgroup takes
-// LIK_THREADS / SEG points per pass and as many passes as the grid leaves it: the launcher spreads the points over up to XL_MAX_BLOCKS
-// workgroups, ONE pass each at B = 1024.  (k_elbo's 64 points per workgroup -- csrc/lv_elbo.hip -- were tried first, a sample being a handful
+// The bound's reduction and the heads of its adjoint: the cores of likelihood_common.h over the closed forms.  A point's state is its
+// constant cb = sum_d c0(y_bd), formed once by the lanes that own the point (over its outputs, float32) and added outside the log-sum-exp;
+// for the heads also sum_d (log y_d - psi(a)), the point's part of d / d shape.  With lse_global the core takes the constant off the job's
+// normaliser (the local L_nk do not carry it) and adds it back in part[b].
+// part[B..2B): the share of d / d shape (Gamma), sum_k w_k sum_d (-mu_kd - psi(a) + log y_d); 0 for the other two.
+// ------------------------------------------------------------------------------------------
+struct XlOps {
+    static constexpr bool HAS_CONST = true;
+    struct Point { float cb; double dpar0; };
+    const XlPar& P; int Dy;
+    template <int SEG, bool GRAD>
+    __device__ __forceinline__ Point point(const float* Y, long long b, bool live, int sl) const {
+        float cb = 0.f, lyb = 0.f;
+        if (live && P.type != IWVI_LIK_EXPONENTIAL)
+            for (int d = sl; d < Dy; d += SEG) { float ly; cb += xl_c0(P, Y[b * Dy + d], ly); lyb += ly; }
+        cb = lseg_sum<SEG>(cb);
+        if (!GRAD) return {cb, 0.0};
+        lyb = lseg_sum<SEG>(lyb);
+        return {cb, (double)lyb - (double)Dy * P.psi};          // sum_d (log y_d - psi(a))
+    }
+    __device__ __forceinline__ float point_const(const Point& pt) const { return pt.cb; }
+    __device__ __forceinline__ float expect(const Point&, const float* mu, const float* var, const float* Y, long long b) const {
+        float acc = 0.f, e;
+        for (int d = 0; d < Dy; ++d) acc += xl_g(P, Y[b * Dy + d], mu[d], 0.5f * var[d], e);
+        return acc;
+    }
+    __device__ __forceinline__ double heads(const Point& pt, const float* mu, const float* var, const float* Y, long long b, float wt,
+                                            float* dm, float* dv, double ds) const {
+        const bool pois = P.type == IWVI_LIK_POISSON;
+        double smu = 0.0;
+        for (int j = 0; j < Dy; ++j) {
+            const float y = Y[b * Dy + j];
+            float e;
+            xl_g(P, y, mu[j], 0.5f * var[j], e);
+            const float ce = (pois ? P.beta : y) * e;
+            if (dm) dm[j] = wt * fmaf(-P.sg, ce, pois ? y : P.cmu);
+            if (dv) dv[j] = wt * (-0.5f * ce);
+            smu += (double)mu[j];
+        }
+        return P.type == IWVI_LIK_GAMMA ? ds + (double)wt * (pt.dpar0 - smu) : ds;
+    }
+};
+
+// A workgroup takes as many passes as the grid leaves it: the launcher spreads the points over up to XL_MAX_BLOCKS workgroups, ONE pass each
+// at B = 1024.  (k_elbo's 64 points per workgroup -- csrc/lv_elbo.hip -- were tried first, a sample being a handful
 // of FMAs and one exp: 16 workgroups at configs[2], and an evaluation took 74.5-79.0 us against the Student-t's 68.3 in the same session.  The
 // per-sample work is small, but a pass is a chain of dependent loads and cross-lane reductions, and eight of them in a row on 16 of 256 CUs
 // is what the time went into -- the finding of DESIGN.md section 6 for k_lik_elbo, again.)
-// ------------------------------------------------------------------------------------------
 constexpr int XL_MAX_BLOCKS = 1024;     // four workgroups per CU
 
 template <int SEG>
 __global__ __launch_bounds__(LIK_THREADS) void k_xl_elbo(LikReduceArgs g) {
-    __shared__ double red[LIK_THREADS];
-    __shared__ int is_last;
-    const int tid = threadIdx.x, sl = tid % SEG, sg = tid / SEG;
-    constexpr int PPP = LIK_THREADS / SEG;           // points per pass
-    const int K = g.K, Dy = g.Dy;
     const XlPar P = xl_par<true, false>(g.lik);
-    for (long long b0 = (long long)blockIdx.x * PPP; b0 < g.B; b0 += (long long)gridDim.x * PPP) {   // (uniform in the workgroup)
-        const long long b = b0 + sg;
-        const bool live = b < g.B;                    // uniform within a segment
-        // sum_d c0(y_bd): once per point, the segment's lanes over the outputs
-        float cb = 0.f;
-        if (live && P.type != IWVI_LIK_EXPONENTIAL)
-            for (int d = sl; d < Dy; d += SEG) { float ly; cb += xl_c0(P, g.Y[b * Dy + d], ly); }
-        cb = xl_seg_sum<SEG>(cb);
-        float m = -INFINITY;
-        double ssum = 0.0, lsum = 0.0;
-        for (int k0 = 0; k0 < K; k0 += SEG) {
-            const int k = k0 + sl;
-            const bool on = live && k < K;
-            float L = -INFINITY;
-            if (on) {
-                const long long t = b * g.stride_b + k * g.stride_k;
-                float acc = 0.f, e;
-                for (int d = 0; d < Dy; ++d)
-                    acc += xl_g(P, g.Y[b * Dy + d], g.fmean[t * Dy + d], 0.5f * g.fvar[t * Dy + d], e);
-                for (int i = 0; i < g.n_kl; ++i)
-                    for (int d = 0; d < g.kl_dims[i]; ++d) acc -= g.kl[i][t * g.kl_dims[i] + d];
-                L = acc;
-            }
-            if (g.mode_vi) { lsum += lseg_sum<SEG>(on ? (double)L : 0.0); continue; }
-            const float nm = fmaxf(m, lseg_max<SEG>(L));
-            const double cs = lseg_sum<SEG>(on ? (double)__expf(L - nm) : 0.0);
-            ssum = (m == -INFINITY ? 0.0 : ssum * (double)__expf(m - nm)) + cs;
-            m = nm;
-        }
-        if (live && sl == 0) {
-            if (g.mode_vi) {
-                if (g.logp) g.logp[b] = (float)(lsum / (double)K + (double)cb);                      // models.py:84
-            } else {
-                m += cb;                                                                              // c0 outside the log-sum-exp
-                if (g.ms) { g.ms[2 * b] = m; g.ms[2 * b + 1] = (float)ssum; }
-                if (g.logp) g.logp[b] = (float)((double)m + log(ssum) - log((double)g.K_total));     // models.py:148
-            }
-        }
-    }
-    if (!g.elbo) return;
-    // ---- publish this workgroup's logp, draw a ticket, the last arriver sums everything ----
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long t = __hip_atomic_fetch_add(g.ticket, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = (t == (unsigned long long)gridDim.x - 1);
-        if (last) {
-            __hip_atomic_store(g.ticket, 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next call
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        is_last = last;
-    }
-    __syncthreads();
-    if (!is_last) return;
-    double acc = 0.0;
-    for (long long b = tid; b < g.B; b += LIK_THREADS) acc += (double)g.logp[b];
-    red[tid] = acc;
-    __syncthreads();
-    for (int s2 = LIK_THREADS / 2; s2 > 0; s2 >>= 1) {
-        if (tid < s2) red[tid] += red[tid + s2];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        double kl = 0.0;
-        for (int i = 0; i < g.n_glob; ++i)
-            for (int c = 0; c < g.klg_n[i]; ++c) kl += g.klg[i][c];
-        *g.elbo = red[0] * g.scale - kl;                                                              // models.py:150
-    }
+    const XlOps ops{P, g.Dy};
+    elbo_points<SEG, true>(g, ops);
 }
 
-// ------------------------------------------------------------------------------------------
-// Heads of the bound's adjoint: k_lik_elbo_bwd with the closed forms.  One wave per data point, lanes over its K samples striding by 64.
-// Pass 1: L_nk (without the point's constant: it cancels in the weights) and the running (max, sum exp); pass 2: the weights and the heads.
-// part[B..2B): the share of d / d shape (Gamma), sum_k w_k sum_d (-mu_kd - psi(a) + log y_d); 0 for the other two.
-// ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_xl_elbo_bwd(LikBwdArgs a) {
-    const int lane = threadIdx.x & 63;
-    const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (b >= a.B) return;
     const XlPar P = xl_par<true, true>(a.lik);
-    const bool gam = P.type == IWVI_LIK_GAMMA;
-    // once per point: sum_d c0(y_d) and (Gamma) sum_d log y_d, the lanes over the outputs
-    float cb = 0.f, lyb = 0.f;
-    if (P.type != IWVI_LIK_EXPONENTIAL)
-        for (int j = lane; j < a.Dy; j += 64) { float ly; cb += xl_c0(P, a.Y[b * a.Dy + j], ly); lyb += ly; }
-    for (int o = 32; o > 0; o >>= 1) { cb += __shfl_xor(cb, o, 64); lyb += __shfl_xor(lyb, o, 64); }
-    auto logw = [&](long long t) {
-        float l = 0.f, e;
-        for (int j = 0; j < a.Dy; ++j)
-            l += xl_g(P, a.Y[b * a.Dy + j], a.fmean[t * a.Dy + j], 0.5f * a.fvar[t * a.Dy + j], e);
-        for (int i = 0; i < a.n_kl; ++i)
-            for (int q = 0; q < a.kl_dims[i]; ++q) l -= a.kl[i][t * a.kl_dims[i] + q];
-        return l;
-    };
-    const bool one = a.K <= 64;                          // every lane holds its only sample's L_nk: no second evaluation
-    float Lc = -INFINITY, mx = -INFINITY;
-    double se = 0.0;
-    if (a.mode_vi) {                                    // models.py:84: mean over the samples -> uniform weights
-        for (int k = lane; k < a.K; k += 64) se += (double)logw(b * a.K + k);
-        for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
-    } else {
-        for (int k = lane; k < a.K; k += 64) { Lc = logw(b * a.K + k); mx = fmaxf(mx, Lc); }
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        if (a.lse_global) {                             // weights against the whole job's normaliser, which carries the constant
-            mx = a.lse_global[b] - cb; se = 1.0;
-        } else {
-            for (int k = lane; k < a.K; k += 64) se += (double)__expf((one ? Lc : logw(b * a.K + k)) - mx);
-            for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
-        }
-    }
-    const double dpar0 = (double)lyb - (double)a.Dy * P.psi;     // sum_d (log y_d - psi(a))
-    double ds = 0.0;
-    for (int k = lane; k < a.K; k += 64) {
-        const long long t = b * a.K + k;
-        float wt;
-        if (a.mode_vi) wt = (float)(a.scale / (double)a.K);
-        else wt = (float)(a.scale * (double)__expf((one ? Lc : logw(t)) - mx) / se);
-        if (a.w) a.w[t] = wt;
-        double smu = 0.0;
-        for (int j = 0; j < a.Dy; ++j) {
-            const float y = a.Y[b * a.Dy + j], mu = a.fmean[t * a.Dy + j];
-            float e;
-            xl_g(P, y, mu, 0.5f * a.fvar[t * a.Dy + j], e);
-            const bool pois = P.type == IWVI_LIK_POISSON;
-            const float ce = (pois ? P.beta : y) * e;
-            if (a.d_mean) a.d_mean[t * a.Dy + j] = wt * fmaf(-P.sg, ce, pois ? y : P.cmu);
-            if (a.d_var) a.d_var[t * a.Dy + j] = wt * (-0.5f * ce);
-            smu += (double)mu;
-        }
-        if (gam) ds += (double)wt * (dpar0 - smu);
-    }
-    for (int o = 32; o > 0; o >>= 1) ds += __shfl_xor(ds, o, 64);
-    if (lane == 0) {
-        a.part[b] = (double)cb + (a.mode_vi ? se / (double)a.K : (double)mx + log(se) - log((double)(a.lse_global ? a.K_total : a.K)));
-        a.part[a.B + b] = ds;
-    }
+    const XlOps ops{P, a.Dy};
+    elbo_bwd_point(a, ops);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -321,35 +218,21 @@ __global__ __launch_bounds__(LIK_THREADS) void k_xl_mix(LikMixArgs g) {
     mix_points<SEG>(g, ops);
 }
 
-template <int SEG>
-static int launch_xl_elbo(const LikReduceArgs& g, hipStream_t stream) {
-    constexpr int PPP = LIK_THREADS / SEG;
-    const long long passes = (g.B + PPP - 1) / PPP;
-    const long long blocks = passes < XL_MAX_BLOCKS ? passes : XL_MAX_BLOCKS;
-    hipLaunchKernelGGL(k_xl_elbo<SEG>, dim3((unsigned)blocks), dim3(LIK_THREADS), 0, stream, g);
-    return check_launch("k_xl_elbo");
-}
-
 int xl_launch_elbo(const LikReduceArgs& g, hipStream_t stream) {
-    if (g.K <= 4) return launch_xl_elbo<4>(g, stream);
-    if (g.K <= 8) return launch_xl_elbo<8>(g, stream);
-    if (g.K <= 16) return launch_xl_elbo<16>(g, stream);
-    if (g.K <= 32) return launch_xl_elbo<32>(g, stream);
-    return launch_xl_elbo<64>(g, stream);
-}
-
-template <int SEG>
-static int launch_xl_mix(const LikMixArgs& g, hipStream_t stream) {
-    hipLaunchKernelGGL(k_xl_mix<SEG>, dim3(mix_blocks(g.N, SEG)), dim3(LIK_THREADS), 0, stream, g);
-    return check_launch("k_xl_mix");
+    return seg_dispatch(g.K, [&](auto seg) {
+        constexpr int SEG = decltype(seg)::value;
+        const long long passes = lik_passes(g.B, SEG);
+        hipLaunchKernelGGL(k_xl_elbo<SEG>, dim3((unsigned)(passes < XL_MAX_BLOCKS ? passes : XL_MAX_BLOCKS)), dim3(LIK_THREADS), 0, stream, g);
+        return check_launch("k_xl_elbo");
+    });
 }
 
 int xl_launch_mix(const LikMixArgs& g, hipStream_t stream) {
-    if (g.S <= 4) return launch_xl_mix<4>(g, stream);
-    if (g.S <= 8) return launch_xl_mix<8>(g, stream);
-    if (g.S <= 16) return launch_xl_mix<16>(g, stream);
-    if (g.S <= 32) return launch_xl_mix<32>(g, stream);
-    return launch_xl_mix<64>(g, stream);
+    return seg_dispatch(g.S, [&](auto seg) {
+        constexpr int SEG = decltype(seg)::value;
+        hipLaunchKernelGGL(k_xl_mix<SEG>, dim3(mix_blocks(g.N, SEG)), dim3(LIK_THREADS), 0, stream, g);
+        return check_launch("k_xl_mix");
+    });
 }
 
 int xl_launch_elbo_bwd(const LikBwdArgs& a, hipStream_t stream) {
@@ -360,11 +243,9 @@ int xl_launch_elbo_bwd(const LikBwdArgs& a, hipStream_t stream) {
 int xl_launch_elem(const char* what, int mode, const Lik& L, const float* Fmu, const float* Fvar, const float* Y, long long T, int Dy,
                    long long row_div, long long row_mod, float* out, float* out2, hipStream_t stream) {
     const long long n = T * Dy;
-    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    if (mode == 0) hipLaunchKernelGGL(k_xl_elem<0>, dim3(blocks), dim3(256), 0, stream, L, Fmu, Fvar, Y, n, Dy, row_div, row_mod, out, out2);
-    else if (mode == 1) hipLaunchKernelGGL(k_xl_elem<1>, dim3(blocks), dim3(256), 0, stream, L, Fmu, Fvar, Y, n, Dy, row_div, row_mod, out, out2);
-    else hipLaunchKernelGGL(k_xl_elem<2>, dim3(blocks), dim3(256), 0, stream, L, Fmu, Fvar, Y, n, Dy, row_div, row_mod, out, out2);
-    return check_launch(what);
+    return launch_elem_mode(what, mode, n, [&](auto m, int blocks) {
+        hipLaunchKernelGGL(k_xl_elem<decltype(m)::value>, dim3(blocks), dim3(256), 0, stream, L, Fmu, Fvar, Y, n, Dy, row_div, row_mod, out, out2);
+    });
 }
 
 }  // namespace iwvi

@@ -88,136 +88,36 @@ __device__ __forceinline__ void mc_heads(const float* __restrict__ mu, const flo
 }
 
 // ------------------------------------------------------------------------------------------
-// The reduction: k_lik_elbo (csrc/likelihood_tail.hip) with the coupled expectation in place of the per-output quadrature.  SEG lanes per
-// data point, one lane per sample; float32 inside a sample, the log-sum-exp over K and the sum over the points in float64; the same
-// release / ticket / acquire epilogue.
+// The bound's reduction and the heads of its adjoint: the cores of likelihood_common.h over the coupled expectation.  A point's state is its
+// clamped label; a sample has 2 C heads, skipped when neither array is asked for.  There is no trained parameter: part[B..2B) = 0.
 // ------------------------------------------------------------------------------------------
+struct McOps {
+    static constexpr bool HAS_CONST = false;
+    struct Point { int y; };
+    int C; float l0, l1;
+    __device__ __forceinline__ McOps(const Lik& L, int C_) : C(C_) { mc_logs(L, C, l0, l1); }
+    template <int SEG, bool GRAD>
+    __device__ __forceinline__ Point point(const float* Y, long long b, bool live, int) const { return {live ? mc_label(Y[b], C) : 0}; }
+    __device__ __forceinline__ float expect(const Point& pt, const float* mu, const float* var, const float*, long long) const {
+        float pa[10], pb[10], a;
+        return mc_ve(mc_prob(mu, var, C, pt.y, pa, pb, a), l0, l1);
+    }
+    __device__ __forceinline__ double heads(const Point& pt, const float* mu, const float* var, const float*, long long, float wt,
+                                            float* dm, float* dv, double ds) const {
+        if (dm || dv) mc_heads(mu, var, C, pt.y, wt * (l1 - l0), dm, dv);
+        return ds;
+    }
+};
+
 template <int SEG>
 __global__ __launch_bounds__(LIK_THREADS) void k_mc_elbo(LikReduceArgs g) {
-    __shared__ double red[LIK_THREADS];
-    __shared__ int is_last;
-    const int tid = threadIdx.x, sl = tid % SEG, sg = tid / SEG;
-    constexpr int PPP = LIK_THREADS / SEG;
-    const int K = g.K, C = g.Dy;
-    float l0, l1;
-    mc_logs(g.lik, C, l0, l1);
-    {
-        const long long b = (long long)blockIdx.x * PPP + sg;
-        const bool live = b < g.B;                    // uniform within a segment
-        const int y = live ? mc_label(g.Y[b], C) : 0;
-        float m = -INFINITY;
-        double ssum = 0.0, lsum = 0.0;
-        for (int k0 = 0; k0 < K; k0 += SEG) {
-            const int k = k0 + sl;
-            const bool on = live && k < K;
-            float L = -INFINITY;
-            if (on) {
-                const long long t = b * g.stride_b + k * g.stride_k;
-                float pa[10], pb[10], a;
-                float acc = mc_ve(mc_prob(g.fmean + t * C, g.fvar + t * C, C, y, pa, pb, a), l0, l1);
-                for (int i = 0; i < g.n_kl; ++i)
-                    for (int d = 0; d < g.kl_dims[i]; ++d) acc -= g.kl[i][t * g.kl_dims[i] + d];
-                L = acc;
-            }
-            if (g.mode_vi) { lsum += lseg_sum<SEG>(on ? (double)L : 0.0); continue; }
-            const float nm = fmaxf(m, lseg_max<SEG>(L));
-            const double cs = lseg_sum<SEG>(on ? (double)__expf(L - nm) : 0.0);
-            ssum = (m == -INFINITY ? 0.0 : ssum * (double)__expf(m - nm)) + cs;
-            m = nm;
-        }
-        if (live && sl == 0) {
-            if (g.mode_vi) {
-                if (g.logp) g.logp[b] = (float)(lsum / (double)K);                                   // models.py:84
-            } else {
-                if (g.ms) { g.ms[2 * b] = m; g.ms[2 * b + 1] = (float)ssum; }
-                if (g.logp) g.logp[b] = (float)((double)m + log(ssum) - log((double)g.K_total));     // models.py:148
-            }
-        }
-    }
-    if (!g.elbo) return;
-    // ---- publish this workgroup's logp, draw a ticket, the last arriver sums everything ----
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long t = __hip_atomic_fetch_add(g.ticket, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = (t == (unsigned long long)gridDim.x - 1);
-        if (last) {
-            __hip_atomic_store(g.ticket, 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next call
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        is_last = last;
-    }
-    __syncthreads();
-    if (!is_last) return;
-    double acc = 0.0;
-    for (long long b = tid; b < g.B; b += LIK_THREADS) acc += (double)g.logp[b];
-    red[tid] = acc;
-    __syncthreads();
-    for (int s2 = LIK_THREADS / 2; s2 > 0; s2 >>= 1) {
-        if (tid < s2) red[tid] += red[tid + s2];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        double kl = 0.0;
-        for (int i = 0; i < g.n_glob; ++i)
-            for (int c = 0; c < g.klg_n[i]; ++c) kl += g.klg[i][c];
-        *g.elbo = red[0] * g.scale - kl;                                                              // models.py:150
-    }
+    const McOps ops(g.lik, g.Dy);
+    elbo_points<SEG, false>(g, ops);
 }
 
-// ------------------------------------------------------------------------------------------
-// Heads of the bound's adjoint: k_lik_elbo_bwd with the coupled expectation.  One wave per data point, lanes over its K samples striding
-// by 64.  Pass 1: L_nk and the running (max, sum exp); pass 2: the weights and the 2 C heads of every sample.  There is no trained
-// parameter: part[B..2B) = 0.
-// ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_mc_elbo_bwd(LikBwdArgs a) {
-    const int lane = threadIdx.x & 63;
-    const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (b >= a.B) return;
-    const int C = a.Dy;
-    const int y = mc_label(a.Y[b], C);
-    float l0, l1;
-    mc_logs(a.lik, C, l0, l1);
-    const float dl = l1 - l0;
-    auto logw = [&](long long t) {
-        float pa[10], pb[10], aa;
-        float l = mc_ve(mc_prob(a.fmean + t * C, a.fvar + t * C, C, y, pa, pb, aa), l0, l1);
-        for (int i = 0; i < a.n_kl; ++i)
-            for (int q = 0; q < a.kl_dims[i]; ++q) l -= a.kl[i][t * a.kl_dims[i] + q];
-        return l;
-    };
-    const bool one = a.K <= 64;                          // every lane holds its only sample's L_nk: no second evaluation
-    float Lc = -INFINITY, mx = -INFINITY;
-    double se = 0.0;
-    if (a.mode_vi) {                                    // models.py:84: mean over the samples -> uniform weights
-        for (int k = lane; k < a.K; k += 64) se += (double)logw(b * a.K + k);
-        for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
-    } else {
-        for (int k = lane; k < a.K; k += 64) { Lc = logw(b * a.K + k); mx = fmaxf(mx, Lc); }
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        if (a.lse_global) {                             // weights against the whole job's normaliser: exp(L - LSE)
-            mx = a.lse_global[b]; se = 1.0;
-        } else {
-            for (int k = lane; k < a.K; k += 64) se += (double)__expf((one ? Lc : logw(b * a.K + k)) - mx);
-            for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
-        }
-    }
-    for (int k = lane; k < a.K; k += 64) {
-        const long long t = b * a.K + k;
-        float wt;
-        if (a.mode_vi) wt = (float)(a.scale / (double)a.K);
-        else wt = (float)(a.scale * (double)__expf((one ? Lc : logw(t)) - mx) / se);
-        if (a.w) a.w[t] = wt;
-        if (a.d_mean || a.d_var)
-            mc_heads(a.fmean + t * C, a.fvar + t * C, C, y, wt * dl, a.d_mean ? a.d_mean + t * C : nullptr, a.d_var ? a.d_var + t * C : nullptr);
-    }
-    if (lane == 0) {
-        a.part[b] = a.mode_vi ? se / (double)a.K : (double)mx + log(se) - log((double)(a.lse_global ? a.K_total : a.K));
-        a.part[a.B + b] = 0.0;
-    }
+    const McOps ops(a.lik, a.Dy);
+    elbo_bwd_point(a, ops);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -312,34 +212,20 @@ __global__ __launch_bounds__(LIK_THREADS) void k_mc_mix(LikMixArgs g) {
     }
 }
 
-template <int SEG>
-static int launch_mc_elbo(const LikReduceArgs& g, hipStream_t stream) {
-    constexpr int PPP = LIK_THREADS / SEG;
-    const long long blocks = (g.B + PPP - 1) / PPP;
-    hipLaunchKernelGGL(k_mc_elbo<SEG>, dim3((unsigned)blocks), dim3(LIK_THREADS), 0, stream, g);
-    return check_launch("k_mc_elbo");
-}
-
 int mc_launch_elbo(const LikReduceArgs& g, hipStream_t stream) {
-    if (g.K <= 4) return launch_mc_elbo<4>(g, stream);
-    if (g.K <= 8) return launch_mc_elbo<8>(g, stream);
-    if (g.K <= 16) return launch_mc_elbo<16>(g, stream);
-    if (g.K <= 32) return launch_mc_elbo<32>(g, stream);
-    return launch_mc_elbo<64>(g, stream);
-}
-
-template <int SEG>
-static int launch_mc_mix(const LikMixArgs& g, hipStream_t stream) {
-    hipLaunchKernelGGL(k_mc_mix<SEG>, dim3(mix_blocks(g.N, SEG)), dim3(LIK_THREADS), 0, stream, g);
-    return check_launch("k_mc_mix");
+    return seg_dispatch(g.K, [&](auto seg) {
+        constexpr int SEG = decltype(seg)::value;
+        hipLaunchKernelGGL(k_mc_elbo<SEG>, dim3((unsigned)lik_passes(g.B, SEG)), dim3(LIK_THREADS), 0, stream, g);
+        return check_launch("k_mc_elbo");
+    });
 }
 
 int mc_launch_mix(const LikMixArgs& g, hipStream_t stream) {
-    if (g.S <= 4) return launch_mc_mix<4>(g, stream);
-    if (g.S <= 8) return launch_mc_mix<8>(g, stream);
-    if (g.S <= 16) return launch_mc_mix<16>(g, stream);
-    if (g.S <= 32) return launch_mc_mix<32>(g, stream);
-    return launch_mc_mix<64>(g, stream);
+    return seg_dispatch(g.S, [&](auto seg) {
+        constexpr int SEG = decltype(seg)::value;
+        hipLaunchKernelGGL(k_mc_mix<SEG>, dim3(mix_blocks(g.N, SEG)), dim3(LIK_THREADS), 0, stream, g);
+        return check_launch("k_mc_mix");
+    });
 }
 
 int mc_launch_elbo_bwd(const LikBwdArgs& a, hipStream_t stream) {
@@ -350,11 +236,9 @@ int mc_launch_elbo_bwd(const LikBwdArgs& a, hipStream_t stream) {
 int mc_launch_elem(const char* what, int mode, const Lik& L, const float* Fmu, const float* Fvar, const float* Y, long long T, int C,
                    long long row_div, long long row_mod, float* out, float* out2, hipStream_t stream) {
     const long long n = mode == 2 ? T * C : T;
-    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    if (mode == 0) hipLaunchKernelGGL(k_mc_elem<0>, dim3(blocks), dim3(256), 0, stream, L, Fmu, Fvar, Y, n, C, row_div, row_mod, out, out2);
-    else if (mode == 1) hipLaunchKernelGGL(k_mc_elem<1>, dim3(blocks), dim3(256), 0, stream, L, Fmu, Fvar, Y, n, C, row_div, row_mod, out, out2);
-    else hipLaunchKernelGGL(k_mc_elem<2>, dim3(blocks), dim3(256), 0, stream, L, Fmu, Fvar, Y, n, C, row_div, row_mod, out, out2);
-    return check_launch(what);
+    return launch_elem_mode(what, mode, n, [&](auto m, int blocks) {
+        hipLaunchKernelGGL(k_mc_elem<decltype(m)::value>, dim3(blocks), dim3(256), 0, stream, L, Fmu, Fvar, Y, n, C, row_div, row_mod, out, out2);
+    });
 }
 
 }  // namespace iwvi

@@ -70,92 +70,35 @@ __device__ __forceinline__ float lik_quad(const Lik& L, float p0, float mu, floa
 }
 
 // ------------------------------------------------------------------------------------------
-// The reduction (csrc/lv_elbo.hip: k_elbo with the quadrature in place of the Gaussian closed form): SEG lanes per data point, one lane
-// per sample walking its Dy outputs; float32 inside a sample, the log-sum-exp over K and the sum over the points in float64; the last
-// workgroup to arrive (agent-scope release / ticket / acquire) adds the points up in a fixed order.
+// The bound's reduction and the heads of its adjoint: the cores of likelihood_common.h (elbo_points, elbo_bwd_point) over the quadrature,
+// one output at a time (the reduction; the heads kernel keeps a body of its own, below).  A point has no state of its own.
 // ------------------------------------------------------------------------------------------
+struct LikQuadOps {
+    static constexpr bool HAS_CONST = false;
+    struct Point {};
+    const Lik& L; float p0; int Dy;
+    template <int SEG, bool GRAD>
+    __device__ __forceinline__ Point point(const float*, long long, bool, int) const { return {}; }
+    __device__ __forceinline__ float expect(const Point&, const float* mu, const float* var, const float* Y, long long b) const {
+        float acc = 0.f, d0, d1, d2;
+        for (int d = 0; d < Dy; ++d) acc += lik_quad<false>(L, p0, mu[d], var[d], Y[b * Dy + d], d0, d1, d2);
+        return acc;
+    }
+};
+
 // A workgroup takes ONE pass of LIK_THREADS / SEG points (k_elbo takes 64 points in several passes: its per-sample work is a handful of
 // FMAs; here a sample costs 20 x Dy evaluations of erfc / log, and 64 points per workgroup left configs[2] -- B = 1024 -- on 16 of the
 // chip's 256 CUs: a Bernoulli evaluation took 101.6 us against 66.0 with the points spread -- profiles/likelihood_tail_time.json)
 template <int SEG>
 __global__ __launch_bounds__(LIK_THREADS) void k_lik_elbo(LikReduceArgs g) {
-    __shared__ double red[LIK_THREADS];
-    __shared__ int is_last;
-    const int tid = threadIdx.x, sl = tid % SEG, sg = tid / SEG;
-    constexpr int PPP = LIK_THREADS / SEG;
-    const int K = g.K, Dy = g.Dy;
-    const float p0 = g.lik.p0_dev ? *g.lik.p0_dev : g.lik.p0;
-    {
-        const long long b = (long long)blockIdx.x * PPP + sg;
-        const bool live = b < g.B;                    // uniform within a segment
-        float m = -INFINITY;
-        double ssum = 0.0, lsum = 0.0;
-        for (int k0 = 0; k0 < K; k0 += SEG) {
-            const int k = k0 + sl;
-            const bool on = live && k < K;
-            float L = -INFINITY;
-            if (on) {
-                const long long t = b * g.stride_b + k * g.stride_k;
-                float acc = 0.f, d0, d1, d2;
-                for (int d = 0; d < Dy; ++d)
-                    acc += lik_quad<false>(g.lik, p0, g.fmean[t * Dy + d], g.fvar[t * Dy + d], g.Y[b * Dy + d], d0, d1, d2);
-                for (int i = 0; i < g.n_kl; ++i)
-                    for (int d = 0; d < g.kl_dims[i]; ++d) acc -= g.kl[i][t * g.kl_dims[i] + d];
-                L = acc;
-            }
-            if (g.mode_vi) { lsum += lseg_sum<SEG>(on ? (double)L : 0.0); continue; }
-            const float nm = fmaxf(m, lseg_max<SEG>(L));
-            const double cs = lseg_sum<SEG>(on ? (double)__expf(L - nm) : 0.0);
-            ssum = (m == -INFINITY ? 0.0 : ssum * (double)__expf(m - nm)) + cs;
-            m = nm;
-        }
-        if (live && sl == 0) {
-            if (g.mode_vi) {
-                if (g.logp) g.logp[b] = (float)(lsum / (double)K);                                   // models.py:84
-            } else {
-                if (g.ms) { g.ms[2 * b] = m; g.ms[2 * b + 1] = (float)ssum; }
-                if (g.logp) g.logp[b] = (float)((double)m + log(ssum) - log((double)g.K_total));     // models.py:148
-            }
-        }
-    }
-    if (!g.elbo) return;
-    // ---- publish this workgroup's logp, draw a ticket, the last arriver sums everything ----
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long t = __hip_atomic_fetch_add(g.ticket, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = (t == (unsigned long long)gridDim.x - 1);
-        if (last) {
-            __hip_atomic_store(g.ticket, 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next call
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        is_last = last;
-    }
-    __syncthreads();
-    if (!is_last) return;
-    double acc = 0.0;
-    for (long long b = tid; b < g.B; b += LIK_THREADS) acc += (double)g.logp[b];
-    red[tid] = acc;
-    __syncthreads();
-    for (int s2 = LIK_THREADS / 2; s2 > 0; s2 >>= 1) {
-        if (tid < s2) red[tid] += red[tid + s2];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        double kl = 0.0;
-        for (int i = 0; i < g.n_glob; ++i)
-            for (int c = 0; c < g.klg_n[i]; ++c) kl += g.klg[i][c];
-        *g.elbo = red[0] * g.scale - kl;                                                              // models.py:150
-    }
+    const LikQuadOps ops{g.lik, g.lik.p0_dev ? *g.lik.p0_dev : g.lik.p0, g.Dy};
+    elbo_points<SEG, false>(g, ops);
 }
 
-// ------------------------------------------------------------------------------------------
-// Heads of the bound's adjoint (csrc/backward.hip: k_elbo_bwd with the quadrature): one wave per data point, lanes over its K samples.
-// Pass 1: L_nk and the running (max, sum exp); pass 2: the weights and, per output, the heads.
-// ------------------------------------------------------------------------------------------
+// Heads of the bound's adjoint: elbo_bwd_point's layout and steps (likelihood_common.h) in a body of its own.  Through the shared core this
+// kernel compiled to 101 VGPRs for 115 and was SLOWER: a Bernoulli value + gradient on ten columns at configs[2] took 703.6-705.6 us against
+// 697.3-703.0 with this body, three alternating pairs in one session (profiles/likcore_time.json) -- so it keeps the body, and a change to the
+// core's lse_global branch, weight or part[] stores has to be made here as well.
 __global__ __launch_bounds__(256) void k_lik_elbo_bwd(LikBwdArgs a) {
     const int lane = threadIdx.x & 63;
     const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -373,20 +316,6 @@ static int take_lik(const iwvi_lik_desc* d, Lik& L, const char* what, bool need_
     }
 }
 
-template <int SEG>
-static int launch_lik_elbo(const LikReduceArgs& g, hipStream_t stream) {
-    constexpr int PPP = LIK_THREADS / SEG;
-    const long long blocks = (g.B + PPP - 1) / PPP;
-    hipLaunchKernelGGL(k_lik_elbo<SEG>, dim3((unsigned)blocks), dim3(LIK_THREADS), 0, stream, g);
-    return check_launch("k_lik_elbo");
-}
-
-template <int SEG>
-static int launch_lik_mix(const LikMixArgs& g, hipStream_t stream) {
-    hipLaunchKernelGGL(k_lik_mix<SEG>, dim3(mix_blocks(g.N, SEG)), dim3(LIK_THREADS), 0, stream, g);
-    return check_launch("k_lik_mix");
-}
-
 }  // namespace iwvi
 
 using namespace iwvi;
@@ -430,11 +359,11 @@ extern "C" int iwvi_lik_elbo_reduce(const iwvi_lik_desc* lik, const float* fmean
         return mc_launch_elbo(g, stream);
     }
     if (xl_type(g.lik.type)) return xl_launch_elbo(g, stream);
-    if (K <= 4) return launch_lik_elbo<4>(g, stream);
-    if (K <= 8) return launch_lik_elbo<8>(g, stream);
-    if (K <= 16) return launch_lik_elbo<16>(g, stream);
-    if (K <= 32) return launch_lik_elbo<32>(g, stream);
-    return launch_lik_elbo<64>(g, stream);
+    return seg_dispatch(K, [&](auto seg) {
+        constexpr int SEG = decltype(seg)::value;
+        hipLaunchKernelGGL(k_lik_elbo<SEG>, dim3((unsigned)lik_passes(B, SEG)), dim3(LIK_THREADS), 0, stream, g);
+        return check_launch("k_lik_elbo");
+    });
 }
 
 extern "C" int iwvi_lik_elbo_backward(const iwvi_lik_desc* lik, const float* fmean, const float* fvar, const float* Y, int Dy,
@@ -492,8 +421,7 @@ static int lik_elementwise(const char* what, const iwvi_lik_desc* lik, const flo
     if (xl_type(L.type))
         return xl_launch_elem(what, MODE, L, Fmu, Fvar, Y, (long long)T, Dy, (long long)row_div, (long long)row_mod, out, out2, (hipStream_t)stream_);
     const long long n = (long long)T * Dy;
-    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(k_lik_elem<MODE>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, L, Fmu, Fvar, Y, n, Dy,
+    hipLaunchKernelGGL(k_lik_elem<MODE>, dim3(elem_blocks(n)), dim3(256), 0, (hipStream_t)stream_, L, Fmu, Fvar, Y, n, Dy,
                        (long long)row_div, (long long)row_mod, out, out2);
     return check_launch(what);
 }
@@ -544,9 +472,9 @@ extern "C" int iwvi_lik_predict_mixture(const iwvi_lik_desc* lik, const float* f
     g.logp = out_logp; g.mean = out_mean; g.var = out_var;
     if (g.lik.type == IWVI_LIK_MULTICLASS) return mc_launch_mix(g, stream);
     if (xl_type(g.lik.type)) return xl_launch_mix(g, stream);
-    if (S <= 4) return launch_lik_mix<4>(g, stream);
-    if (S <= 8) return launch_lik_mix<8>(g, stream);
-    if (S <= 16) return launch_lik_mix<16>(g, stream);
-    if (S <= 32) return launch_lik_mix<32>(g, stream);
-    return launch_lik_mix<64>(g, stream);
+    return seg_dispatch(S, [&](auto seg) {
+        constexpr int SEG = decltype(seg)::value;
+        hipLaunchKernelGGL(k_lik_mix<SEG>, dim3(mix_blocks(N, SEG)), dim3(LIK_THREADS), 0, stream, g);
+        return check_launch("k_lik_mix");
+    });
 }

@@ -27,7 +27,10 @@ FIELDS = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_sp
 # kernels whose instantiations must not touch scratch memory at all ...
 # (k_lik_*: csrc/likelihood_tail.hip -- twenty quadrature nodes unrolled per element: no scratch, and a VGPR ceiling each, MAX_VGPRS below;
 #  k_mc_*: csrc/likelihood_multiclass.hip -- twenty running products per sample, which must stay in registers;
-#  k_xl_*: csrc/likelihood_explink.hip -- closed forms, and a float64 lgamma / digamma of the shape per wave)
+#  k_xl_*: csrc/likelihood_explink.hip -- closed forms, and a float64 lgamma / digamma of the shape per wave.
+#  The *_elbo and *_elbo_bwd kernels of the three files are ONE core each, csrc/likelihood_common.h: elbo_points / elbo_bwd_point, inlined over a
+#  policy per family -- but for k_lik_elbo_bwd, which keeps a body of its own --: a change to a core moves every family's rows;
+#  profiles/likcore_kernel_resources.txt has them side by side)
 NO_SCRATCH = ("k_dgp_forward", "k_bw_chain", "k_sample_stats", "k_lik_elbo", "k_lik_elbo_bwd", "k_lik_elem", "k_lik_finish", "k_kde_grid",
               "k_mc_elbo", "k_mc_elbo_bwd", "k_mc_elem", "k_xl_elbo", "k_xl_elbo_bwd", "k_xl_elem",
               "k_lik_mix", "k_mc_mix", "k_xl_mix",
@@ -53,9 +56,11 @@ MAX_SPILLS = {
 
 # VGPR ceilings (kernel name before its template arguments -> most VGPRs any instantiation may use).  The likelihood-tail kernels are latency
 # chains of transcendental evaluations: 128 VGPRs keep four waves on a SIMD (512 per lane) to hide them.  Today: k_lik_elbo 80, k_lik_elbo_bwd 115,
-# k_lik_elem 17-65, k_lik_finish 12; the predictive-mixture kernels (iwvi_lik_predict_mixture) k_lik_mix 105-109, k_mc_mix 113.
+# k_lik_elem 17-65, k_lik_finish 12, k_mc_elbo 108, k_mc_elbo_bwd 126, k_mc_elem 72-78; the predictive-mixture kernels
+# (iwvi_lik_predict_mixture) k_lik_mix 106-110, k_mc_mix 113.
 # The exp-link kernels (k_xl_*) do a handful of FMAs and one exp per element: their ceilings are the compiled counts (k_xl_elbo 79-89,
-# k_xl_elbo_bwd 65, k_xl_elem 37-63, k_xl_mix 95) rounded up to a multiple of 8, so a change that costs them a wave of occupancy shows.
+# k_xl_elem 37-63, k_xl_mix 95; k_xl_elbo_bwd 65 when the ceiling was set, 54 today) rounded up to a multiple of 8, so a change that costs them
+# a wave of occupancy shows.
 MAX_VGPRS = {"k_lik_elbo": 128, "k_lik_elbo_bwd": 128, "k_lik_elem": 128, "k_lik_finish": 32,
              "k_mc_elbo": 128, "k_mc_elbo_bwd": 128, "k_mc_elem": 128,
              "k_xl_elbo": 96, "k_xl_elbo_bwd": 72, "k_xl_elem": 64,

@@ -70,6 +70,23 @@ class StudentT:
         return quad(lambda f: self.logp(f, _t(Y)[..., None]), Fmu, Fvar, logspace=True)
 
 
+def sharded_heads(expect, Fmu, Fvar, kl, scale):
+    """The heads of iwvi_lik_elbo_backward for a K-shard against the whole job's normaliser, in float64.  ``expect(mu, var)`` -> [B, K]: a
+    sample's expectation summed over its outputs (tensors in, tensor out: the derivatives are autograd's); Fmu, Fvar [B, K, D] and
+    kl [B, K, width] hold float32 values.  The job is this shard and a second one that holds the same samples:
+      L = expect - sum kl,  lse_global = float32(logsumexp_k L + log 2),  K_total = 2 K,  w = scale exp(L - lse_global),
+      d_mean = w dE/dmu,  d_var = w dE/dvar.
+    Returns (L, lse_global, w, d_mean, d_var, dE/dmu, dE/dvar) as float64 arrays."""
+    mu = torch.tensor(np.asarray(Fmu, dtype=np.float64), requires_grad=True)
+    var = torch.tensor(np.asarray(Fvar, dtype=np.float64), requires_grad=True)
+    E = expect(mu, var)
+    dmu, dvar = (g.numpy() for g in torch.autograd.grad(E.sum(), (mu, var)))
+    L = E.detach().numpy() - np.asarray(kl, dtype=np.float64).sum(-1)
+    lse = (torch.logsumexp(torch.as_tensor(L), 1).numpy() + math.log(2.0)).astype(np.float32).astype(np.float64)
+    w = scale * np.exp(L - lse[:, None])
+    return L, lse, w, w[..., None] * dmu, w[..., None] * dvar, dmu, dvar
+
+
 def quad(g, Fmu, Fvar, logspace=False):
     """sum_i w_i g(mu + sqrt(2 v) x_i), or log sum_i exp(g(.) + log w_i)."""
     Fmu, Fvar = _t(Fmu), _t(Fvar)

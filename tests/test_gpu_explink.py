@@ -103,14 +103,21 @@ def test_elementwise_callables_match_the_restatement(gpu_device, kind, kw, ys):
 
 
 # ---- 2: the heads directly ----------------------------------------------------------------------------------------------------------
-def _backward_call(dev, desc, fm, fv, Y, B, K, Dy, scale=1.0, mode_vi=1):
+def _backward_call(dev, desc, fm, fv, Y, B, K, Dy, scale=1.0, mode_vi=1, kls=(), glob=None, lse_global=None, K_total=0):
+    """kls: local regularisers [B K, width] each; glob: one float64 array of global KL shares; lse_global [B] with K_total: the heads of a
+    K-shard against the whole job's normaliser."""
     from dgps_with_iwvi_amd import _abi
     T = B * K
     w, dm, dv = torch.empty(T, device=dev), torch.empty(T, Dy, device=dev), torch.empty(T, Dy, device=dev)
     sums = torch.empty(3, dtype=torch.float64, device=dev)
     ws = torch.empty(2 * B, dtype=torch.float64, device=dev)
-    _abi.check(_abi.lib().iwvi_lik_elbo_backward(desc, _abi.ptr(fm), _abi.ptr(fv), _abi.ptr(Y), Dy, None, None, 0, B, K, scale, mode_vi,
-                                                 _abi.ptr(w), _abi.ptr(dm), _abi.ptr(dv), None, None, 0, None, K,
+    kls = list(kls)
+    kd = (ctypes.c_int32 * max(len(kls), 1))(*[k.shape[-1] for k in kls])
+    gl = [] if glob is None else [glob]
+    gn = (ctypes.c_int32 * 1)(glob.numel() if gl else 0)
+    _abi.check(_abi.lib().iwvi_lik_elbo_backward(desc, _abi.ptr(fm), _abi.ptr(fv), _abi.ptr(Y), Dy, _abi.ptr_array(kls) if kls else None, kd, len(kls),
+                                                 B, K, scale, mode_vi, _abi.ptr(w), _abi.ptr(dm), _abi.ptr(dv), _abi.ptr_array(gl) if gl else None, gn,
+                                                 len(gl), _abi.ptr(lse_global), K_total or K,
                                                  ctypes.c_void_p(sums.data_ptr()), ctypes.c_void_p(ws.data_ptr()), _abi.stream_ptr()))
     return w, dm, dv, sums
 
@@ -143,6 +150,52 @@ def test_heads_are_the_derivatives_of_the_closed_form(gpu_device, kind, kw, ys):
     print("%s %r heads: worst multiples of 2^-24 S: " % (kind, kw) + "  ".join("%s %.2f" % kv for kv in sorted(mult.items())))
     for what, x in mult.items():
         assert x <= C8, (what, x)
+
+
+@pytest.mark.parametrize("K", [3, 70])
+def test_gamma_heads_of_a_k_shard_against_the_jobs_normaliser(gpu_device, K):
+    """iwvi_lik_elbo_backward with lse_global (the K-sharded weights scale exp(L - lse_global), the constant c0 taken off the job's normaliser
+    and added back to out_sums[0]) at K = 3 and K = 70 -- past the one-sample-per-lane shortcut --, B = 5, Dy = 2, one regulariser of width 2,
+    scale 2.75, against X.R.sharded_heads in float64.  L carries 8 x 2^-24 x S (S: the expectation's scales of the sample's outputs and its
+    regulariser entries, the worst sample of the point) plus half a spacing of the float32 normaliser; the weights follow
+    iw_reduction_reference.tol_w from that; a head adds 8 x 2^-24 x its own scale (X.heads) per unit weight; d shape likewise."""
+    from scipy import special
+    import iw_reduction_reference as IR
+    lik, ref = _liks("gamma", **STACK["gamma"])
+    B, Dy, scale = 5, 2, 2.75
+    rng = np.random.default_rng(23 + K)
+    mu32 = rng.uniform(-1.5, 1.5, (B, K, Dy)).astype(np.float32)
+    v32 = rng.uniform(0.05, 0.5, (B, K, Dy)).astype(np.float32)
+    kl32 = rng.uniform(0.0, 1.0, (B, K, 2)).astype(np.float32)
+    Y32 = rng.uniform(0.3, 4.0, (B, Dy)).astype(np.float32)
+    glob = np.array([1.25, 0.5])
+    m64, v64, kl64 = (a.astype(np.float64) for a in (mu32, v32, kl32))
+    y64 = np.broadcast_to(Y32.astype(np.float64)[:, None, :], (B, K, Dy)).copy()
+    L, lse, wr, dmr, dvr, _, _ = X.R.sharded_heads(lambda m, v: ref.variational_expectations(m, v, y64).sum(-1), m64, v64, kl64, scale)
+    Kt = 2 * K
+    fm, fv, kl = (_t(a, gpu_device).reshape(B * K, -1) for a in (mu32, v32, kl32))
+    w, dm, dv, sums = _backward_call(gpu_device, lik.lik_desc(), fm, fv, _t(Y32, gpu_device), B, K, Dy, scale=scale, mode_vi=0, kls=[kl],
+                                     glob=torch.as_tensor(glob, dtype=torch.float64, device=gpu_device), lse_global=_t(lse, gpu_device), K_total=Kt)
+    w, dm, dv, sums = _n64(w).reshape(B, K), _n64(dm).reshape(B, K, Dy), _n64(dv).reshape(B, K, Dy), sums.cpu().numpy()
+    S_L = (X.var_exp_scale(ref, m64, v64, y64).sum(-1).numpy() + kl64.sum(-1)).max(1) + np.abs(L).max(1)
+    tol_L = C8 * U * S_L + 0.5 * IR.spacing32(lse)
+    tw = IR.tol_w(wr, scale, tol_L)
+    print("gamma K=%d lse_global: w max err / allowed %.3f" % (K, float((np.abs(w - wr) / tw).max())))
+    assert np.isfinite(w).all() and np.all(np.abs(w - wr) <= tw), float((np.abs(w - wr) / tw).max())
+    _, _, S_h = X.heads(ref, m64, v64, y64)
+    for nm, got, want in (("d_mean", dm, dmr), ("d_var", dv, dvr)):
+        tol = np.abs(want) * (tw / wr)[..., None] + wr[..., None] * C8 * U * S_h.numpy()
+        print("gamma K=%d lse_global: %s max err / allowed %.3f" % (K, nm, float((np.abs(got - want) / tol).max())))
+        assert np.all(np.abs(got - want) <= tol), (nm, float((np.abs(got - want) / tol).max()))
+    want0 = float((lse - math.log(Kt)).sum())
+    assert abs(sums[0] - want0) <= float(tol_L.sum()), (sums[0], want0)
+    assert abs(sums[2] - (scale * sums[0] - glob.sum())) <= 4 * 2.0 ** -52 * (abs(scale * sums[0]) + glob.sum()), sums
+    psi = float(special.digamma(STACK["gamma"]["shape"]))
+    term = -m64 - psi + np.log(y64)
+    want1 = float((wr[..., None] * term).sum())
+    tol1 = float(((tw[..., None] + wr[..., None] * C8 * U) * (1.0 + np.abs(m64) + abs(psi) + np.abs(np.log(y64)))).sum())
+    print("gamma K=%d lse_global: d_shape err %.3e allowed %.3e" % (K, abs(sums[1] - want1), tol1))
+    assert abs(sums[1] - want1) <= tol1, (sums[1], want1, tol1)
 
 
 @pytest.mark.parametrize("kind", sorted(STACK))

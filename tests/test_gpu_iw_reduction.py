@@ -481,3 +481,36 @@ def test_generic_tail_reduction_and_weights(gpu_device, kind):
             # the heads ([B, K] layout only): the weights follow the weight rule
             got = _backward(gpu_device, fm, fv, Y, None, kls, False, glob[:R.MAX_GLOB_BWD], scale, lik=desc)
             _check_heads(got, Lref, tol_L, fm, fv, Y, _f32v(0.4), scale, False, glob, what + " heads", gaussian=False)
+
+
+@pytest.mark.parametrize("K", [3, 70])
+def test_generic_tail_heads_of_a_k_shard_against_the_jobs_normaliser(gpu_device, K):
+    """k_lik_elbo_bwd with lse_global (Student-t): the K-sharded weights scale exp(L - lse_global) and out_sums[0] = sum (lse_global -
+    log K_total), at K = 3 and K = 70 -- past the one-sample-per-lane shortcut --, B = 5, Dy = 2, one regulariser of width 2, scale 2.75,
+    moments that differ from sample to sample; the reference is lik_restatement.sharded_heads in float64.  L: the generic tail's tol_L plus
+    half a spacing of the float32 normaliser, as the Gaussian test above; w, out_sums[0] and [2]: _check_heads.  d_mean and d_var carry the
+    weight's relative error, four float32 roundings, and per unit weight the error of the rule's derivative sums: a node's g' = (nu + 1) e /
+    (s^2 nu + e^2) is off by at most |g''| <= (nu + 1) / (s^2 nu) = 2.55 times half a spacing32 of |f| < 8 plus four roundings of |g'| <= 1.79
+    -- 1.65e-6 --, and the ten fused accumulations add 10 x 2^-24 x 1.79 = 1.1e-6: under 4e-6 for dE/dmu (the weights sum to 1), and 4e-6 x
+    sum_i w_i |x_i| / sqrt(2 v) = 4e-6 x 0.5642 / sqrt(2 v) for dE/dv = sum_i w_i x_i g'(f_i) / sqrt(2 v)."""
+    import lik_restatement as LR
+    B, Dy, scale = 5, 2, 2.75
+    rng = np.random.default_rng(80 + K)
+    desc = _lik("student_t")
+    ref = LR.StudentT(scale=_f32v(0.7), df=4.0)
+    fm, fv = R.f32(rng.standard_normal((B, K, Dy))), R.f32(rng.uniform(0.05, 0.5, (B, K, Dy)))
+    Y, kl = R.f32(rng.standard_normal((B, Dy))), R.f32(rng.uniform(0.0, 1.0, (B, K, 2)))
+    Lref, lse, wr, dmr, dvr, _, _ = LR.sharded_heads(lambda m, v: ref.variational_expectations(m, v, Y[:, None, :]).sum(-1), fm, fv, kl, scale)
+    E = Lref + kl.sum(-1)
+    big = np.maximum.reduce([np.abs(E) + 2.0, kl[..., 0], np.abs(E - kl[..., 0]), kl[..., 1], np.abs(Lref)])
+    tol_L = R.tol_logw(big, Dy + 2) + Dy * 1.5e-6 + 0.5 * R.spacing32(lse)
+    glob = R.global_kls(2, 2, seed=K)
+    what = "student_t B=%d K=%d Dy=%d lse_global" % (B, K, Dy)
+    got = _backward(gpu_device, fm, fv, Y, None, [kl], False, glob, scale, lse_global=lse, K_total=2 * K, lik=desc)
+    _check_heads(got, Lref, tol_L, fm, fv, Y, _f32v(0.4), scale, False, glob, what, lse_global=lse, K_total=2 * K, gaussian=False)
+    rel = R.tol_w(wr, scale, tol_L) / wr
+    extra = {"d_mean": 4e-6 * np.ones_like(fv), "d_var": 4e-6 * 0.5642 / np.sqrt(2.0 * fv)}
+    for nm, a_, r_ in (("d_mean", got[1], dmr), ("d_var", got[2], dvr)):
+        tol = np.abs(r_) * (rel[..., None] + 4 * 2.0 ** -23) + wr[..., None] * extra[nm]
+        print("  %s: %s max of err / allowed %.3f" % (what, nm, float((np.abs(a_ - r_) / tol).max())))
+        assert np.all(np.abs(a_ - r_) <= tol), (what, nm, float((np.abs(a_ - r_) / tol).max()))

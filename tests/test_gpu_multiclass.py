@@ -295,6 +295,50 @@ def test_graph_step_equals_eager_step_and_resume_is_exact(gpu_device, tmp_path):
 from test_gpu_likelihoods import _Calls, _TAILS   # noqa: E402  (counts the calls of the library's entry points)
 
 
+from test_gpu_explink import _backward_call   # noqa: E402  (iwvi_lik_elbo_backward directly)
+
+
+@pytest.mark.parametrize("K", [3, 70])
+def test_heads_of_a_k_shard_against_the_jobs_normaliser(gpu_device, K):
+    """iwvi_lik_elbo_backward with lse_global (the K-sharded weights scale exp(L - lse_global), out_sums[0] = sum (lse_global - log K_total))
+    at K = 3 and K = 70 -- past the one-sample-per-lane shortcut --, B = 5, C = 3, one regulariser of width 2, scale 2.75, against
+    lik_restatement.sharded_heads in float64.  L: the margin on the recorded error of the expectation, the float32 subtractions of the two
+    regulariser entries (iw_reduction_reference.tol_logw) and half a spacing of the float32 normaliser; the weights follow tol_w from that.
+    A head is a float32 sum over the twenty nodes of products of C - 1 cdfs, an exponential and a quotient -- about three roundings a node:
+    64 x 2^-24 of the sample's largest head of that array, on top of the weight's relative error."""
+    import iw_reduction_reference as IR
+    C, B, scale = 3, 5, 2.75
+    lik, ref = _lik(C)
+    rng = np.random.default_rng(29 + K)
+    mu32 = rng.uniform(-1.5, 1.5, (B, K, C)).astype(np.float32)
+    v32 = rng.uniform(0.05, 0.5, (B, K, C)).astype(np.float32)
+    kl32 = rng.uniform(0.0, 1.0, (B, K, 2)).astype(np.float32)
+    Y = rng.integers(0, C, (B, 1)).astype(np.float64)
+    glob = np.array([1.25, 0.5])
+    m64, v64, kl64 = (a.astype(np.float64) for a in (mu32, v32, kl32))
+    L, lse, wr, dmr, dvr, _, _ = MR.R.sharded_heads(lambda m, v: ref.variational_expectations(m, v, Y[:, None, :])[..., 0], m64, v64, kl64, scale)
+    Kt = 2 * K
+    fm, fv, kl = (_t(a, gpu_device).reshape(B * K, -1) for a in (mu32, v32, kl32))
+    w, dm, dv, sums = _backward_call(gpu_device, lik.lik_desc(), fm, fv, _t(Y, gpu_device), B, K, C, scale=scale, mode_vi=0, kls=[kl],
+                                     glob=torch.as_tensor(glob, dtype=torch.float64, device=gpu_device), lse_global=_t(lse, gpu_device), K_total=Kt)
+    n64 = lambda t: t.cpu().numpy().astype(np.float64)
+    w, dm, dv, sums = n64(w).reshape(B, K), n64(dm).reshape(B, K, C), n64(dv).reshape(B, K, C), sums.cpu().numpy()
+    E = L + kl64.sum(-1)
+    big = np.maximum.reduce([np.abs(E), kl64[..., 0], np.abs(E - kl64[..., 0]), kl64[..., 1], np.abs(L)])
+    tol_L = MARGIN * ELEMENTWISE_RECORD["var_exp"] + IR.tol_logw(big, 2) + 0.5 * IR.spacing32(lse)
+    tw = IR.tol_w(wr, scale, tol_L)
+    print("multiclass K=%d lse_global: w max err / allowed %.3f" % (K, float((np.abs(w - wr) / tw).max())))
+    assert np.isfinite(w).all() and np.all(np.abs(w - wr) <= tw), float((np.abs(w - wr) / tw).max())
+    for nm, got, want in (("d_mean", dm, dmr), ("d_var", dv, dvr)):
+        tol = np.abs(want) * (tw / wr)[..., None] + 64 * 2.0 ** -24 * np.abs(want).max(-1, keepdims=True)
+        print("multiclass K=%d lse_global: %s max err / allowed %.3f" % (K, nm, float((np.abs(got - want) / tol).max())))
+        assert np.all(np.abs(got - want) <= tol), (nm, float((np.abs(got - want) / tol).max()))
+    want0 = float((lse - math.log(Kt)).sum())
+    assert abs(sums[0] - want0) <= float(tol_L.sum()), (sums[0], want0)
+    assert sums[1] == 0.0                                        # no trained parameter
+    assert abs(sums[2] - (scale * sums[0] - glob.sum())) <= 4 * 2.0 ** -52 * (abs(scale * sums[0]) + glob.sum()), sums
+
+
 def test_gaussian_keeps_the_fused_tail_and_multiclass_takes_the_three_launch_route(gpu_device):
     """BASELINE configs[2] (L=2, M=128, K=20, B=1024, latent-variable layer): a Gaussian model still evaluates in ONE iwvi_dgp_forward in
     LEAN mode 1 and takes its heads from the launch; a MultiClass model of the same stack (10 classes) calls iwvi_lik_elbo_reduce once per
