@@ -128,6 +128,25 @@ class SghmcTensor(ctypes.Structure):
                 ("theta64", c_void_p), ("noise", c_void_p), ("noise_out", c_void_p), ("n", c_int64)]
 
 
+CVAE_MAX_MAPS, CVAE_MAX_WIDTH, CVAE_MAX_L, CVAE_MAX_DY = 4, 128, 8, 8
+CVAE_NO_Y_NOISE = 1         # iwvi_cvae_predict_samples flags
+
+
+class CvaeDesc(ctypes.Structure):
+    """struct iwvi_cvae_desc (include/iwvi_hip.h): the CVAE baseline's two nets."""
+    _fields_ = [("enc_W", ctypes.POINTER(c_void_p)), ("enc_b", ctypes.POINTER(c_void_p)),
+                ("dec_W", ctypes.POINTER(c_void_p)), ("dec_b", ctypes.POINTER(c_void_p)),
+                ("enc_dims", ctypes.POINTER(ctypes.c_int32)), ("dec_dims", ctypes.POINTER(ctypes.c_int32)),
+                ("n_maps", ctypes.c_int32), ("Dx", ctypes.c_int32), ("Dy", ctypes.c_int32), ("L", ctypes.c_int32),
+                ("act", ctypes.c_int32), ("variance", c_float), ("variance_dev", c_void_p)]
+
+
+class CvaeGrads(ctypes.Structure):
+    """struct iwvi_cvae_grads (include/iwvi_hip.h): d elbo / d parameter, shaped like the parameters."""
+    _fields_ = [("enc_dW", ctypes.POINTER(c_void_p)), ("enc_db", ctypes.POINTER(c_void_p)),
+                ("dec_dW", ctypes.POINTER(c_void_p)), ("dec_db", ctypes.POINTER(c_void_p)), ("dvariance", c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/iwvi_hip.h declares
 PROTOTYPES = {
     "iwvi_version": (c_int, []),
@@ -258,6 +277,13 @@ PROTOTYPES = {
     "iwvi_fill_normal_dev": (c_int, [c_void_p, c_int64, ctypes.c_uint64, c_void_p, c_void_p]),
     "iwvi_sghmc_step": (c_int, [ctypes.POINTER(SghmcTensor), c_int, c_double, c_double, c_double, c_int, ctypes.c_uint64, c_void_p, c_void_p]),
     "iwvi_neg_log_prior": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "iwvi_cvae_ws_bytes": (c_size_t, [ctypes.POINTER(CvaeDesc), c_int64]),
+    "iwvi_cvae_elbo": (c_int, [ctypes.POINTER(CvaeDesc), c_void_p, c_void_p, c_int64, c_void_p, ctypes.c_uint64, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p]),
+    "iwvi_cvae_elbo_and_grad": (c_int, [ctypes.POINTER(CvaeDesc), c_void_p, c_void_p, c_int64, c_void_p, ctypes.c_uint64, c_void_p, c_void_p,
+                                        c_void_p, ctypes.POINTER(CvaeGrads), c_void_p, c_void_p]),
+    "iwvi_cvae_predict_samples": (c_int, [ctypes.POINTER(CvaeDesc), c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, ctypes.c_uint64,
+                                          c_void_p, c_void_p, c_void_p]),
 }
 
 DEBUG_OPTIONS = ("IWVI_BW_FUSED", "IWVI_CHAIN_EXIT", "IWVI_FW_SLOW_TAIL", "IWVI_FW_MAX_NS", "IWVI_NATGRAD_UNFUSED", "IWVI_NG_ONE_WG", "IWVI_NG_STOP", "IWVI_DEBUG_STOP", "IWVI_PRE_STAMP_P",

@@ -6,7 +6,8 @@
 dimensions), ``ARGS.M`` inducing points, ``ARGS.likelihood_variance``, ``ARGS.minibatch_size``,
 ``ARGS.num_IW_samples``.  The training op the reference attaches (``model.train_op``: natural gradient + Adam,
 :270-304) is ``attach_train_op`` over ``training.Trainer`` (row F1).  ``build_sghmc_model`` builds the reference's third mode, ``'SGHMC'`` (``q_sqrt = None`` layers,
-the sampler of ``sghmc.SGHMC`` as the train op); ``build_model`` itself raises for it and for the CVAE baseline, which is out of scope.
+the sampler of ``sghmc.SGHMC`` as the train op) and ``build_cvae_model`` the fourth, the ``'CVAE'`` baseline (``cvae.CVAE``, Adam as the train op);
+``build_model`` itself raises for both and names the builder to call.
 
 Initial values follow the reference: first-layer inducing inputs by k-means of X (or X padded with N(0,1) rows when
 N <= M), deeper layers N(0,1) with their first columns taken from them (:218-219, :239-240); RBF-ARD kernels with
@@ -76,8 +77,8 @@ def build_layers(configuration, X, M, rng=None):
 def build_model(ARGS, X, Y, apply_name=True, device=None):
     if ARGS.mode not in ("VI", "IWAE"):
         raise NotImplementedError("mode %r: the VI / IWAE models (with their NatGrad + Adam train_op) are built here; an SGHMC model "
-                                  "(with its sampler + Adam train_op) by build_sghmc_model; the CVAE baseline is outside the scope "
-                                  "of this port (SURVEY.md section 8)" % (ARGS.mode,))
+                                  "(with its sampler + Adam train_op) by build_sghmc_model; the CVAE baseline (with its Adam train_op) "
+                                  "by build_cvae_model" % (ARGS.mode,))
     layers = build_layers(ARGS.configuration, X, ARGS.M)
     lik = Gaussian(ARGS.likelihood_variance)
     name = "Model" if apply_name else None
@@ -128,6 +129,51 @@ def build_sghmc_model(ARGS, X, Y, apply_name=True, device=None):
         return opt.train_hypers()
 
     model.init_op, model.train_op = init_op, train_op
+    return model
+
+
+def parse_cvae_configuration(configuration):
+    """'100_100' -> [100, 100]; '' -> [] (one linear map per net).  As the reference (build_models.py:150-155): the tokens that are
+    integers are kept, anything else is dropped."""
+    out = []
+    for tok in configuration.split("_"):
+        try:
+            out.append(int(tok))
+        except ValueError:
+            pass
+    return out
+
+
+def build_cvae_model(ARGS, X, Y, apply_name=True, device=None):
+    """The reference's ``mode == 'CVAE'`` model (build_models.py:148-173): ``cvae.CVAE`` with ``latent_dim = 1``, the hidden widths of
+    ``ARGS.configuration`` ('', '50', '50_50', '100_100' in the reference's grid) and ``batch_size = ARGS.minibatch_size``, and the
+    reference's attributes on it, none of which takes a session: ``model.init_op()`` (global_step = 0), ``model.train_op()`` (global_step
+    += 1, then one Adam step at ``ARGS.lr`` 0.98^floor(global_step / 1000) -- the 0.98 is the reference's constant, not ``ARGS.lr_decay``)
+    and ``model.global_step``.  The optimiser (``cvae.CVAETrainer``, ``model.trainer()``) is created at the first call: it needs the ROCm
+    device, the model itself can be built on any."""
+    from .cvae import CVAE, CVAETrainer
+    model = CVAE(X, Y, 1, parse_cvae_configuration(ARGS.configuration), batch_size=ARGS.minibatch_size,
+                 name="CVAE" if apply_name else None, device=device or settings.default_device())
+    state = {}
+
+    def trainer():
+        if "t" not in state:
+            state["t"] = CVAETrainer(model, lr=getattr(ARGS, "lr", 5e-3), use_graph=bool(getattr(ARGS, "use_graph", True)))
+            state["t"].global_step = model.global_step
+        return state["t"]
+
+    def init_op():
+        model.global_step = 0
+        if "t" in state:
+            state["t"].global_step = 0
+
+    def train_op():
+        elbo = trainer().step()
+        model.global_step = state["t"].global_step
+        return elbo
+
+    model.global_step = 0
+    model.trainer, model.init_op, model.train_op = trainer, init_op, train_op
     return model
 
 
@@ -294,9 +340,14 @@ def load_state_dict(model, state):
     return model
 
 
+def _is_cvae(model):
+    from .cvae import CVAE
+    return isinstance(model, CVAE)
+
+
 def save_checkpoint(model, path, trainer=None):
     """Parameters (+ the optimiser state of ``trainer``: Adam moments and unconstrained variables, step counters) -> .npz."""
-    out = state_dict(model)
+    out = model.state_dict() if _is_cvae(model) else state_dict(model)
     if trainer is not None:
         out.update({"trainer." + k: v for k, v in trainer.state_dict().items()})
     np.savez(path, **out)
@@ -305,7 +356,13 @@ def save_checkpoint(model, path, trainer=None):
 def load_checkpoint(model, path, trainer=None):
     with np.load(path) as f:
         state = {k: f[k] for k in f.files}
-    load_state_dict(model, {k: v for k, v in state.items() if not k.startswith("trainer.")})
+    own = {k: v for k, v in state.items() if not k.startswith("trainer.")}
+    if _is_cvae(model):
+        model.load_state_dict(own)
+    else:
+        load_state_dict(model, own)
     if trainer is not None:
         trainer.load_state_dict({k[len("trainer."):]: v for k, v in state.items() if k.startswith("trainer.")})
+        if _is_cvae(model) and hasattr(model, "global_step"):
+            model.global_step = trainer.global_step
     return model

@@ -810,6 +810,68 @@ int iwvi_sghmc_step(const iwvi_sghmc_tensor* tensors_host, int n_tensors, double
                     int burn_in, uint64_t seed, uint64_t* rng_state, void* stream);
 int iwvi_neg_log_prior(const float* q_mu, int M, int R, double* out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The CVAE baseline (additive extension of ABI 19; csrc/cvae.hip; reference experiments/build_models.py:29-142): an MLP encoder and an MLP
+ * decoder in float32, NO skip connections (unlike the Encoder of the latent-variable layer above).
+ *   encoder  [x, y] -> (means | raw) [2L]   widths enc_dims = [Dx + Dy, hidden.., 2L];  hidden activation after every map but the last
+ *   raw_c = clip(raw, ln 1e-12, ln 1e10) (zero gradient outside, as tf.clip_by_value);  sigma = exp(raw_c / 2);  z = mu + eps sigma
+ *   decoder  [z, x] -> yhat [Dy]            widths dec_dims = [L + Dx, hidden.., Dy] (the same hidden widths), z FIRST
+ *   out[0] = elbo = out[1] - out[2],  out[1] = sum_{n,d} log N(y_nd; yhat_nd, variance),  out[2] = sum_{n,j} KL(N(mu_nj, sigma_nj^2) || N(0, 1))
+ * Both sums run over the B rows given; no N / B scale (the reference applies none).  W[i] is [dims[i], dims[i+1]] row-major, b[i] [dims[i+1]].
+ * variance = *variance_dev when that device scalar is given.
+ *
+ * Launch structure.  A row-parallel launch takes eight rows per workgroup through encoder, clip, sample, decoder, the per-row log density and
+ * KL and -- gradient entry only -- the deltas of every map, activations in LDS; every map's input rows and deltas go to the workspace.  The
+ * second launch of the gradient entry forms dW = A^T Delta and db of every map in 8 x 8 tiles, each entry summing the rows in a fixed order,
+ * and its last workgroup sums the per-workgroup (log p, KL, d variance) partials in float64 in a fixed order; the value entry's second
+ * launch is that last workgroup alone.  No float atomics: two calls on the same inputs give the same bits, and the value entry's three
+ * scalars are bit-identical to the gradient entry's.  iwvi_cvae_elbo_and_grad does not run the value entry.
+ *
+ * Noise.  eps [B, L] if given; otherwise the launch draws exactly what iwvi_fill_normal(out, B L, seed, c) writes, c = rng_state[0], and the
+ * entry's second launch advances the counter by ceil(B L / 4) (the protocol of iwvi_sghmc_step; rng_state[1] is left as it is found).
+ * eps_out [B, L] (optional) receives what was used.  rng_state may be NULL when eps is given.
+ * ws: iwvi_cvae_ws_bytes(desc, B) bytes of device memory, 256-byte aligned, no initial contents (0 for B <= 0 or an invalid descriptor).
+ *
+ * iwvi_cvae_predict_samples: out_y[n, s, d] = decoder(z_t, x_n)_d + sqrt(variance) z_y[t, d], t = n S + s -- [N, S, Dy], a point's S samples
+ * contiguous (what iwvi_dgp_predict_samples writes and iwvi_sample_stats reads fastest); ONE launch.  z [N S, L] and z_y [N S, Dy] may be
+ * injected; a missing one is drawn: z as iwvi_fill_normal(., N S L, seed, c), z_y as iwvi_fill_normal(., N S Dy, seed, c + ceil(N S L / 4)),
+ * and a launch that draws anything advances the counter by ceil(N S L / 4) + ceil(N S Dy / 4) (rng_state = {counter, arrival ticket} as for
+ * iwvi_fill_normal_dev).  flags & IWVI_CVAE_NO_Y_NOISE: the decoder's output alone (predict_y), z_y is neither read nor drawn.
+ * N S < 2^31 - 4096.
+ *
+ * IWVI_ERR_ARG (iwvi_last_error names the entry point) before any HIP call for: a null pointer, B / N / S <= 0, n_maps outside
+ * 1 .. IWVI_CVAE_MAX_MAPS, a width outside 1 .. IWVI_CVAE_MAX_WIDTH, L outside 1 .. IWVI_CVAE_MAX_L, Dy outside 1 .. IWVI_CVAE_MAX_DY,
+ * enc_dims[0] != Dx + Dy, dec_dims[0] != L + Dx, enc_dims[last] != 2 L, dec_dims[last] != Dy, hidden widths that differ between the two
+ * nets, an unknown activation, a missing workspace, a drawing call without rng_state, N S out of range.
+ * ---------------------------------------------------------------------- */
+#define IWVI_CVAE_MAX_MAPS 4     /* linear maps per net ('100_100_100')                    */
+#define IWVI_CVAE_MAX_WIDTH 128  /* every width, Dx + Dy and L + Dx included               */
+#define IWVI_CVAE_MAX_L 8        /* latent dimensions                                      */
+#define IWVI_CVAE_MAX_DY 8       /* target columns                                         */
+#define IWVI_CVAE_NO_Y_NOISE 1   /* iwvi_cvae_predict_samples flags                        */
+typedef struct iwvi_cvae_desc {
+    const float* const* enc_W; const float* const* enc_b;   /* host arrays of n_maps device pointers */
+    const float* const* dec_W; const float* const* dec_b;
+    const int32_t* enc_dims; const int32_t* dec_dims;       /* host: n_maps + 1 widths each          */
+    int32_t n_maps;                                         /* linear maps per net                   */
+    int32_t Dx, Dy, L;
+    int32_t act;                                            /* IWVI_ACT_* of the hidden layers       */
+    float variance;
+    const float* variance_dev;                              /* optional device scalar, wins when given */
+} iwvi_cvae_desc;
+typedef struct iwvi_cvae_grads {                            /* d elbo / d parameter, shaped like the parameters */
+    float* const* enc_dW; float* const* enc_db;             /* host arrays of n_maps device pointers */
+    float* const* dec_dW; float* const* dec_db;
+    double* dvariance;                                      /* [1] float64 (feeds IWVI_ADAM_GRAD_F64) */
+} iwvi_cvae_grads;
+size_t iwvi_cvae_ws_bytes(const iwvi_cvae_desc* desc, int64_t B);
+int iwvi_cvae_elbo(const iwvi_cvae_desc* desc, const float* X, const float* Y, int64_t B, const float* eps, uint64_t seed,
+                   uint64_t* rng_state, float* eps_out, double* out, void* ws, void* stream);
+int iwvi_cvae_elbo_and_grad(const iwvi_cvae_desc* desc, const float* X, const float* Y, int64_t B, const float* eps, uint64_t seed,
+                            uint64_t* rng_state, float* eps_out, double* out, const iwvi_cvae_grads* grads, void* ws, void* stream);
+int iwvi_cvae_predict_samples(const iwvi_cvae_desc* desc, const float* X, int64_t N, int64_t S, const float* z, const float* z_y,
+                              int flags, uint64_t seed, uint64_t* rng_state, float* out_y, void* stream);
+
 /* Diagnostic / development route switches (NOT part of the drop-in surface, like iwvi_debug_set_stamps): the library itself never reads
  * the environment.  name = one of the IWVI_* route names listed in csrc/abi.hip (e.g. "IWVI_BW_FUSED", "IWVI_NATGRAD_UNFUSED"),
  * value 0 = default route.  Returns 0, or IWVI_ERR_ARG for an unknown name.  Process-wide; not for concurrent use with launches. */

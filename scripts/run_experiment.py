@@ -4,6 +4,7 @@ configuration string, train with the reference's train_op (NatGrad + Adam), eval
 
     python scripts/run_experiment.py --configuration L1_G5 --mode IWAE --iterations 500
     python scripts/run_experiment.py --configuration G5 --mode SGHMC --iterations 500      (the sampler + Adam on the hyperparameters)
+    python scripts/run_experiment.py --configuration 100_100 --mode CVAE --iterations 2000 (the CVAE baseline, Adam)
 """
 import argparse
 import os
@@ -50,6 +51,26 @@ def run_sghmc(ARGS, X, Y, Xs, Ys, dev):
     return res
 
 
+def run_cvae(ARGS, X, Y, Xs, Ys, dev):
+    """--mode CVAE (reference build_models.py:148-173): the baseline of the paper's tables -- build, train with its Adam train_op,
+    evaluate like every other mode; the reference's ``res`` keys."""
+    model = build_models.build_cvae_model(ARGS, X.astype(np.float32), Y.astype(np.float32), device=dev)
+    model.init_op()
+    before = evaluation.evaluate(model, Xs, Ys, ARGS.num_predict_samples, ARGS.predict_batch_size, on_device=ARGS.device_eval)
+    t0 = time.perf_counter()
+    for it in range(ARGS.iterations):
+        elbo = model.train_op()
+        if it % max(1, ARGS.iterations // 10) == 0:
+            print("iteration %5d  ELBO %.2f" % (it, float(elbo)), flush=True)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    res = evaluation.evaluate(model, Xs, Ys, ARGS.num_predict_samples, ARGS.predict_batch_size, shapiro=True, on_device=ARGS.device_eval)
+    res.update(test_loglik_before_training=before["test_loglik"], train_seconds=dt, ms_per_iteration=dt / max(ARGS.iterations, 1) * 1e3)
+    res.update(ARGS.__dict__)
+    print(res)
+    return res
+
+
 def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--mode", default="IWAE")
@@ -83,6 +104,8 @@ def main(argv=None):
     dev = torch.device("cuda:0")
     if ARGS.mode == "SGHMC":
         return run_sghmc(ARGS, X, Y, Xs, Ys, dev)
+    if ARGS.mode == "CVAE":
+        return run_cvae(ARGS, X, Y, Xs, Ys, dev)
     model = build_models.build_model(ARGS, X.astype(np.float32), Y.astype(np.float32), device=dev)
     before = evaluation.evaluate(model, Xs, Ys, ARGS.num_predict_samples, ARGS.predict_batch_size)
     t0 = time.perf_counter()
