@@ -317,19 +317,11 @@ static bool launch_fast(hipStream_t st, const GemmArgs& g) {
     if (a_ld % 4 || b_ld % 4 || g.a_seg % 4 || g.b_seg % 4 || g.b_batch % 4 || !aligned16(g.A) || !aligned16(g.B)) return false;
     // 128x128 tiles only when they still give every CU two workgroups (measured: at M = 128 / T = 20480 -- 160 big tiles --
     // they are 10 % slower than the 64x64 ones, at M = 256 / T = 204800 2 % faster)
-    if (use_big_tiles(g)) {
-        const dim3 gridb(g.N / BT, g.M / BT, g.nsplit * g.nbatch), blockb(256);
-        if (a_kc && b_nc) hipLaunchKernelGGL((k_gemm_big<true, true>), gridb, blockb, 0, st, g);
-        else if (a_kc) hipLaunchKernelGGL((k_gemm_big<true, false>), gridb, blockb, 0, st, g);
-        else if (b_nc) hipLaunchKernelGGL((k_gemm_big<false, true>), gridb, blockb, 0, st, g);
-        else hipLaunchKernelGGL((k_gemm_big<false, false>), gridb, blockb, 0, st, g);
-        return true;
-    }
-    const dim3 grid(g.N / GT, g.M / GT, g.nsplit * g.nbatch), block(256);
-    if (a_kc && b_nc) hipLaunchKernelGGL((k_gemm_fast<true, true>), grid, block, 0, st, g);
-    else if (a_kc) hipLaunchKernelGGL((k_gemm_fast<true, false>), grid, block, 0, st, g);
-    else if (b_nc) hipLaunchKernelGGL((k_gemm_fast<false, true>), grid, block, 0, st, g);
-    else hipLaunchKernelGGL((k_gemm_fast<false, false>), grid, block, 0, st, g);
+    typedef void (*Kern)(GemmArgs);
+    static const Kern big[2][2] = {{k_gemm_big<true, true>, k_gemm_big<true, false>}, {k_gemm_big<false, true>, k_gemm_big<false, false>}};     // [!a_kc][!b_nc]
+    static const Kern fast[2][2] = {{k_gemm_fast<true, true>, k_gemm_fast<true, false>}, {k_gemm_fast<false, true>, k_gemm_fast<false, false>}};
+    const bool bigt = use_big_tiles(g); const int t = bigt ? BT : GT;
+    hipLaunchKernelGGL((bigt ? big : fast)[!a_kc][!b_nc], dim3(g.N / t, g.M / t, g.nsplit * g.nbatch), dim3(256), 0, st, g);
     return true;
 }
 
@@ -421,30 +413,33 @@ static int splitk_chunk(long long K) {
     for (long long t = q; t < q + 64; ++t) if (K % (512 * t) == 0) return (int)(512 * t);
     return (int)(512 * q);
 }
-// split-K product(s) summed over many samples: out (+ b*out_batch) = alpha * A^T-style product, reduced in float64
-static int gemm(hipStream_t st, GemmArgs g, float* part_ws, size_t part_floats, float* out, double* out64, long long ldo,
-                double alpha, double beta, int tri, int nbatch = 1, long long b_batch = 0, long long s_batch = 0, long long out_batch = 0,
-                ReduceQueue* rq = nullptr, const float* add = nullptr, double add_coef = 0.0, int add_diag_inv = 0) {
+// where the sum of a split-K product goes, and how many products one launch holds
+struct GemmOut {
+    float* out; double* out64; long long ldo;               // out (+ b * out_batch) = alpha * sum of the splits; either output may be null
+    double alpha; int tri;
+    int nbatch; long long b_batch, s_batch, out_batch;      // nbatch products: B, scale and out advance by these per product
+    const float* add; double add_coef; int add_diag_inv;    // the KL rider of the reduction (ReduceArgs)
+};
+// split-K product(s) summed over many samples, reduced in float64: the partial sums take their own slice of the queue's workspace
+// and are summed by the queue's one launch (by a launch of their own once the queue is full)
+static int gemm(hipStream_t st, GemmArgs g, const GemmOut& o, ReduceQueue& rq) {
     const int kchunk = splitk_chunk(g.K);                   // 512 samples per split, more once that would exceed 256 splits
     g.nsplit = (g.K + kchunk - 1) / kchunk; g.kchunk = kchunk;
     if (g.nsplit < 2) { g.nsplit = 2; g.kchunk = round_up((g.K + 1) / 2, GK); if (g.kchunk < GK) g.kchunk = GK; }
-    g.kseg = g.K; g.a_seg = g.b_seg = g.s_seg = 0; g.nbatch = nbatch; g.b_batch = b_batch; g.s_batch = s_batch;
-    if (rq) {                                              // own slice of the workspace; summed by the queue's one launch
-        part_ws = rq->take((size_t)g.nsplit * nbatch * g.M * g.N);
-        if (!part_ws) { set_error("backward: split-K workspace too small"); return IWVI_ERR_ARG; }
-    } else if ((size_t)g.nsplit * nbatch * g.M * g.N > part_floats) { set_error("backward: split-K workspace too small"); return IWVI_ERR_ARG; }
+    g.kseg = g.K; g.a_seg = g.b_seg = g.s_seg = 0; g.nbatch = o.nbatch; g.b_batch = o.b_batch; g.s_batch = o.s_batch;
+    float* part_ws = rq.take((size_t)g.nsplit * o.nbatch * g.M * g.N);
+    if (!part_ws) { set_error("backward: split-K workspace too small"); return IWVI_ERR_ARG; }
     g.part = part_ws;
     if (!launch_fast(st, g)) {
-        for (int b = 0; b < nbatch; ++b) {
+        for (int b = 0; b < o.nbatch; ++b) {
             GemmArgs q = g;
-            q.B = g.B + b * b_batch; if (g.scale) q.scale = g.scale + b * s_batch;
+            q.B = g.B + b * o.b_batch; if (g.scale) q.scale = g.scale + b * o.s_batch;
             q.part = part_ws + (size_t)b * g.nsplit * g.M * g.N;
             hipLaunchKernelGGL(k_gemm, dim3((g.N + GT - 1) / GT, (g.M + GT - 1) / GT, g.nsplit), dim3(256), 0, st, q);
         }
     }
-    ReduceArgs r{part_ws, g.nsplit, g.M, g.N, out, out64, ldo, alpha, beta, tri, out_batch, add, add_coef, add_diag_inv};
-    if (rq && rq->push(r, nbatch)) return check_launch("k_gemm (split-K)");
-    hipLaunchKernelGGL(k_reduce_parts, dim3((g.M * g.N + 63) / 64, nbatch), dim3(256), 0, st, r);
+    ReduceArgs r{part_ws, g.nsplit, g.M, g.N, o.out, o.out64, o.ldo, o.alpha, 0.0, o.tri, o.out_batch, o.add, o.add_coef, o.add_diag_inv};
+    if (!rq.push(r, o.nbatch)) hipLaunchKernelGGL(k_reduce_parts, dim3((g.M * g.N + 63) / 64, o.nbatch), dim3(256), 0, st, r);
     return check_launch("k_gemm (split-K)");
 }
 // many rows, short K: direct store.  nseg > 1: the sum of nseg products (segment strides a_seg / b_seg / s_seg)
@@ -846,37 +841,30 @@ __global__ __launch_bounds__(256) void k_bw_mid(MidArgs a) {
         if (sub == 0) { a.Qx[t * Wq + D] = sdv_s[j]; a.Qx[t * Wq + D + 1] = skd; }
     }
 }
-template <int NP>
-static void launch_mid_d(hipStream_t st, const MidArgs& a, dim3 grid, size_t lds) {
-    if (a.D <= 8) hipLaunchKernelGGL((k_bw_mid<NP, 8>), grid, dim3(256), lds, st, a);
-    else if (a.D <= 16) hipLaunchKernelGGL((k_bw_mid<NP, 16>), grid, dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((k_bw_mid<NP, 32>), grid, dim3(256), lds, st, a);
-}
-// returns 1 if the fused kernel was launched, 0 if the shapes do not allow it, < 0 on error
-static int launch_mid(hipStream_t st, const MidArgs& a) {
-    const int M = a.M;
-    if (!a.GMV || M % 64 || M > 256 || M == 192 || a.T % 64 || a.Mp != M) return 0;
+// whether a layer call off the streaming chain takes the fused kernel (else the GEMM path): the forward's gmv block at hand, the
+// kernel's shapes, and its float4 loads of U, q_sqrt, LinvF and the C (= DA) buffer
+static bool mid_ok(const float* GMV, long long T, int M, int Mp, const float* U, const float* q_sqrt, const float* LinvF, const float* C) {
+    if (!GMV || M % 64 || M > 256 || M == 192 || T % 64 || Mp != M) return false;
     // measured (configs[1] / [2] / [3]): -3.5 % of the whole evaluation at M = 128, T = 20480; +7 % at T = 5120 (80 workgroups
     // for 256 CUs) and +10 % at M = 256 (105 KB of LDS: one workgroup per CU) -- so only where it wins, unless forced
-    if (!dbg_opt("IWVI_BW_FUSED") && (M > 128 || a.T < 16384)) return 0;
-    if (!aligned16(a.U) || !aligned16(a.q_sqrt) || !aligned16(a.LinvF) || !aligned16(a.C)) return 0;
-    const size_t lds = sizeof(float) * ((size_t)64 * (M + 4) + 4 * OPB + (size_t)64 * (2 * a.R + 1) + (size_t)64 * a.D);
+    if (!dbg_opt("IWVI_BW_FUSED") && (M > 128 || T < 16384)) return false;
+    return aligned16(U) && aligned16(q_sqrt) && aligned16(LinvF) && aligned16(C);
+}
+static int launch_mid(hipStream_t st, const MidArgs& a) {
+    typedef void (*Kern)(MidArgs);
+    static const Kern kern[3][3] = {{k_bw_mid<1, 8>, k_bw_mid<1, 16>, k_bw_mid<1, 32>},       // [M = 64, 128, 256][D <= 8, 16, 32]
+                                    {k_bw_mid<2, 8>, k_bw_mid<2, 16>, k_bw_mid<2, 32>},
+                                    {k_bw_mid<4, 8>, k_bw_mid<4, 16>, k_bw_mid<4, 32>}};
+    const size_t lds = sizeof(float) * ((size_t)64 * (a.M + 4) + 4 * OPB + (size_t)64 * (2 * a.R + 1) + (size_t)64 * a.D);
     static bool done = false;
     if (!done) {
         const size_t most = sizeof(float) * ((size_t)64 * 260 + 4 * OPB + (size_t)64 * (2 * IWVI_MAX_R + 1) + (size_t)64 * IWVI_MAX_D);
-        const void* fns[] = {(const void*)k_bw_mid<1, 8>, (const void*)k_bw_mid<1, 16>, (const void*)k_bw_mid<1, 32>,
-                             (const void*)k_bw_mid<2, 8>, (const void*)k_bw_mid<2, 16>, (const void*)k_bw_mid<2, 32>,
-                             (const void*)k_bw_mid<4, 8>, (const void*)k_bw_mid<4, 16>, (const void*)k_bw_mid<4, 32>};
-        for (const void* f : fns)
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most) != hipSuccess) { set_error("hipFuncSetAttribute(k_bw_mid)"); return IWVI_ERR_LAUNCH; }
+        for (const Kern* row : kern) for (int i = 0; i < 3; ++i)
+            if (hipFuncSetAttribute((const void*)row[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)most) != hipSuccess) { set_error("hipFuncSetAttribute(k_bw_mid)"); return IWVI_ERR_LAUNCH; }
         done = true;
     }
-    const dim3 grid((unsigned)(a.T / 64));
-    if (M == 64) launch_mid_d<1>(st, a, grid, lds);
-    else if (M == 128) launch_mid_d<2>(st, a, grid, lds);
-    else launch_mid_d<4>(st, a, grid, lds);
-    const int rc = check_launch("k_bw_mid");
-    return rc == IWVI_OK ? 1 : rc;
+    hipLaunchKernelGGL(kern[a.M == 64 ? 0 : (a.M == 128 ? 1 : 2)][a.D <= 8 ? 0 : (a.D <= 16 ? 1 : 2)], dim3((unsigned)(a.T / 64)), dim3(256), lds, st, a);
+    return check_launch("k_bw_mid");
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1749,6 +1737,20 @@ __global__ __launch_bounds__(256) void k_pack_bw(const float* __restrict__ q_sqr
                                                  unsigned short* __restrict__ SP16, const float* __restrict__ cst, float* __restrict__ spf, int own_qscale) {
     pack_bw_body((int)blockIdx.x, q_sqrt, Linv64, Mp, M, R, nbk, SP, LinvTP, SP16, cst, spf, own_qscale);
 }
+// The chain plan: everything the host decides about k_bw_chain for one layer shape and one arithmetic mode (f32_chain = the
+// descriptor's IWVI_BW_F32_CHAIN), in one value.  The sizing entries, the workspace layout, the prepare entries and the layer
+// driver all read it; nothing else derives any of it.  A shape off the chain (ok == false) has every other field zero.
+struct ChainPlan {
+    bool ok, fits;                      // ok: M a multiple of 16 up to 512, T a multiple of 16 (beyond M = 256: 32 samples per workgroup, or split f16);
+                                        // fits: and lds_bytes <= 160 KB -- the shape takes the chain (given the forward's gmv block)
+    bool s16, z_lds;                    // phase 1 on split-f16 operands (an even number of 16-row blocks: the state then carries the scales);
+                                        // the scaled inducing inputs staged in LDS (M <= 256; beyond, they stay in L2)
+    bool products;                      // the two M x M products over samples inside the kernel: only while the number of per-workgroup shares stays moderate
+    int ns_ws;                          // samples per workgroup / 16, the conservative choice (fits for any D, R, P): what the workspace is sized for
+    int ns, nsamp;                      // ... for this shape (>= ns_ws: never more shares than the workspace holds), and 16 ns
+    int DM, ts, dsz;                    // D bucket of the template; tile row stride (float4); floats of the staging region
+    size_t lds_bytes; long long shares_ws, shares;   // workgroups = per-workgroup partial sums: T / (16 ns_ws), T / nsamp
+};
 static int chain_ns_cap(long long T, int cap) {             // samples per workgroup / 16: as the forward's (every CU a workgroup), then down to a divisor of T
     int ns = (int)((T + 16 * 256 - 1) / (16 * 256));
     if (ns > cap) ns = cap;
@@ -1756,89 +1758,61 @@ static int chain_ns_cap(long long T, int cap) {             // samples per workg
     while (ns > 1 && T % (16 * ns)) --ns;
     return ns;
 }
-// the conservative choice (two [M x 16 NS] float tiles + staging in 160 KB of LDS for any D, R, P): what the workspace is sized for
-// phase 1 of the chain on split-f16 operands: an even number of 16-row blocks (the state then carries the scales); a third tile holds
-// the a planes, so beyond M = 256 only 16 samples fit a workgroup -- still faster than the fp32 phase 1 at 32 (configs[4]: 277 -> 240 ms per
-// value + gradient)
-// IWVI_BW_F32_CHAIN of the descriptor being served by this thread's current call (set at the entry points that take a descriptor;
-// the sizing functions, which take none, see the default -- the split-f16 chain needs the larger workspace)
-static thread_local bool t_bw_f32_chain = false;
-struct BwFlagScope { bool old; explicit BwFlagScope(int flags) : old(t_bw_f32_chain) { t_bw_f32_chain = (flags & IWVI_BW_F32_CHAIN) != 0; } ~BwFlagScope() { t_bw_f32_chain = old; } };
-static bool chain_s16(int M, int Mp) { return Mp == M && ((Mp / 16) & 1) == 0 && !t_bw_f32_chain; }
-static int chain_ns(long long T, int M = 128) { return chain_ns_cap(T, M <= 128 ? 5 : ((M > 256 && chain_s16(M, M)) ? 1 : 2)); }
-static bool chain_ok(int M, int Mp, long long T) {
+static int d_bucket(int D) { return D <= 8 ? 8 : (D <= 16 ? 16 : 32); }   // D bucket of the kernel-adjoint templates
+static ChainPlan chain_plan(long long T, int M, int D, int R, int P, bool f32_chain) {
+    ChainPlan p{};
+    if (M % 16 || M > 512 || T % 16) return p;
+    const bool s16 = ((M / 16) & 1) == 0 && !f32_chain;
+    // the conservative choice (two [M x 16 NS] float tiles + staging in 160 KB of LDS for any D, R, P).  On split-f16 operands a third
+    // tile holds the a planes, so beyond M = 256 only 16 samples fit a workgroup -- still faster than the fp32 phase 1 at 32
+    // (configs[4]: 277 -> 240 ms per value + gradient)
+    const int ns_ws = chain_ns_cap(T, M <= 128 ? 5 : ((M > 256 && s16) ? 1 : 2));
     // M > 256: only with 32 samples per workgroup (two [M x 32] tiles; the scaled inducing inputs then stay in L2) -- at 16 every packed
     // S_r block (R * 32 * 32 KiB per layer) would be fetched from L2 for 4 MFMAs: measured 383 ms per value + gradient at configs[4]
     // against 359 ms on the GEMM path
-    return Mp == M && M <= 512 && (T % 16) == 0 && (M <= 256 || chain_ns(T, M) >= 2 || chain_s16(M, Mp));
-}
-// floats of the staging region beside the two tiles: what is staged there before (heads) / after (kernel adjoint: x~ rows, z~, shares)
-static bool chain_z_lds(int M) { return M <= 256; }
-static int chain_dsz(int NSAMP, int M, int D, int R, int P, int DM, bool z_lds = true) {
-    const int heads = 3 * NSAMP * P + P * R + 4 * NSAMP * R + D * P, adj = NSAMP * round_up(D + 2, 4) + (z_lds ? M * DM : 0) + 16 * NSAMP;
-    return ((heads > adj ? heads : adj) + 3) & ~3;
-}
-// LDS bytes of k_bw_chain for a layer shape and a tile row stride ts (float4)
-static size_t chain_lds_bytes_ts(int NSAMP, int ts, int M, int D, int R, int P) {
-    const int DM = D <= 8 ? 8 : (D <= 16 ? 16 : 32);
-    return sizeof(float) * ((size_t)(chain_s16(M, round_up(M, 16)) ? 3 : 2) * ts * M + (size_t)chain_dsz(NSAMP, M, D, R, P, DM, M <= 256) + (size_t)M * R + (size_t)NSAMP * (2 * R + 1) + (size_t)NSAMP * D
-                            + (size_t)NSAMP * DM + DM + (size_t)NSAMP * (D + 2));
-}
-// the padded row stride where it fits, else the plain one
-static int chain_ts(int NSAMP, int M, int D, int R, int P) { return chain_lds_bytes_ts(NSAMP, NSAMP + 4, M, D, R, P) <= 160 * 1024 ? NSAMP + 4 : NSAMP; }
-// samples per workgroup / 16 for a layer shape: 128 < M <= 256 takes 64 samples where the shape's tiles and staging fit (every packed
-// S_r block fetched from L2 then feeds 16 MFMAs instead of 8), else the conservative choice.  Never fewer workgroups than chain_ns()
-// implies more partial sums: the workspace (sized with chain_ns) covers both.
-static int chain_ns_shape(long long T, int M, int D, int R, int P) {
-    const int base = chain_ns(T, M);
+    if (M > 256 && ns_ws < 2 && !s16) return p;
+    p.ok = true; p.s16 = s16; p.ns_ws = ns_ws; p.z_lds = M <= 256;
+    p.DM = d_bucket(D);
+    // floats of the staging region beside the tiles: what is staged there before (heads) / after (kernel adjoint: x~ rows, z~, shares)
+    auto dsz = [&](int nsamp) {
+        const int heads = 3 * nsamp * P + P * R + 4 * nsamp * R + D * P, adj = nsamp * round_up(D + 2, 4) + (p.z_lds ? M * p.DM : 0) + 16 * nsamp;
+        return ((heads > adj ? heads : adj) + 3) & ~3;
+    };
+    auto lds = [&](int nsamp, int ts) {                    // LDS bytes for a tile row stride ts (float4)
+        return sizeof(float) * ((size_t)(s16 ? 3 : 2) * ts * M + (size_t)dsz(nsamp) + (size_t)M * R + (size_t)nsamp * (2 * R + 1) + (size_t)nsamp * D
+                                + (size_t)nsamp * p.DM + p.DM + (size_t)nsamp * (D + 2));
+    };
+    // 128 < M <= 256 takes 64 samples where the shape's tiles and staging fit (every packed S_r block fetched from L2 then feeds 16 MFMAs
+    // instead of 8), else the conservative choice
+    p.ns = ns_ws;
     if (M > 128 && M <= 256) {
         const int ns4 = chain_ns_cap(T, 4);
-        if (ns4 > base && chain_lds_bytes_ts(16 * ns4, 16 * ns4, M, D, R, P) <= 160 * 1024) return ns4;
+        if (ns4 > ns_ws && lds(16 * ns4, 16 * ns4) <= 160 * 1024) p.ns = ns4;
     }
-    return base;
+    p.nsamp = 16 * p.ns;
+    p.ts = lds(p.nsamp, p.nsamp + 4) <= 160 * 1024 ? p.nsamp + 4 : p.nsamp;     // the padded row stride where it fits, else the plain one
+    p.dsz = dsz(p.nsamp); p.lds_bytes = lds(p.nsamp, p.ts);
+    p.fits = p.lds_bytes <= 160 * 1024;
+    p.shares_ws = T / (16 * ns_ws); p.shares = T / p.nsamp;
+    p.products = M <= 128 && p.shares_ws <= 1024;
+    return p;
 }
-static size_t chain_lds_bytes(long long T, int M, int D, int R, int P) {
-    const int NSAMP = 16 * chain_ns_shape(T, M, D, R, P);
-    return chain_lds_bytes_ts(NSAMP, chain_ts(NSAMP, M, D, R, P), M, D, R, P);
-}
-static bool chain_fits(long long T, int M, int Mp, int D, int R, int P) { return chain_ok(M, Mp, T) && chain_lds_bytes(T, M, D, R, P) <= 160 * 1024; }
-// the two M x M products over samples inside the chain kernel: only while the number of per-workgroup shares stays moderate
-static bool chain_products_ok(int M, long long T) {
-    return chain_ok(M, round_up(M, 16), T) && M <= 128 && T / (16 * chain_ns(T, M)) <= 1024;
-}
-template <int NS>
-static int launch_chain_ns(hipStream_t st, ChainArgs a) {
-    constexpr int NSAMP = 16 * NS;
-    const int DM = a.D <= 8 ? 8 : (a.D <= 16 ? 16 : 32);
-    a.z_lds = chain_z_lds(a.M) ? 1 : 0;
-    a.s16 = chain_s16(a.M, a.Mp) ? 1 : 0;
-    a.p5h = (a.s16 && !dbg_opt("IWVI_BW_P5_F32")) ? 1 : 0;
-    a.dsz = chain_dsz(NSAMP, a.M, a.D, a.R, a.P, DM, a.M <= 256);
-    a.ts = chain_ts(NSAMP, a.M, a.D, a.R, a.P);
-    const size_t lds = chain_lds_bytes_ts(NSAMP, a.ts, a.M, a.D, a.R, a.P);
-    static bool done = false;
-    if (!done) {
-        const size_t most = 160 * 1024;
-        const void* fns[] = {(const void*)k_bw_chain<NS, 8>, (const void*)k_bw_chain<NS, 16>, (const void*)k_bw_chain<NS, 32>};
-        for (const void* f : fns)
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most) != hipSuccess) { set_error("hipFuncSetAttribute(k_bw_chain)"); return IWVI_ERR_LAUNCH; }
-        done = true;
+static int launch_chain(hipStream_t st, const ChainArgs& a, const ChainPlan& cp) {
+    typedef void (*Kern)(ChainArgs);
+    static const Kern kern[5][3] = {{k_bw_chain<1, 8>, k_bw_chain<1, 16>, k_bw_chain<1, 32>},  // [ns - 1][DM = 8, 16, 32]
+                                    {k_bw_chain<2, 8>, k_bw_chain<2, 16>, k_bw_chain<2, 32>},
+                                    {k_bw_chain<3, 8>, k_bw_chain<3, 16>, k_bw_chain<3, 32>},
+                                    {k_bw_chain<4, 8>, k_bw_chain<4, 16>, k_bw_chain<4, 32>},
+                                    {k_bw_chain<5, 8>, k_bw_chain<5, 16>, k_bw_chain<5, 32>}};
+    static bool done[5] = {false, false, false, false, false};
+    const Kern* row = kern[cp.ns - 1];
+    if (!done[cp.ns - 1]) {
+        for (int i = 0; i < 3; ++i)
+            if (hipFuncSetAttribute((const void*)row[i], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) { set_error("hipFuncSetAttribute(k_bw_chain)"); return IWVI_ERR_LAUNCH; }
+        done[cp.ns - 1] = true;
     }
-    if (lds > 160 * 1024) { set_error("k_bw_chain: %zu B of LDS", lds); return IWVI_ERR_UNSUPPORTED; }
-    const dim3 grid((unsigned)(a.T / NSAMP)), block(512);
-    if (a.D <= 8) hipLaunchKernelGGL((k_bw_chain<NS, 8>), grid, block, lds, st, a);
-    else if (a.D <= 16) hipLaunchKernelGGL((k_bw_chain<NS, 16>), grid, block, lds, st, a);
-    else hipLaunchKernelGGL((k_bw_chain<NS, 32>), grid, block, lds, st, a);
+    hipLaunchKernelGGL(row[cp.DM == 8 ? 0 : (cp.DM == 16 ? 1 : 2)], dim3((unsigned)cp.shares), dim3(512), cp.lds_bytes, st, a);
     return check_launch("k_bw_chain");
-}
-static int launch_chain(hipStream_t st, const ChainArgs& a) {
-    switch (chain_ns_shape(a.T, a.M, a.D, a.R, a.P)) {
-        case 1: return launch_chain_ns<1>(st, a);
-        case 2: return launch_chain_ns<2>(st, a);
-        case 3: return launch_chain_ns<3>(st, a);
-        case 4: return launch_chain_ns<4>(st, a);
-        default: return launch_chain_ns<5>(st, a);
-    }
 }
 // dq_sqrt[r] = tril(sym(G_r) L_r) + add_coef * (L_r - diag(1 / L_ii)),  G_r given by its lower triangle (the reduced split-K SYRK):
 // 16x16 output tile per workgroup, operands through LDS, k from the tile's first column (L_r is lower triangular).
@@ -1920,20 +1894,17 @@ __global__ __launch_bounds__(256) void k_thin(ThinArgs a) {
 
 // out[m, n] = sum_t X[t, m] Y[t, n] (n < N) and, with ones, out[m, N] = sum_t X[t, m];  out is [M, N + ones]
 static int thin(hipStream_t st, const float* X, long long ldx, int M, const float* Y, long long ldy, int N, int ones, long long T,
-                float* part_ws, size_t part_floats, float* out, int ldo = 0, ReduceQueue* rq = nullptr,
-                const float* add = nullptr, double add_coef = 0.0) {
+                float* out, ReduceQueue& rq, int ldo = 0, const float* add = nullptr, double add_coef = 0.0) {
     if (ldo == 0) ldo = N + ones;
     if (N > 32) {                                          // columns of Y in two passes (LDS budget of k_thin)
-        int rc = thin(st, X, ldx, M, Y, ldy, 32, 0, T, part_ws, part_floats, out, ldo, rq, add, add_coef);
+        int rc = thin(st, X, ldx, M, Y, ldy, 32, 0, T, out, rq, ldo, add, add_coef);
         if (rc != IWVI_OK) return rc;
-        return thin(st, X, ldx, M, Y + 32, ldy, N - 32, ones, T, part_ws, part_floats, out + 32, ldo, rq, add ? add + 32 : nullptr, add_coef);
+        return thin(st, X, ldx, M, Y + 32, ldy, N - 32, ones, T, out + 32, rq, ldo, add ? add + 32 : nullptr, add_coef);
     }
     const int chunks = thin_chunks(T);
     const int nblk = (int)((T + (long long)THIN_ROWS * chunks - 1) / ((long long)THIN_ROWS * chunks)), NN = N + ones;
-    if (rq) {
-        part_ws = rq->take((size_t)nblk * M * NN);
-        if (!part_ws) { set_error("backward: thin-reduction workspace too small"); return IWVI_ERR_ARG; }
-    } else if ((size_t)nblk * M * NN > part_floats) { set_error("backward: thin-reduction workspace too small"); return IWVI_ERR_ARG; }
+    float* part_ws = rq.take((size_t)nblk * M * NN);        // own slice of the workspace; summed by the queue's one launch
+    if (!part_ws) { set_error("backward: thin-reduction workspace too small"); return IWVI_ERR_ARG; }
     ThinArgs a{X, ldx, Y, ldy, N, ones, T, M, part_ws, chunks};
     const dim3 grid(nblk), block(256);
     if (N <= 1) hipLaunchKernelGGL(k_thin<1>, grid, block, 0, st, a);
@@ -1941,8 +1912,7 @@ static int thin(hipStream_t st, const float* X, long long ldx, int M, const floa
     else if (N <= 16) hipLaunchKernelGGL(k_thin<16>, grid, block, 0, st, a);
     else hipLaunchKernelGGL(k_thin<32>, grid, block, 0, st, a);
     ReduceArgs r{part_ws, nblk, M, NN, out, nullptr, ldo, 1.0, 0.0, 0, 0, add, add_coef, 0};
-    if (rq && rq->push(r, 1)) return check_launch("k_thin");
-    hipLaunchKernelGGL(k_reduce_parts, dim3((M * NN + 63) / 64, 1), dim3(256), 0, st, r);
+    if (!rq.push(r, 1)) hipLaunchKernelGGL(k_reduce_parts, dim3((M * NN + 63) / 64, 1), dim3(256), 0, st, r);
     return check_launch("k_thin");
 }
 
@@ -2084,7 +2054,9 @@ struct BwdWs {
     unsigned short* SP16; float* spf;   // split-f16 image of S_r and its per-r factors (even nbk)
     size_t part_floats, bytes;
 };
-static BwdWs bwd_layout(char* base, long long T, int M, int D, int R) {
+// (cp: the chain plan of the call's arithmetic mode -- the share regions below differ between the modes beyond M = 256; only its
+// shape-only fields ok / products / shares_ws are read)
+static BwdWs bwd_layout(char* base, long long T, int M, int D, int R, const ChainPlan& cp) {
     BwdWs w; size_t o = 0;
     auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o = align256(o + bytes); return p; };
     const int nsplit = (int)((T + splitk_chunk(T) - 1) / splitk_chunk(T)) + 2;
@@ -2092,12 +2064,12 @@ static BwdWs bwd_layout(char* base, long long T, int M, int D, int R) {
     w.DA = (float*)take(sizeof(float) * T * M); w.DK = (float*)take(sizeof(float) * T * M);
     w.Qx = (float*)take(sizeof(float) * T * (D + 2));
     w.part_floats = (size_t)nsplit * M * M * (R + 1);          // dLm + the R batched dL_r, parked together
-    if (chain_products_ok(M, T)) {                               // the chain kernel's per-workgroup shares of dLm and G_r instead
-        const size_t need = (size_t)(T / (16 * chain_ns(T, M))) * M * M * (R + 1);
+    if (cp.products) {                                           // the chain kernel's per-workgroup shares of dLm and G_r instead
+        const size_t need = (size_t)cp.shares_ws * M * M * (R + 1);
         if (need > w.part_floats) w.part_floats = need;
     }
-    if (chain_ok(M, round_up(M, 16), T)) {                        // + its per-workgroup shares of the thin sums
-        const size_t S = (size_t)(T / (16 * chain_ns(T, M)));
+    if (cp.ok) {                                                  // + its per-workgroup shares of the thin sums
+        const size_t S = (size_t)cp.shares_ws;
         w.part_floats += S * ((size_t)M * (R + D + 1) + D + 2 + 3 * (size_t)IWVI_MAX_P * R + 2 * (size_t)D * IWVI_MAX_P) + 64 * 8;
     }
     {   // thin reductions: ceil(T / THIN_ROWS) chunks of at most [max(M, 34)][33]
@@ -2245,7 +2217,7 @@ struct EncBwdArgs {
 };
 constexpr int ER = 4, ELD = 65;         // rows per workgroup, row stride of an activation tile in LDS
 constexpr int EW_MAX = IWVI_MAX_ENC * (64 * 64 + 64);   // LDS copy of the weights and biases (widths <= 64)
-// 8 rows per workgroup (128 workgroups at B = 1024: the phase is latency-bound), activations, deltas AND the weights in LDS
+// ER = 4 rows per workgroup (256 workgroups at B = 1024: the phase is latency-bound), activations, deltas AND the weights in LDS
 // (weights read from global memory inside the dot-product loops cost an L1 round trip per term), threads over (row, unit)
 __global__ __launch_bounds__(256) void k_enc_bwd(EncBwdArgs a) {
     extern __shared__ float esm[];
@@ -2627,44 +2599,47 @@ using namespace iwvi;
 // flags (IWVI_BW_F32_CHAIN): u is needed when either mode's adjoint reads it, the workspace is the larger of the two layouts.
 extern "C" int iwvi_gp_layer_backward_needs_u(int64_t T, int M, int D, int R, int P) {
     if (T <= 0 || M <= 0 || D <= 0 || R <= 0 || P <= 0) return 1;
-    bool fits_s16, fits_f32;
-    { const BwFlagScope sc(0); fits_s16 = chain_fits(T, M, round_up(M, 16), D, R, P); }
-    { const BwFlagScope sc(IWVI_BW_F32_CHAIN); fits_f32 = chain_fits(T, M, round_up(M, 16), D, R, P); }
-    return (fits_s16 && fits_f32) ? 0 : 1;
+    return (chain_plan(T, M, D, R, P, false).fits && chain_plan(T, M, D, R, P, true).fits) ? 0 : 1;
 }
-
 extern "C" size_t iwvi_gp_layer_backward_ws_bytes(int64_t T, int M, int D, int R) {
     if (T <= 0 || M <= 0 || D <= 0 || R <= 0) return 0;
-    size_t b_s16, b_f32;
-    { const BwFlagScope sc(0); b_s16 = bwd_layout(nullptr, T, M, D, R).bytes; }
-    { const BwFlagScope sc(IWVI_BW_F32_CHAIN); b_f32 = bwd_layout(nullptr, T, M, D, R).bytes; }
+    const size_t b_s16 = bwd_layout(nullptr, T, M, D, R, chain_plan(T, M, D, R, R, false)).bytes;      // (the layout reads the plan's shape-only fields: any P serves)
+    const size_t b_f32 = bwd_layout(nullptr, T, M, D, R, chain_plan(T, M, D, R, R, true)).bytes;
     return b_s16 > b_f32 ? b_s16 : b_f32;
 }
 
 // What the adjoint of a layer needs besides the forward's outputs: scaled inducing inputs, a float32 Lm^-1, and for the
 // streaming chain the packed S_r / Lm^-T operands.  Depends only on the parameters and the dense factors, so a caller may
 // queue it early on another stream (beside the forward) and pass desc.prepared = 1 to iwvi_gp_layer_backward.
-extern "C" int iwvi_gp_layer_backward_prepare(const iwvi_gp_bwd_desc* dp, int64_t T, void* ws_, void* stream_) {
-    if (!dp || !ws_ || T <= 0) { set_error("iwvi_gp_layer_backward_prepare: bad argument"); return IWVI_ERR_ARG; }
-    const iwvi_gp_bwd_desc& d = *dp;
-    const BwFlagScope flag_scope(d.flags);
-    if (!d.state || !d.Z || !d.lengthscales || !d.q_sqrt || d.M <= 0 || d.M > IWVI_MAX_M || d.D <= 0 || d.D > IWVI_MAX_D || d.R <= 0 || d.R > IWVI_MAX_R) {
-        set_error("iwvi_gp_layer_backward_prepare: null input or size out of range"); return IWVI_ERR_ARG;
-    }
-    hipStream_t st = (hipStream_t)stream_;
+static bool prep_desc_ok(const iwvi_gp_bwd_desc& d) {
+    return d.state && d.Z && d.lengthscales && d.q_sqrt && d.M > 0 && d.M <= IWVI_MAX_M && d.D > 0 && d.D <= IWVI_MAX_D && d.R > 0 && d.R <= IWVI_MAX_R;
+}
+// one layer's operands and block counts (npack == 0: the shape is off the chain, nothing to pack)
+static PrepOne prep_one(const iwvi_gp_bwd_desc& d, long long T, void* ws) {
     const int M = d.M, D = d.D, R = d.R;
     const StateLayout sl = state_layout(M, R);
-    const int Mp = sl.Mp;
-    const double* Linv64 = (const double*)((const char*)d.state + sl.off_Linv);
-    BwdWs w = bwd_layout((char*)ws_, T, M, D, R);
-    const int n = M * M > M * D ? M * M : M * D;
-    hipLaunchKernelGGL(k_prep, dim3((n + 255) / 256), dim3(256), 0, st, d.Z, d.lengthscales, Linv64, Mp, w.Zt, w.invls, w.LinvF, M, D);
-    if (chain_fits(T, M, Mp, D, R, d.P > 0 ? d.P : R)) {
-        const int nbk = Mp / 16;
-        const bool s16 = chain_s16(M, Mp);
-        hipLaunchKernelGGL(k_pack_bw, dim3((unsigned)(R * nbk * nbk + tri_blocks(nbk))), dim3(256), 0, st, d.q_sqrt, Linv64, Mp, M, R, nbk, w.SP, w.LinvTP,
-                           s16 ? w.SP16 : (unsigned short*)nullptr, (const float*)((const char*)d.state + sl.off_cst), w.spf, (d.flags & IWVI_BW_OWN_QSCALE) ? 1 : 0);
-    }
+    const ChainPlan cp = chain_plan(T, M, D, R, d.P > 0 ? d.P : R, (d.flags & IWVI_BW_F32_CHAIN) != 0);
+    const BwdWs w = bwd_layout((char*)ws, T, M, D, R, cp);
+    PrepOne L{};
+    L.Z = d.Z; L.ls = d.lengthscales; L.Linv64 = (const double*)((const char*)d.state + sl.off_Linv); L.q_sqrt = d.q_sqrt;
+    L.cst = (const float*)((const char*)d.state + sl.off_cst);
+    L.Zt = w.Zt; L.invls = w.invls; L.LinvF = w.LinvF; L.SP = w.SP; L.LinvTP = w.LinvTP; L.spf = w.spf;
+    L.Mp = sl.Mp; L.M = M; L.D = D; L.R = R; L.nbk = sl.Mp / 16;
+    const int nn = M * M > M * D ? M * M : M * D;
+    L.nprep = (nn + 255) / 256;
+    L.npack = cp.fits ? R * L.nbk * L.nbk + tri_blocks(L.nbk) : 0;
+    L.SP16 = (cp.fits && cp.s16) ? w.SP16 : (unsigned short*)nullptr;
+    L.own_qscale = (d.flags & IWVI_BW_OWN_QSCALE) ? 1 : 0;
+    return L;
+}
+extern "C" int iwvi_gp_layer_backward_prepare(const iwvi_gp_bwd_desc* dp, int64_t T, void* ws_, void* stream_) {
+    if (!dp || !ws_ || T <= 0) { set_error("iwvi_gp_layer_backward_prepare: bad argument"); return IWVI_ERR_ARG; }
+    if (!prep_desc_ok(*dp)) { set_error("iwvi_gp_layer_backward_prepare: null input or size out of range"); return IWVI_ERR_ARG; }
+    hipStream_t st = (hipStream_t)stream_;
+    const PrepOne L = prep_one(*dp, T, ws_);
+    hipLaunchKernelGGL(k_prep, dim3(L.nprep), dim3(256), 0, st, L.Z, L.ls, L.Linv64, L.Mp, L.Zt, L.invls, L.LinvF, L.M, L.D);
+    if (L.npack)
+        hipLaunchKernelGGL(k_pack_bw, dim3((unsigned)L.npack), dim3(256), 0, st, L.q_sqrt, L.Linv64, L.Mp, L.M, L.R, L.nbk, L.SP, L.LinvTP, L.SP16, L.cst, L.spf, L.own_qscale);
     return check_launch("iwvi_gp_layer_backward_prepare");
 }
 
@@ -2675,27 +2650,10 @@ extern "C" int iwvi_gp_layers_backward_prepare(const iwvi_gp_bwd_desc* descs, in
     unsigned grid = 0;
     for (int i = 1; i < n; ++i)                                    // (one launch for all layers: one arithmetic mode)
         if ((descs[i].flags ^ descs[0].flags) & IWVI_BW_F32_CHAIN) { set_error("iwvi_gp_layers_backward_prepare: layer %d asks for another arithmetic mode (IWVI_BW_F32_CHAIN) than layer 0", i); return IWVI_ERR_ARG; }
-    const BwFlagScope flag_scope(descs[0].flags);
     for (int i = 0; i < n; ++i) {
-        const iwvi_gp_bwd_desc& d = descs[i];
-        if (!ws[i] || !d.state || !d.Z || !d.lengthscales || !d.q_sqrt || d.M <= 0 || d.M > IWVI_MAX_M || d.D <= 0 || d.D > IWVI_MAX_D || d.R <= 0 || d.R > IWVI_MAX_R) {
-            set_error("iwvi_gp_layers_backward_prepare: layer %d: null input or size out of range", i); return IWVI_ERR_ARG;
-        }
-        const int M = d.M, D = d.D, R = d.R;
-        const StateLayout sl = state_layout(M, R);
-        BwdWs w = bwd_layout((char*)ws[i], T, M, D, R);
-        PrepOne& L = a.L[i];
-        L.Z = d.Z; L.ls = d.lengthscales; L.Linv64 = (const double*)((const char*)d.state + sl.off_Linv); L.q_sqrt = d.q_sqrt;
-        L.cst = (const float*)((const char*)d.state + sl.off_cst);
-        L.Zt = w.Zt; L.invls = w.invls; L.LinvF = w.LinvF; L.SP = w.SP; L.LinvTP = w.LinvTP; L.spf = w.spf;
-        L.Mp = sl.Mp; L.M = M; L.D = D; L.R = R; L.nbk = sl.Mp / 16;
-        const int nn = M * M > M * D ? M * M : M * D;
-        L.nprep = (nn + 255) / 256;
-        const bool chain = chain_fits(T, M, sl.Mp, D, R, d.P > 0 ? d.P : R);
-        L.npack = chain ? R * L.nbk * L.nbk + tri_blocks(L.nbk) : 0;
-        L.SP16 = (chain && chain_s16(M, sl.Mp)) ? w.SP16 : (unsigned short*)nullptr;
-        L.own_qscale = (d.flags & IWVI_BW_OWN_QSCALE) ? 1 : 0;
-        grid += (unsigned)(L.nprep + L.npack);
+        if (!ws[i] || !prep_desc_ok(descs[i])) { set_error("iwvi_gp_layers_backward_prepare: layer %d: null input or size out of range", i); return IWVI_ERR_ARG; }
+        a.L[i] = prep_one(descs[i], T, ws[i]);
+        grid += (unsigned)(a.L[i].nprep + a.L[i].npack);
     }
     hipLaunchKernelGGL(k_prepare_all, dim3(grid), dim3(256), 0, (hipStream_t)stream_, a);
     return check_launch("iwvi_gp_layers_backward_prepare");
@@ -2717,255 +2675,297 @@ extern "C" int iwvi_debug_last_backward_routes(int* out_host, int max) {
     g_bw_nroute = 0;
     return n;
 }
-extern "C" int iwvi_gp_layer_backward(const iwvi_gp_bwd_desc* dp, int64_t T, void* ws_, void* stream_) {
-    if (!dp || !ws_ || T <= 0) { set_error("iwvi_gp_layer_backward: bad argument"); return IWVI_ERR_ARG; }
-    const iwvi_gp_bwd_desc& d = *dp;
-    const BwFlagScope flag_scope(d.flags);
-    if (!d.state || !d.Z || !d.lengthscales || !d.q_mu || !d.q_sqrt || !d.F || !d.A) { set_error("iwvi_gp_layer_backward: null input"); return IWVI_ERR_ARG; }
-    if (d.M <= 0 || d.M > IWVI_MAX_M || d.D <= 0 || d.D > IWVI_MAX_D || d.R <= 0 || d.R > IWVI_MAX_R || d.P <= 0 || d.P > IWVI_MAX_P || T >= (1LL << 31) / (d.M > d.D ? d.M : d.D)) {
-        set_error("iwvi_gp_layer_backward: size out of range"); return IWVI_ERR_ARG;
+
+// The layer adjoint's driver.  Everything a call decides is in two values made before its first launch -- the ChainPlan of its shape
+// and arithmetic mode and the RoutePlan below -- and iwvi_gp_layer_backward is a sequence of steps that read them.
+struct RoutePlan {
+    int route;                          // IWVI_BW_ROUTE_CHAIN: the streaming chain (no saved u_r; needs the forward's gmv block and a shape that fits);
+                                        // _MID: k_bw_mid, heads + DA + dK + kernel adjoint in one launch (mid_ok);  _GEMM: every other call
+    // q_any: only dq_mu / dq_sqrt asked for (the natural-gradient op, build_models.py:288-295, moves nothing else); off the chain the GEMM
+    // route then runs the heads and two products.  q_only: the same on the chain -- heads + two sums over samples, no da / dk, no kernel
+    // adjoint, no adjoint of the factorisation, nothing of iwvi_gp_layer_backward_prepare (the state may be the packed one: the dense
+    // factors are not read).
+    bool q_any, q_only;
+    // desc.phase splits a chain call where dF is queued: 1 = the per-sample chain only, 2 = the parameter branch only (same descriptor, same
+    // workspace; the caller orders 2 after 1 -- on any stream -- and may queue other work in between: a captured graph then keeps the layers'
+    // chains on one hardware queue).  Every other call does everything in phase 1: 0, or -1 (nothing left to do) when asked for phase 2.
+    int phase;
+    bool prod;                          // chain route: the dLm and G_r shares come out of the chain kernel (no DK / A round trip, no split-K launches)
+    bool two_q; size_t partA;           // two side streams: branch A's reduction has its own queue, the first partA floats of the share region
+    bool lin_on;                        // gradients of the mixing matrix and / or the linear mean function
+};
+static RoutePlan route_plan(const iwvi_gp_bwd_desc& d, long long T, int Mp, const ChainPlan& cp, const BwdWs& w) {
+    RoutePlan rp{};
+    const bool chain = d.GMV && cp.fits;
+    rp.q_any = !d.dZ && !d.dls && !d.dvariance && !d.dF && !d.dW && !d.dmf_A;
+    rp.q_only = rp.q_any && chain;
+    rp.phase = (rp.q_only || !chain) ? (d.phase == 2 ? -1 : 0) : d.phase;
+    rp.route = chain ? IWVI_BW_ROUTE_CHAIN
+             : (!rp.q_any && mid_ok(d.GMV, T, d.M, Mp, d.U, d.q_sqrt, w.LinvF, w.DA)) ? IWVI_BW_ROUTE_MID : IWVI_BW_ROUTE_GEMM;
+    rp.prod = chain && cp.products;
+    rp.two_q = d.side_stream && d.side_stream2 && d.side_stream2 != d.side_stream;
+    if (rp.two_q) {                                        // dLm's split-K partial sums, or the chain's shares of it where the workspace holds those
+        rp.partA = (size_t)((T + splitk_chunk(T) - 1) / splitk_chunk(T) + 2) * d.M * d.M;
+        if (d.GMV && cp.products && (size_t)cp.shares_ws * d.M * d.M > rp.partA) rp.partA = (size_t)cp.shares_ws * d.M * d.M;
     }
+    rp.lin_on = (d.dW && d.W) || (d.dmf_A && d.mf_type == IWVI_MF_LINEAR);
+    return rp;
+}
+// one call: the descriptor, its plans, and what the steps hand each other
+struct BwCall {
+    const iwvi_gp_bwd_desc& d; const long long T; const int M, D, R;
+    const StateLayout sl; const int Mp;
+    const ChainPlan cp; const BwdWs w; const RoutePlan rp;
+    ReduceQueue rqA, rqB;               // deferred reductions: every product over samples parks its partial sums in its own slice of the workspace
+    float* s[3] = {nullptr, nullptr, nullptr}; float* a12[2] = {nullptr, nullptr};     // the reduced sums behind dW / dmf_A (k_bw_final reads them)
+    BwCall(const iwvi_gp_bwd_desc& d_, long long T_, void* ws)
+        : d(d_), T(T_), M(d_.M), D(d_.D), R(d_.R), sl(state_layout(M, R)), Mp(sl.Mp),
+          cp(chain_plan(T, M, D, R, d.P, (d.flags & IWVI_BW_F32_CHAIN) != 0)), w(bwd_layout((char*)ws, T, M, D, R, cp)), rp(route_plan(d, T, Mp, cp, w)),
+          rqA(w.part, rp.partA), rqB(w.part + rp.partA, w.part_floats - rp.partA) {}
+};
+static int bw_check_desc(const iwvi_gp_bwd_desc& d, long long T) {
+    if (!d.state || !d.Z || !d.lengthscales || !d.q_mu || !d.q_sqrt || !d.F || !d.A) { set_error("iwvi_gp_layer_backward: null input"); return IWVI_ERR_ARG; }
+    const bool size_ok = d.M > 0 && d.M <= IWVI_MAX_M && d.D > 0 && d.D <= IWVI_MAX_D && d.R > 0 && d.R <= IWVI_MAX_R && d.P > 0 && d.P <= IWVI_MAX_P && T < (1LL << 31) / (d.M > d.D ? d.M : d.D);
+    if (!size_ok) { set_error("iwvi_gp_layer_backward: size out of range"); return IWVI_ERR_ARG; }
     if (d.kern_type != IWVI_KERN_RBF && d.kern_type != IWVI_KERN_MATERN52) { set_error("iwvi_gp_layer_backward: unknown kernel type %d", d.kern_type); return IWVI_ERR_UNSUPPORTED; }
     if (!d.W && d.P != d.R) { set_error("iwvi_gp_layer_backward: P != R without a mixing matrix"); return IWVI_ERR_ARG; }
     if (d.mf_type == IWVI_MF_LINEAR && !d.mf_A) { set_error("iwvi_gp_layer_backward: linear mean function without A"); return IWVI_ERR_ARG; }
     if (d.mf_type == IWVI_MF_IDENTITY && d.P != d.D) { set_error("iwvi_gp_layer_backward: identity mean function needs P == D"); return IWVI_ERR_ARG; }
     if (d.d_sample && !d.noise) { set_error("iwvi_gp_layer_backward: d_sample needs the forward's draws"); return IWVI_ERR_ARG; }
-    hipStream_t st = (hipStream_t)stream_;
-    const int M = d.M, D = d.D, R = d.R;
-    const StateLayout sl = state_layout(M, R);
-    const int Mp = sl.Mp;
-    const double* Lm64 = (const double*)((const char*)d.state + sl.off_Lm);
-    const double* Linv64 = (const double*)((const char*)d.state + sl.off_Linv);
-    BwdWs w = bwd_layout((char*)ws_, T, M, D, R);
-    int rc;
-    // Only dq_mu / dq_sqrt asked for (the natural-gradient op, build_models.py:288-295, moves nothing else): on the streaming chain's
-    // shapes that is the heads + two sums over samples -- no da / dk, no kernel adjoint, no adjoint of the factorisation, and
-    // nothing of iwvi_gp_layer_backward_prepare (the state may then be the packed one: the dense factors are not read).
-    const bool q_any = !d.dZ && !d.dls && !d.dvariance && !d.dF && !d.dW && !d.dmf_A;
-    const bool q_only = q_any && d.GMV && chain_fits(T, M, Mp, D, R, d.P);
-    // desc.phase splits the call at the point where dF is queued: 1 = the per-sample chain only, 2 = the parameter branch only (same
-    // descriptor, same workspace; the caller orders 2 after 1 -- on any stream -- and may queue other work in between: a captured
-    // graph then keeps the layers' chains on one hardware queue).  Shapes off the streaming chain do everything in phase 1.
-    const int phase = (q_only || !(d.GMV && chain_fits(T, M, Mp, D, R, d.P))) ? (d.phase == 2 ? -1 : 0) : d.phase;
-    if (phase == -1) return IWVI_OK;
-    if (phase < 0 || phase > 2) { set_error("iwvi_gp_layer_backward: phase %d", d.phase); return IWVI_ERR_ARG; }
-    if (phase != 2 && !q_any && !d.prepared && (rc = iwvi_gp_layer_backward_prepare(dp, T, ws_, stream_)) != IWVI_OK) return rc;
-    const float* gmv = d.GMV ? d.GMV : w.GMV;
-    // deferred reductions of this layer: every product over samples parks its partial sums in its own slice of the workspace
-    const bool prod = d.GMV && chain_products_ok(M, T);    // dLm and G_r shares come out of the chain kernel
-    size_t partA = (size_t)((T + splitk_chunk(T) - 1) / splitk_chunk(T) + 2) * M * M;
-    if (prod && (size_t)(T / (16 * chain_ns(T, M))) * M * M > partA) partA = (size_t)(T / (16 * chain_ns(T, M))) * M * M;
-    const bool two_q = d.side_stream && d.side_stream2 && d.side_stream2 != d.side_stream;
-    ReduceQueue rqA(w.part, two_q ? partA : 0), rqB(w.part + (two_q ? partA : 0), w.part_floats - (two_q ? partA : 0));
-    float* s[3] = {nullptr, nullptr, nullptr}; float* a12[2] = {nullptr, nullptr};
-    const bool lin_on = (d.dW && d.W) || (d.dmf_A && d.mf_type == IWVI_MF_LINEAR);
-    // streaming chain (no saved u_r): M a multiple of 16 up to 128, T a multiple of 64, the forward's gmv block at hand
-    const bool chain = d.GMV && chain_fits(T, M, Mp, D, R, d.P);
-    if (!chain && !d.U) { set_error("iwvi_gp_layer_backward: this shape (M=%d, T=%lld) takes the GEMM path, which needs the forward's u_out", M, (long long)T); return IWVI_ERR_ARG; }
-    if (chain) {
-        const int nbk = Mp / 16;
-        ChainArgs ca{d.GMV, d.noise, d.W, d.mf_A, d.d_sample, d.d_mean, d.d_var, w.DMU, w.DV2, w.SDV, d.dF, d.P, d.mf_type,
-                     d.A, Mp, d.q_mu, w.SP, w.LinvTP, w.DK, d.F, w.Zt, w.invls, w.DA, w.Qx, (long long)T, M, D, R, nbk, d.variance, d.kern_type,
-                     dbg_opt("IWVI_CHAIN_EXIT"), d.variance_dev};
-        // the thin sums over samples ride in the chain kernel: one partial per workgroup and job, summed with the rest of chain B
-        const int S = (int)(T / (16 * chain_ns_shape(T, M, D, R, d.P))), P = d.P;
-        auto job = [&](int Mj, int Nj, float* out, const float* add, double add_coef) -> float* {
-            float* pp = rqB.take((size_t)S * Mj * Nj);
-            if (!pp) return nullptr;
-            ReduceArgs r{pp, S, Mj, Nj, out, nullptr, (long long)Nj, 1.0, 0.0, 0, 0, add, add_coef, 0};
-            return rqB.push(r, 1) ? pp : nullptr;
-        };
-        // (- kl_weight * dKL/dq_mu = - kl_weight * q_mu rides in the reduction; temp_workaround.py:186-188)
-        ca.p_qmu = job(M, R, d.dq_mu ? d.dq_mu : w.DMU, d.dq_mu ? d.q_mu : nullptr, -d.kl_weight);
-        ca.q_only = q_only ? 1 : 0;
-        ca.SP16 = (const float*)w.SP16; ca.spf = w.spf;
-        ca.ZtP = (const float*)((const char*)d.state + sl.off_ZtP); ca.cst = (const float*)((const char*)d.state + sl.off_cst); ca.nsteps = round_up(D + 2, 4) / 4;
-        if (!q_only) { ca.p_ctf = job(M, D + 1, w.CtF1, nullptr, 0.0); ca.p_q = job(D + 2, 1, w.Qsum, nullptr, 0.0); }
-        if (d.dW && d.W) { ca.p_w = job(3 * P, R, w.lin, nullptr, 0.0); for (int i = 0; i < 3; ++i) s[i] = w.lin + (size_t)i * P * R; if (!ca.p_w) ca.p_qmu = nullptr; }
-        if (d.dmf_A && d.mf_type == IWVI_MF_LINEAR) { ca.p_a = job(2 * D, P, w.lin + 3 * IWVI_MAX_P * IWVI_MAX_R, nullptr, 0.0); for (int i = 0; i < 2; ++i) a12[i] = w.lin + 3 * IWVI_MAX_P * IWVI_MAX_R + (size_t)i * D * P; if (!ca.p_a) ca.p_qmu = nullptr; }
-        if (!ca.p_qmu || (!q_only && (!ca.p_ctf || !ca.p_q))) { set_error("backward: workspace too small for the chain kernel's partial sums"); return IWVI_ERR_ARG; }
-        ca.S = S;
-        if (prod) {                                        // dLm and G_r shares too: no DK / A round trip, no split-K launches
-            ReduceQueue& qa = two_q ? rqA : rqB;
-            if (!q_only) {
-                ca.p_lm = qa.take((size_t)S * M * M);
-                ReduceArgs rl{ca.p_lm, S, M, M, nullptr, w.Lbar, (long long)M, -1.0, 0.0, 1, 0, nullptr, 0.0, 0, nbk};      // (shares: lower blocks, accumulator images)
-                if (!ca.p_lm || !qa.push(rl, 1)) { set_error("backward: workspace too small for the chain kernel's dLm shares"); return IWVI_ERR_ARG; }
-            }
-            if (d.dq_sqrt) {
-                ca.p_g = rqB.take((size_t)R * S * M * M);
-                ReduceArgs rg{ca.p_g, S, M, M, w.G, nullptr, (long long)M, 1.0, 0.0, 1, (long long)M * M, nullptr, 0.0, 0, nbk};
-                if (!ca.p_g || !rqB.push(rg, R)) { set_error("backward: workspace too small for the chain kernel's G_r shares"); return IWVI_ERR_ARG; }
-            }
-            ca.DK = nullptr;
-        }
-        if (phase != 2) note_bw_route(IWVI_BW_ROUTE_CHAIN, D <= 8 ? 8 : (D <= 16 ? 16 : 32), 16 * chain_ns_shape(T, M, D, R, d.P));
-        if (phase != 2 && (rc = launch_chain(st, ca)) != IWVI_OK) return rc;
-        if (phase == 1) return IWVI_OK;
-        if (q_only) {                                      // the two reductions (+ G_r by split-K GEMM where the chain does not form it), then dL_r
-            if (d.dq_sqrt && !prod) {
-                GemmArgs q{};
-                q.A = d.A; q.a_sm = 1; q.a_sk = Mp; q.B = d.A; q.b_sk = Mp; q.b_sn = 1;
-                q.scale = w.DV2; q.s_stride = R; q.scale_on_k = 1; q.M = M; q.N = M; q.K = (int)T; q.tri_out = 1;
-                if ((rc = gemm(st, q, w.part, w.part_floats, w.G, nullptr, M, 1.0, 0.0, 1, R, 0, 1, (long long)M * M, &rqB)) != IWVI_OK) return rc;
-            }
-            if ((rc = rqB.flush(st)) != IWVI_OK) return rc;
-            if (d.dq_sqrt) {
-                hipLaunchKernelGGL(k_gl_tril, dim3((M + 15) / 16, (M + 15) / 16, R), dim3(256), 0, st, (const float*)w.G, d.q_sqrt, d.dq_sqrt, M, -d.kl_weight);
-                if ((rc = check_launch("k_gl_tril")) != IWVI_OK) return rc;
-            }
-            return IWVI_OK;
-        }
-    }
-    if (q_any && !chain) {
-        // the same two gradients on the GEMM path (shapes off the streaming chain, e.g. M = 512): heads, dq_mu = A^T DMU, dL_r = tril(A^T
-        // diag(2 dv_r) U_r) -- nothing of the kernel adjoint, the triangular solves or the adjoint of the factorisation
-        HeadArgs h{d.A, d.U, d.noise, d.W, d.mf_A, d.d_sample, d.d_mean, d.d_var, w.DMU, w.DV2, w.SDV, nullptr, T, M, Mp, D, R, d.P, d.mf_type, d.variance, d.variance_dev,
-                   d.q_mu, nullptr, d.GMV};
-        note_bw_route(IWVI_BW_ROUTE_GEMM, 0, 0);           // (no kernel adjoint on this route)
-        hipLaunchKernelGGL(k_bw_heads, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, st, h);
-        if ((rc = check_launch("k_bw_heads")) != IWVI_OK) return rc;
-        if (d.dq_mu && (rc = thin(st, d.A, Mp, M, w.DMU, R, R, 0, T, w.part, w.part_floats, d.dq_mu, 0, &rqB, d.q_mu, -d.kl_weight)) != IWVI_OK) return rc;
-        if (d.dq_sqrt) {
-            GemmArgs q{};
-            q.A = d.A; q.a_sm = 1; q.a_sk = Mp; q.B = d.U; q.b_sk = Mp; q.b_sn = 1;
-            q.scale = w.DV2; q.s_stride = R; q.scale_on_k = 1; q.M = M; q.N = M; q.K = (int)T; q.tri_out = 1;
-            if ((rc = gemm(st, q, w.part, w.part_floats, d.dq_sqrt, nullptr, M, 1.0, 0.0, 1, R, (long long)T * Mp, 1, (long long)M * M, &rqB, d.q_sqrt, -d.kl_weight, 1)) != IWVI_OK) return rc;
-        }
-        return rqB.flush(st);
-    }
-    MidArgs ma{d.GMV, d.noise, d.W, d.mf_A, d.d_sample, d.d_mean, d.d_var, w.DMU, w.DV2, w.SDV, d.dF, d.P, d.mf_type,
-               d.U, d.A, Mp, d.q_sqrt, d.q_mu, w.LinvF, w.DK, d.F, w.Zt, w.invls, w.DA, w.Qx, (long long)T, M, D, R, d.variance, d.kern_type, d.variance_dev};
-    const int fused = chain ? 1 : launch_mid(st, ma);      // heads + DA + dK + kernel adjoint in one launch where the shapes allow
-    if (fused < 0) return fused;
-    if (fused && !chain) note_bw_route(IWVI_BW_ROUTE_MID, D <= 8 ? 8 : (D <= 16 ? 16 : 32), 64);
-    if (!fused) {
-        note_bw_route(IWVI_BW_ROUTE_GEMM, D <= 4 ? 4 : (D <= 8 ? 8 : (D <= 16 ? 16 : 32)), 16);
-        HeadArgs h{d.A, d.U, d.noise, d.W, d.mf_A, d.d_sample, d.d_mean, d.d_var, w.DMU, w.DV2, w.SDV, d.dF, T, M, Mp, D, R, d.P, d.mf_type, d.variance, d.variance_dev,
-                   d.q_mu, (d.dW && d.W && !d.GMV) ? w.GMV : nullptr, d.GMV};
-        hipLaunchKernelGGL(k_bw_heads, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, st, h);
-        if ((rc = check_launch("k_bw_heads")) != IWVI_OK) return rc;
-        // DA = DMU q_mu^T - 2 SDV o A + sum_r (2 dv_r) o (U_r L_r^T): ONE launch -- R segments of M along the contraction, the
-        // first two terms in the epilogue
-        {
-            GemmArgs q{};
-            q.A = d.U; q.a_sm = Mp; q.a_sk = 1;
-            q.B = d.q_sqrt; q.b_sk = 1; q.b_sn = M; q.b_keep_n_ge_k = 1;                          // B(k = j, n = i) = L_r[i][j], i >= j
-            q.scale = w.DV2; q.s_stride = R; q.scale_on_k = 0;
-            q.C = w.DA; q.ldc = M; q.M = (int)T; q.N = M; q.K = M; q.alpha = 1.f; q.beta = 0.f;
-            q.e_dmu = w.DMU; q.e_qmu = d.q_mu; q.e_sdv = w.SDV; q.e_A = d.A; q.e_lda = Mp; q.e_R = R;
-            if ((rc = gemm_rows(st, q, R, (long long)T * Mp, (long long)M * M, 1)) != IWVI_OK) return rc;
-        }
-        // DK = DA Lm^-1
-        {
-            GemmArgs q{};
-            q.A = w.DA; q.a_sm = M; q.a_sk = 1; q.B = w.LinvF; q.b_sk = M; q.b_sn = 1;
-            q.C = w.DK; q.ldc = M; q.M = (int)T; q.N = M; q.K = M; q.alpha = 1.f; q.beta = 0.f; q.b_lower_kn = 1;
-            if ((rc = gemm_rows(st, q)) != IWVI_OK) return rc;
-        }
-        // C = -1/2 K o DK (over DA), dx~, dF, per-sample rows of the column sums
-        KernArgs ka{d.F, w.Zt, w.invls, w.DK, w.DA, w.SDV, d.dF, w.Qx, T, M, D, d.variance, d.kern_type, d.variance_dev};
-        {
-            const dim3 grid((unsigned)((T + 15) / 16)), block(256);
-            if (D <= 4) hipLaunchKernelGGL(k_bw_kernel<4>, grid, block, 0, st, ka);
-            else if (D <= 8) hipLaunchKernelGGL(k_bw_kernel<8>, grid, block, 0, st, ka);
-            else if (D <= 16) hipLaunchKernelGGL(k_bw_kernel<16>, grid, block, 0, st, ka);
-            else hipLaunchKernelGGL(k_bw_kernel<32>, grid, block, 0, st, ka);
-        }
-        if ((rc = check_launch("k_bw_kernel")) != IWVI_OK) return rc;
-
-    }
-    // Everything the layer below needs (dF) is now queued on `st`.  What follows only produces this layer's parameter
-    // gradients: with side streams it runs beside the next layer's adjoint instead of ahead of it, as two chains --
-    //   A: dLm -> its reduction -> Cholesky adjoint -> K_uu's gradient          B: every other sum over samples -> one reduction
-    // -- that meet in the final assembly (on B's stream).
-    hipStream_t stA = st, stB = st;
-    hipEvent_t evA = nullptr;
-    if (d.side_stream) {
-        stA = (hipStream_t)d.side_stream;
-        stB = d.side_stream2 ? (hipStream_t)d.side_stream2 : stA;
-        hipEvent_t ev;
-        // (a stream never waits on its own event: in phase 2 the caller's stream IS the first side stream)
-        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(ev, st) != hipSuccess ||
-            (stA != st && hipStreamWaitEvent(stA, ev, 0) != hipSuccess) || (stB != stA && stB != st && hipStreamWaitEvent(stB, ev, 0) != hipSuccess)) {
-            set_error("iwvi_gp_layer_backward: stream fork failed"); return IWVI_ERR_LAUNCH;
-        }
-        (void)hipEventDestroy(ev);                         // (released once the recorded work has passed it)
-    }
-    // ---- chain A: dLm = -tril(DK^T A)  (float64, for the adjoint of the factorisation), then S = Lm^-T Phi(Lm^T Lbar) Lm^-1
-    const bool two = stB != stA;
-    auto chol_adjoint = [&](hipStream_t s_) {
-        const dim3 grid((M + 15) / 16, (M + 15) / 16), block(256);
-        (void)grid; (void)block;
-        dmm(s_, Lm64, 1, Mp, (const double*)w.Lbar, M, 1, w.T1, M, M, M, M, 1.0, nullptr, 0, 0.0, 1);      // T1 = Phi(Lm^T Lbar)
-        dmm(s_, Linv64, 1, Mp, (const double*)w.T1, M, 1, w.T2, M, M, M, M);                                // T2 = Lm^-T T1
-        dmm(s_, (const double*)w.T2, M, 1, Linv64, Mp, 1, w.S, M, M, M, M);                                 // S  = T2 Lm^-1
-        hipLaunchKernelGGL(k_kuu_bwd, dim3((M + 3) / 4), dim3(256), 0, s_, w.Zt, (const double*)w.S, M, D, (double)d.variance, d.variance_dev, d.kern_type, w.dZt_uu, w.dvar_m);
-        return check_launch("cholesky adjoint");
+    return IWVI_OK;
+}
+// the weighted Gram product A^T diag(2 dv_r) B summed over the samples: all r in one batched split-K launch, lower tiles only.
+//   B = A (streaming chain): G_r, a SYRK, for dL_r = tril(G_r L_r) by k_gl_tril;   B = U (GEMM path): dL_r = tril(A^T diag(2 dv_r) U_r)
+//   itself, and - kl_weight * dKL/dL_r = - kl_weight * (L_r - diag(1 / L_ii)) rides in the reduction
+static int bw_weighted_gram(BwCall& c, hipStream_t st, bool from_u) {
+    GemmArgs q{};
+    q.A = c.d.A; q.a_sm = 1; q.a_sk = c.Mp; q.B = from_u ? c.d.U : c.d.A; q.b_sk = c.Mp; q.b_sn = 1;
+    q.scale = c.w.DV2; q.s_stride = c.R; q.scale_on_k = 1; q.M = c.M; q.N = c.M; q.K = (int)c.T; q.tri_out = 1;
+    const GemmOut g_r{c.w.G, nullptr, c.M, 1.0, 1, c.R, 0, 1, (long long)c.M * c.M, nullptr, 0.0, 0};
+    const GemmOut dl_r{c.d.dq_sqrt, nullptr, c.M, 1.0, 1, c.R, (long long)c.T * c.Mp, 1, (long long)c.M * c.M, c.d.q_sqrt, -c.d.kl_weight, 1};
+    return gemm(st, q, from_u ? dl_r : g_r, c.rqB);
+}
+// dq_mu = A^T DMU  (- kl_weight * dKL/dq_mu = - kl_weight * q_mu rides in the reduction; temp_workaround.py:186-188)
+static int bw_dqmu_thin(BwCall& c, hipStream_t st) {
+    return thin(st, c.d.A, c.Mp, c.M, c.w.DMU, c.R, c.R, 0, c.T, c.d.dq_mu, c.rqB, 0, c.d.q_mu, -c.d.kl_weight);
+}
+// (- kl_weight * dKL/dL_r = - kl_weight * (L_r - diag(1 / L_ii)) rides along)
+static int bw_gl_tril(BwCall& c, hipStream_t st) {
+    hipLaunchKernelGGL(k_gl_tril, dim3((c.M + 15) / 16, (c.M + 15) / 16, c.R), dim3(256), 0, st, (const float*)c.w.G, c.d.q_sqrt, c.d.dq_sqrt, c.M, -c.d.kl_weight);
+    return check_launch("k_gl_tril");
+}
+static int bw_branch_b(BwCall& c, hipStream_t st, bool then_chol);
+static int bw_heads(BwCall& c, hipStream_t st, float* dF, float* gmv_out) {
+    const iwvi_gp_bwd_desc& d = c.d;
+    HeadArgs h{d.A, d.U, d.noise, d.W, d.mf_A, d.d_sample, d.d_mean, d.d_var, c.w.DMU, c.w.DV2, c.w.SDV, dF, c.T, c.M, c.Mp, c.D, c.R, d.P, d.mf_type,
+               d.variance, d.variance_dev, d.q_mu, gmv_out, d.GMV};
+    hipLaunchKernelGGL(k_bw_heads, dim3((unsigned)((c.T + 3) / 4)), dim3(256), 0, st, h);
+    return check_launch("k_bw_heads");
+}
+// ---- the chain route: arguments, the queued partial-sum jobs, the launch (phase 2 queues the same jobs and launches nothing)
+static int bw_chain(BwCall& c, hipStream_t st) {
+    const iwvi_gp_bwd_desc& d = c.d; const BwdWs& w = c.w; const ChainPlan& cp = c.cp; const RoutePlan& rp = c.rp;
+    const int M = c.M, D = c.D, R = c.R, P = d.P, nbk = c.Mp / 16;
+    ChainArgs ca{d.GMV, d.noise, d.W, d.mf_A, d.d_sample, d.d_mean, d.d_var, w.DMU, w.DV2, w.SDV, d.dF, d.P, d.mf_type,
+                 d.A, c.Mp, d.q_mu, w.SP, w.LinvTP, w.DK, d.F, w.Zt, w.invls, w.DA, w.Qx, c.T, M, D, R, nbk, d.variance, d.kern_type,
+                 dbg_opt("IWVI_CHAIN_EXIT"), d.variance_dev};
+    ca.z_lds = cp.z_lds ? 1 : 0; ca.s16 = cp.s16 ? 1 : 0; ca.p5h = (cp.s16 && !dbg_opt("IWVI_BW_P5_F32")) ? 1 : 0; ca.dsz = cp.dsz; ca.ts = cp.ts;
+    // the thin sums over samples ride in the chain kernel: one partial per workgroup and job, summed with the rest of branch B
+    const int S = (int)cp.shares;
+    auto job = [&](int Mj, int Nj, float* out, const float* add, double add_coef) -> float* {
+        float* pp = c.rqB.take((size_t)S * Mj * Nj);
+        if (!pp) return nullptr;
+        ReduceArgs r{pp, S, Mj, Nj, out, nullptr, (long long)Nj, 1.0, 0.0, 0, 0, add, add_coef, 0};
+        return c.rqB.push(r, 1) ? pp : nullptr;
     };
-    {
+    // (- kl_weight * dKL/dq_mu = - kl_weight * q_mu rides in the reduction; temp_workaround.py:186-188)
+    ca.p_qmu = job(M, R, d.dq_mu ? d.dq_mu : w.DMU, d.dq_mu ? d.q_mu : nullptr, -d.kl_weight);
+    ca.q_only = rp.q_only ? 1 : 0; ca.SP16 = (const float*)w.SP16; ca.spf = w.spf;
+    ca.ZtP = (const float*)((const char*)d.state + c.sl.off_ZtP); ca.cst = (const float*)((const char*)d.state + c.sl.off_cst); ca.nsteps = round_up(D + 2, 4) / 4;
+    if (!rp.q_only) { ca.p_ctf = job(M, D + 1, w.CtF1, nullptr, 0.0); ca.p_q = job(D + 2, 1, w.Qsum, nullptr, 0.0); }
+    if (d.dW && d.W) { ca.p_w = job(3 * P, R, w.lin, nullptr, 0.0); for (int i = 0; i < 3; ++i) c.s[i] = w.lin + (size_t)i * P * R; if (!ca.p_w) ca.p_qmu = nullptr; }
+    if (d.dmf_A && d.mf_type == IWVI_MF_LINEAR) { ca.p_a = job(2 * D, P, w.lin + 3 * IWVI_MAX_P * IWVI_MAX_R, nullptr, 0.0); for (int i = 0; i < 2; ++i) c.a12[i] = w.lin + 3 * IWVI_MAX_P * IWVI_MAX_R + (size_t)i * D * P; if (!ca.p_a) ca.p_qmu = nullptr; }
+    if (!ca.p_qmu || (!rp.q_only && (!ca.p_ctf || !ca.p_q))) { set_error("backward: workspace too small for the chain kernel's partial sums"); return IWVI_ERR_ARG; }
+    ca.S = S;
+    if (rp.prod) {                                         // dLm and G_r shares too
+        // a `frag` job reads its shares as accumulator images of the lower 16x16 blocks: right only while the matrix has no padded rows
+        if (M != c.Mp) { set_error("backward: the chain kernel's block shares need M == Mp (M=%d, Mp=%d)", M, c.Mp); return IWVI_ERR_ARG; }
+        ReduceQueue& qa = rp.two_q ? c.rqA : c.rqB;
+        if (!rp.q_only) {
+            ca.p_lm = qa.take((size_t)S * M * M);
+            ReduceArgs rl{ca.p_lm, S, M, M, nullptr, w.Lbar, (long long)M, -1.0, 0.0, 1, 0, nullptr, 0.0, 0, nbk};      // (shares: lower blocks, accumulator images)
+            if (!ca.p_lm || !qa.push(rl, 1)) { set_error("backward: workspace too small for the chain kernel's dLm shares"); return IWVI_ERR_ARG; }
+        }
+        if (d.dq_sqrt) {
+            ca.p_g = c.rqB.take((size_t)R * S * M * M);
+            ReduceArgs rg{ca.p_g, S, M, M, w.G, nullptr, (long long)M, 1.0, 0.0, 1, (long long)M * M, nullptr, 0.0, 0, nbk};
+            if (!ca.p_g || !c.rqB.push(rg, R)) { set_error("backward: workspace too small for the chain kernel's G_r shares"); return IWVI_ERR_ARG; }
+        }
+        ca.DK = nullptr;
+    }
+    if (rp.phase == 2) return IWVI_OK;
+    note_bw_route(IWVI_BW_ROUTE_CHAIN, cp.DM, cp.nsamp);
+    return launch_chain(st, ca, cp);
+}
+// ---- the same two gradients on the GEMM route (shapes off the streaming chain, e.g. M = 512): heads, then branch B's dq_mu = A^T DMU and
+// dL_r = tril(A^T diag(2 dv_r) U_r) -- nothing of the kernel adjoint, the triangular solves or the adjoint of the factorisation
+static int bw_gemm_q(BwCall& c, hipStream_t st) {
+    note_bw_route(IWVI_BW_ROUTE_GEMM, 0, 0);               // (no kernel adjoint on this route)
+    const int rc = bw_heads(c, st, nullptr, nullptr);
+    return rc != IWVI_OK ? rc : bw_branch_b(c, st, false);
+}
+// ---- the MID route: heads + DA + dK + kernel adjoint in one launch
+static int bw_mid(BwCall& c, hipStream_t st) {
+    const iwvi_gp_bwd_desc& d = c.d; const BwdWs& w = c.w;
+    MidArgs ma{d.GMV, d.noise, d.W, d.mf_A, d.d_sample, d.d_mean, d.d_var, w.DMU, w.DV2, w.SDV, d.dF, d.P, d.mf_type,
+               d.U, d.A, c.Mp, d.q_sqrt, d.q_mu, w.LinvF, w.DK, d.F, w.Zt, w.invls, w.DA, w.Qx, c.T, c.M, c.D, c.R, d.variance, d.kern_type, d.variance_dev};
+    const int rc = launch_mid(st, ma);
+    if (rc == IWVI_OK) note_bw_route(IWVI_BW_ROUTE_MID, d_bucket(c.D), 64);
+    return rc;
+}
+// ---- the GEMM route: heads, DA, DK, kernel adjoint
+static int bw_gemm(BwCall& c, hipStream_t st) {
+    const iwvi_gp_bwd_desc& d = c.d; const BwdWs& w = c.w;
+    const int M = c.M, D = c.D, R = c.R, Mp = c.Mp; const long long T = c.T;
+    note_bw_route(IWVI_BW_ROUTE_GEMM, D <= 4 ? 4 : d_bucket(D), 16);
+    int rc = bw_heads(c, st, d.dF, (d.dW && d.W && !d.GMV) ? w.GMV : nullptr);
+    if (rc != IWVI_OK) return rc;
+    // DA = DMU q_mu^T - 2 SDV o A + sum_r (2 dv_r) o (U_r L_r^T): ONE launch -- R segments of M along the contraction, the
+    // first two terms in the epilogue
+    GemmArgs q{};
+    q.A = d.U; q.a_sm = Mp; q.a_sk = 1;
+    q.B = d.q_sqrt; q.b_sk = 1; q.b_sn = M; q.b_keep_n_ge_k = 1;                              // B(k = j, n = i) = L_r[i][j], i >= j
+    q.scale = w.DV2; q.s_stride = R; q.scale_on_k = 0;
+    q.C = w.DA; q.ldc = M; q.M = (int)T; q.N = M; q.K = M; q.alpha = 1.f; q.beta = 0.f;
+    q.e_dmu = w.DMU; q.e_qmu = d.q_mu; q.e_sdv = w.SDV; q.e_A = d.A; q.e_lda = Mp; q.e_R = R;
+    if ((rc = gemm_rows(st, q, R, (long long)T * Mp, (long long)M * M, 1)) != IWVI_OK) return rc;
+    // DK = DA Lm^-1
+    q = GemmArgs{};
+    q.A = w.DA; q.a_sm = M; q.a_sk = 1; q.B = w.LinvF; q.b_sk = M; q.b_sn = 1;
+    q.C = w.DK; q.ldc = M; q.M = (int)T; q.N = M; q.K = M; q.alpha = 1.f; q.beta = 0.f; q.b_lower_kn = 1;
+    if ((rc = gemm_rows(st, q)) != IWVI_OK) return rc;
+    // C = -1/2 K o DK (over DA), dx~, dF, per-sample rows of the column sums
+    KernArgs ka{d.F, w.Zt, w.invls, w.DK, w.DA, w.SDV, d.dF, w.Qx, T, M, D, d.variance, d.kern_type, d.variance_dev};
+    const dim3 grid((unsigned)((T + 15) / 16)), block(256);
+    if (D <= 4) hipLaunchKernelGGL(k_bw_kernel<4>, grid, block, 0, st, ka);
+    else if (D <= 8) hipLaunchKernelGGL(k_bw_kernel<8>, grid, block, 0, st, ka);
+    else if (D <= 16) hipLaunchKernelGGL(k_bw_kernel<16>, grid, block, 0, st, ka);
+    else hipLaunchKernelGGL(k_bw_kernel<32>, grid, block, 0, st, ka);
+    return check_launch("k_bw_kernel");
+}
+// ---- the stream fork.  Everything the layer below needs (dF) is now queued on `st`.  What follows only produces this layer's parameter
+// gradients: with side streams it runs beside the next layer's adjoint instead of ahead of it, as two branches --
+//   A: dLm -> its reduction -> Cholesky adjoint -> K_uu's gradient          B: every other sum over samples -> one reduction
+// -- that meet in the final assembly (on B's stream).
+static int bw_fork(const iwvi_gp_bwd_desc& d, hipStream_t st, hipStream_t& stA, hipStream_t& stB) {
+    stA = stB = st;
+    if (!d.side_stream) return IWVI_OK;
+    stA = (hipStream_t)d.side_stream;
+    stB = d.side_stream2 ? (hipStream_t)d.side_stream2 : stA;
+    hipEvent_t ev;
+    // (a stream never waits on its own event: in phase 2 the caller's stream IS the first side stream)
+    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(ev, st) != hipSuccess ||
+        (stA != st && hipStreamWaitEvent(stA, ev, 0) != hipSuccess) || (stB != stA && stB != st && hipStreamWaitEvent(stB, ev, 0) != hipSuccess)) {
+        set_error("iwvi_gp_layer_backward: stream fork failed"); return IWVI_ERR_LAUNCH;
+    }
+    (void)hipEventDestroy(ev);                             // (released once the recorded work has passed it)
+    return IWVI_OK;
+}
+// S = Lm^-T Phi(Lm^T Lbar) Lm^-1 in float64, then K_uu's gradient
+static int bw_chol_adjoint(BwCall& c, hipStream_t st) {
+    const BwdWs& w = c.w; const int M = c.M, Mp = c.Mp;
+    const double* Lm64 = (const double*)((const char*)c.d.state + c.sl.off_Lm);
+    const double* Linv64 = (const double*)((const char*)c.d.state + c.sl.off_Linv);
+    dmm(st, Lm64, 1, Mp, (const double*)w.Lbar, M, 1, w.T1, M, M, M, M, 1.0, nullptr, 0, 0.0, 1);      // T1 = Phi(Lm^T Lbar)
+    dmm(st, Linv64, 1, Mp, (const double*)w.T1, M, 1, w.T2, M, M, M, M);                                // T2 = Lm^-T T1
+    dmm(st, (const double*)w.T2, M, 1, Linv64, Mp, 1, w.S, M, M, M, M);                                 // S  = T2 Lm^-1
+    hipLaunchKernelGGL(k_kuu_bwd, dim3((M + 3) / 4), dim3(256), 0, st, w.Zt, (const double*)w.S, M, c.D, (double)c.d.variance, c.d.variance_dev, c.d.kern_type, w.dZt_uu, w.dvar_m);
+    return check_launch("cholesky adjoint");
+}
+// ---- branch A: dLm = -tril(DK^T A)  (float64, for the adjoint of the factorisation); with a stream of its own also its reduction and
+// the float64 chain, concurrently with branch B (*evA then marks its end)
+static int bw_branch_a(BwCall& c, hipStream_t stA, bool two, hipEvent_t* evA) {
+    int rc;
+    if (!c.rp.prod) {
         GemmArgs q{};
-        q.A = w.DK; q.a_sm = 1; q.a_sk = M; q.B = d.A; q.b_sk = Mp; q.b_sn = 1; q.M = M; q.N = M; q.K = (int)T; q.tri_out = 1;
-        if (!(chain && prod) && (rc = gemm(stA, q, w.part, w.part_floats, nullptr, w.Lbar, M, -1.0, 0.0, 1, 1, 0, 0, 0, two ? &rqA : &rqB)) != IWVI_OK) return rc;
-        if (two) {                                         // its own reduction and the float64 chain, concurrently with chain B
-            if ((rc = rqA.flush(stA)) != IWVI_OK || (rc = chol_adjoint(stA)) != IWVI_OK) return rc;
-            if (hipEventCreateWithFlags(&evA, hipEventDisableTiming) != hipSuccess || hipEventRecord(evA, stA) != hipSuccess) {
-                set_error("iwvi_gp_layer_backward: stream join failed"); return IWVI_ERR_LAUNCH;
+        q.A = c.w.DK; q.a_sm = 1; q.a_sk = c.M; q.B = c.d.A; q.b_sk = c.Mp; q.b_sn = 1; q.M = c.M; q.N = c.M; q.K = (int)c.T; q.tri_out = 1;
+        const GemmOut o{nullptr, c.w.Lbar, c.M, -1.0, 1, 1, 0, 0, 0, nullptr, 0.0, 0};
+        if ((rc = gemm(stA, q, o, two ? c.rqA : c.rqB)) != IWVI_OK) return rc;
+    }
+    if (!two) return IWVI_OK;
+    if ((rc = c.rqA.flush(stA)) != IWVI_OK || (rc = bw_chol_adjoint(c, stA)) != IWVI_OK) return rc;
+    if (hipEventCreateWithFlags(evA, hipEventDisableTiming) == hipSuccess && hipEventRecord(*evA, stA) == hipSuccess) return IWVI_OK;
+    set_error("iwvi_gp_layer_backward: stream join failed"); return IWVI_ERR_LAUNCH;
+}
+// ---- branch B: the remaining sums over samples, their one reduction, k_gl_tril; then_chol: on one stream the float64 chain follows here,
+// after the single reduction.  A q-only call ends with this step alone (on the chain: G_r by split-K where the kernel did not form it)
+static int bw_branch_b(BwCall& c, hipStream_t st, bool then_chol) {
+    const iwvi_gp_bwd_desc& d = c.d; const BwdWs& w = c.w;
+    const int M = c.M, D = c.D, R = c.R; const long long T = c.T;
+    const bool chain = c.rp.route == IWVI_BW_ROUTE_CHAIN;
+    int rc = IWVI_OK;
+    if (!chain) {
+        if (d.dq_mu && (rc = bw_dqmu_thin(c, st)) != IWVI_OK) return rc;
+        if (d.dq_sqrt && (rc = bw_weighted_gram(c, st, true)) != IWVI_OK) return rc;
+        // sums over samples: C^T [F | 1]  and the column sums of Qx = (dx~ o x | sum_r dv_r | sum_m k dk)
+        if (!c.rp.q_any && (rc = thin(st, w.DA, M, M, d.F, D, D, 1, T, w.CtF1, c.rqB)) != IWVI_OK) return rc;
+        if (!c.rp.q_any && (rc = thin(st, w.Qx, D + 2, D + 2, nullptr, 0, 0, 1, T, w.Qsum, c.rqB)) != IWVI_OK) return rc;
+        // mixing matrix and linear mean function (trainable when the reference runs with fix_linear=False, build_models.py:224-227)
+        if (c.rp.lin_on) {
+            const int P = d.P;
+            const float* gmv = d.GMV ? d.GMV : w.GMV;
+            const float* ups[3] = {d.d_sample, d.d_mean, d.d_var};
+            if (d.dW && d.W) for (int i = 0; i < 3; ++i) if (ups[i]) {
+                c.s[i] = w.lin + i * IWVI_MAX_P * IWVI_MAX_R;
+                if ((rc = thin(st, ups[i], P, P, gmv + i * R, 3 * R, R, 0, T, c.s[i], c.rqB)) != IWVI_OK) return rc;
+            }
+            if (d.dmf_A && d.mf_type == IWVI_MF_LINEAR) for (int i = 0; i < 2; ++i) if (ups[i]) {
+                c.a12[i] = w.lin + 3 * IWVI_MAX_P * IWVI_MAX_R + i * IWVI_MAX_D * IWVI_MAX_P;
+                if ((rc = thin(st, d.F, D, D, ups[i], P, P, 0, T, c.a12[i], c.rqB)) != IWVI_OK) return rc;
             }
         }
-    }
-    // ---- chain B
-    st = stB;
-    // dq_mu = A^T DMU
-    // (- kl_weight * dKL/dq_mu = - kl_weight * q_mu rides in the reduction; temp_workaround.py:186-188)
-    if (!chain && d.dq_mu && (rc = thin(st, d.A, Mp, M, w.DMU, R, R, 0, T, w.part, w.part_floats, d.dq_mu, 0, &rqB, d.q_mu, -d.kl_weight)) != IWVI_OK) return rc;
-    // streaming path: dL_r = tril(G_r L_r) with G_r = A^T diag(2 dv_r) A (lower tiles of a split-K SYRK, all r in one batched launch)
-    if (d.dq_sqrt && chain && !prod) {
-        GemmArgs q{};
-        q.A = d.A; q.a_sm = 1; q.a_sk = Mp; q.B = d.A; q.b_sk = Mp; q.b_sn = 1;
-        q.scale = w.DV2; q.s_stride = R; q.scale_on_k = 1; q.M = M; q.N = M; q.K = (int)T; q.tri_out = 1;
-        if ((rc = gemm(st, q, w.part, w.part_floats, w.G, nullptr, M, 1.0, 0.0, 1, R, 0, 1, (long long)M * M, &rqB)) != IWVI_OK) return rc;
-    }
-    // dL_r = tril(A^T diag(2 dv_r) U_r), all r in one batched launch
-    if (d.dq_sqrt && !chain) {
-        GemmArgs q{};
-        q.A = d.A; q.a_sm = 1; q.a_sk = Mp; q.B = d.U; q.b_sk = Mp; q.b_sn = 1;
-        q.scale = w.DV2; q.s_stride = R; q.scale_on_k = 1; q.M = M; q.N = M; q.K = (int)T; q.tri_out = 1;
-        // (- kl_weight * dKL/dL_r = - kl_weight * (L_r - diag(1 / L_ii)) rides in the reduction)
-        if ((rc = gemm(st, q, w.part, w.part_floats, d.dq_sqrt, nullptr, M, 1.0, 0.0, 1, R, (long long)T * Mp, 1, (long long)M * M, &rqB, d.q_sqrt, -d.kl_weight, 1)) != IWVI_OK) return rc;
-    }
-    // sums over samples: C^T [F | 1]  and the column sums of Qx = (dx~ o x | sum_r dv_r | sum_m k dk)
-    if (!chain && (rc = thin(st, w.DA, M, M, d.F, D, D, 1, T, w.part, w.part_floats, w.CtF1, 0, &rqB)) != IWVI_OK) return rc;
-    if (!chain && (rc = thin(st, w.Qx, D + 2, D + 2, nullptr, 0, 0, 1, T, w.part, w.part_floats, w.Qsum, 0, &rqB)) != IWVI_OK) return rc;
-    // mixing matrix and linear mean function (trainable when the reference runs with fix_linear=False, build_models.py:224-227)
-    if (lin_on && !chain) {
-        const int P = d.P;
-        const float* ups[3] = {d.d_sample, d.d_mean, d.d_var};
-        if (d.dW && d.W) for (int i = 0; i < 3; ++i) if (ups[i]) {
-            s[i] = w.lin + i * IWVI_MAX_P * IWVI_MAX_R;
-            if ((rc = thin(st, ups[i], P, P, gmv + i * R, 3 * R, R, 0, T, w.part, w.part_floats, s[i], 0, &rqB)) != IWVI_OK) return rc;
-        }
-        if (d.dmf_A && d.mf_type == IWVI_MF_LINEAR) for (int i = 0; i < 2; ++i) if (ups[i]) {
-            a12[i] = w.lin + 3 * IWVI_MAX_P * IWVI_MAX_R + i * IWVI_MAX_D * IWVI_MAX_P;
-            if ((rc = thin(st, d.F, D, D, ups[i], P, P, 0, T, w.part, w.part_floats, a12[i], 0, &rqB)) != IWVI_OK) return rc;
-        }
-    }
-    if ((rc = rqB.flush(st)) != IWVI_OK) return rc;
-    if (d.dq_sqrt && chain) {                              // (- kl_weight * dKL/dL_r = - kl_weight * (L_r - diag(1 / L_ii)) rides along)
-        hipLaunchKernelGGL(k_gl_tril, dim3((M + 15) / 16, (M + 15) / 16, R), dim3(256), 0, st, (const float*)w.G, d.q_sqrt, d.dq_sqrt, M, -d.kl_weight);
-        if ((rc = check_launch("k_gl_tril")) != IWVI_OK) return rc;
-    }
-    if (!two && (rc = chol_adjoint(st)) != IWVI_OK) return rc;     // one stream: after the single reduction, as before
-    const int n_w = (lin_on && d.dW && d.W) ? d.P * R : 0, n_a = (lin_on && d.dmf_A && d.mf_type == IWVI_MF_LINEAR) ? D * d.P : 0;
-    if (evA) {                                             // the assembly needs chain A's dZt_uu / dvar_m
+    } else if (d.dq_sqrt && !c.rp.prod && (rc = bw_weighted_gram(c, st, false)) != IWVI_OK) return rc;
+    if ((rc = c.rqB.flush(st)) != IWVI_OK) return rc;
+    if (d.dq_sqrt && chain && (rc = bw_gl_tril(c, st)) != IWVI_OK) return rc;
+    return then_chol ? bw_chol_adjoint(c, st) : IWVI_OK;
+}
+// ---- the join and the final assembly (which needs branch A's dZt_uu / dvar_m)
+static int bw_join_final(BwCall& c, hipStream_t stB, hipEvent_t evA) {
+    const iwvi_gp_bwd_desc& d = c.d; const BwdWs& w = c.w; const int D = c.D; const bool lin_on = c.rp.lin_on;
+    const int n_w = (lin_on && d.dW && d.W) ? d.P * c.R : 0, n_a = (lin_on && d.dmf_A && d.mf_type == IWVI_MF_LINEAR) ? D * d.P : 0;
+    if (evA) {
         if (hipStreamWaitEvent(stB, evA, 0) != hipSuccess) { set_error("iwvi_gp_layer_backward: stream join failed"); return IWVI_ERR_LAUNCH; }
         (void)hipEventDestroy(evA);
     }
     FinalArgsB f{d.Z, d.lengthscales, d.q_mu, d.q_sqrt, w.Zt, w.invls, w.CtF1, w.CtF1, w.Qsum + D, w.Qsum, w.dZt_uu, w.dvar_m,
-                 d.dZ, d.dls, d.dvariance, d.dq_mu, d.dq_sqrt, M, D, R, d.kl_weight, (double)d.variance, d.variance_dev,
-                 s[0], s[1], s[2], d.W, n_w ? d.dW : nullptr, n_w, a12[0], a12[1], n_a ? d.dmf_A : nullptr, n_a};
-    hipLaunchKernelGGL(k_bw_final, dim3(D + 1 + (lin_on ? 1 : 0)), dim3(64), 0, st, f);
+                 d.dZ, d.dls, d.dvariance, d.dq_mu, d.dq_sqrt, c.M, D, c.R, d.kl_weight, (double)d.variance, d.variance_dev,
+                 c.s[0], c.s[1], c.s[2], d.W, n_w ? d.dW : nullptr, n_w, c.a12[0], c.a12[1], n_a ? d.dmf_A : nullptr, n_a};
+    hipLaunchKernelGGL(k_bw_final, dim3(D + 1 + (lin_on ? 1 : 0)), dim3(64), 0, stB, f);
     return check_launch("k_bw_final");
+}
+
+extern "C" int iwvi_gp_layer_backward(const iwvi_gp_bwd_desc* dp, int64_t T, void* ws_, void* stream_) {
+    if (!dp || !ws_ || T <= 0) { set_error("iwvi_gp_layer_backward: bad argument"); return IWVI_ERR_ARG; }
+    const iwvi_gp_bwd_desc& d = *dp;
+    hipStream_t st = (hipStream_t)stream_, stA, stB;
+    hipEvent_t evA = nullptr;
+    int rc;
+    if ((rc = bw_check_desc(d, T)) != IWVI_OK) return rc;
+    BwCall c(d, T, ws_);                                    // the chain plan, the workspace layout, the route plan, the reduction queues
+    const RoutePlan& rp = c.rp;
+    if (rp.phase == -1) return IWVI_OK;
+    if (rp.phase < 0 || rp.phase > 2) { set_error("iwvi_gp_layer_backward: phase %d", d.phase); return IWVI_ERR_ARG; }
+    if (rp.phase != 2 && !rp.q_any && !d.prepared && (rc = iwvi_gp_layer_backward_prepare(dp, T, ws_, stream_)) != IWVI_OK) return rc;
+    if (rp.route != IWVI_BW_ROUTE_CHAIN && !d.U) { set_error("iwvi_gp_layer_backward: this shape (M=%d, T=%lld) takes the GEMM path, which needs the forward's u_out", c.M, (long long)T); return IWVI_ERR_ARG; }
+    if (rp.route == IWVI_BW_ROUTE_CHAIN) {
+        if ((rc = bw_chain(c, st)) != IWVI_OK || rp.phase == 1) return rc;
+        if (rp.q_only) return bw_branch_b(c, st, false);
+    } else if (rp.q_any) return bw_gemm_q(c, st);
+    else if ((rc = rp.route == IWVI_BW_ROUTE_MID ? bw_mid(c, st) : bw_gemm(c, st)) != IWVI_OK) return rc;
+    if ((rc = bw_fork(d, st, stA, stB)) != IWVI_OK) return rc;
+    const bool two = stB != stA;
+    if ((rc = bw_branch_a(c, stA, two, &evA)) != IWVI_OK || (rc = bw_branch_b(c, stB, !two)) != IWVI_OK) return rc;
+    return bw_join_final(c, stB, evA);
 }
 
 extern "C" int iwvi_iw_elbo_backward(const float* fmean, const float* fvar, const float* Y, int Dy,

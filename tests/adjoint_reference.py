@@ -131,7 +131,7 @@ def solo_norms(spec, li, F, z, cs, cm, cv, rows, kern=None):
 # li = 0: the inner layer (D = Dx inputs, R latent GPs, W [Dx, R], Linear mean function), li = 1: the final layer (R = Dy outputs, no W).
 # ``fused``: IWVI_BW_FUSED, ``f32``: settings.bw_f32_chain, ``rows``: "live" = live_rows(T), "all" = every row.
 # ``route`` = (route, D bucket of the kernel-adjoint template, samples per workgroup) as iwvi_debug_last_backward_routes reports it,
-# derived by hand from chain_ns_shape / chain_fits / launch_mid / splitk_chunk of csrc/backward.hip (the comment beside each row).
+# derived by hand from chain_plan (ns, fits, products) / mid_ok / splitk_chunk of csrc/backward.hip (the comment beside each row).
 Case = namedtuple("Case", "id M Dx R li T fused f32 rows route kern")
 
 
@@ -140,8 +140,8 @@ def _c(id, M, Dx, R, li, T, route, fused=0, f32=False, rows="live", kern=None):
 
 
 CASES = [
-    # chain_ns_cap: NS = ceil(T / 4096) capped at 5 for M <= 128, lowered to a divisor of T / 16; M = 128 has 8 blocks: split-f16 chain;
-    # T / (16 NS) <= 1024 workgroups and M <= 128: dLm / G_r shares formed in the chain (chain_products_ok)
+    # chain_plan: NS = ceil(T / 4096) capped at 5 for M <= 128, lowered to a divisor of T / 16; M = 128 has 8 blocks: split-f16 chain;
+    # T / (16 NS) <= 1024 workgroups and M <= 128: dLm / G_r shares formed in the chain (ChainPlan::products)
     _c("chain-ns2", 128, 8, 5, 0, 8192, (CHAIN, 8, 32)),
     _c("chain-ns3", 128, 8, 5, 0, 9600, (CHAIN, 8, 48)),                      # ceil(9600 / 4096) = 3, 600 tiles = 3 * 200
     _c("chain-ns4", 128, 8, 5, 0, 16384, (CHAIN, 8, 64)),
@@ -149,15 +149,15 @@ CASES = [
     _c("chain-ns5-to-3", 128, 8, 5, 0, 20496, (CHAIN, 8, 48)),               # 1281 tiles = 3 * 7 * 61: 5, 4 do not divide
     _c("chain-ns1-1031-shares", 64, 8, 2, 0, 16496, (CHAIN, 8, 16)),         # 1031 tiles, prime: NS = 1; > 1024 shares: products by split-K GEMM
     _c("chain-ns5-dm16", 128, 12, 5, 0, 20480, (CHAIN, 16, 80)),
-    # DM = 32 at NS = 5: at M = 128 the three [M x 84] tiles of the split-f16 chain + the staging of D = 20 are ~182 KB, chain_fits is
+    # DM = 32 at NS = 5: at M = 128 the three [M x 84] tiles of the split-f16 chain + the staging of D = 20 are ~182 KB, the plan's `fits` is
     # false at any T > 16384 (the default rule then launches k_bw_mid) -- so M = 64 for the split-f16 chain, and the issue's M = 128
     # shape on the two-tile fp32 chain, which does fit
     _c("chain-ns5-dm32-m64", 64, 20, 5, 0, 20480, (CHAIN, 32, 80)),
     _c("chain-ns5-dm32-f32", 128, 20, 5, 0, 20480, (CHAIN, 32, 80), f32=True),
-    _c("chain-m256-32", 256, 20, 2, 0, 16384, (CHAIN, 32, 32)),              # chain_ns_shape: 64 samples do not fit beside D = 20 -> 2 * 16
+    _c("chain-m256-32", 256, 20, 2, 0, 16384, (CHAIN, 32, 32)),              # chain_plan's ns: 64 samples do not fit beside D = 20 -> 2 * 16
     _c("gemm-m256-16-splits", 256, 20, 20, 0, 8192, (GEMM, 32, 16)),         # R = 20: the chain does not fit; M > 128: no k_bw_mid by default
     _c("chain-m176-f32-64", 176, 20, 2, 0, 16384, (CHAIN, 32, 64)),          # 11 blocks (odd): fp32 chain, two tiles, 4 * 16 samples fit
-    _c("chain-m512-s16", 512, 8, 1, 1, 1024, (CHAIN, 8, 16), rows="all"),    # chain_ok by chain_s16 (32 blocks); three [512 x 20] tiles fit
+    _c("chain-m512-s16", 512, 8, 1, 1, 1024, (CHAIN, 8, 16), rows="all"),    # the plan is ok by s16 (32 blocks); three [512 x 20] tiles fit
     _c("mid-forced-m64", 64, 24, 32, 0, 20480, (MID, 32, 64), fused=1),
     _c("mid-forced-m256", 256, 20, 20, 0, 8192, (MID, 32, 64), fused=1),
     _c("mid-default", 128, 32, 32, 0, 16384, (MID, 32, 64)),                 # the chain does not fit, M = 128, T >= 16384, T % 64 == 0

@@ -11,7 +11,7 @@ dls, dvariance, dW and dmf_A against the reference at the tolerance test_gpu_bac
 call bit for bit.  A final layer gets d_sample = None, as in the model.
 
 Not reached: k_bw_chain<5, 32> on split-f16 operands at M = 128 -- three [128 x 84] tiles and the staging of D > 16 need ~182 KB of LDS,
-chain_fits is false there at any T > 16384 and the default rule launches k_bw_mid; <5, 32> runs here at M = 64 (split f16) and at
+the chain plan's `fits` is false there at any T > 16384 and the default rule launches k_bw_mid; <5, 32> runs here at M = 64 (split f16) and at
 M = 128 with IWVI_BW_F32_CHAIN (two tiles).
 
 Observed on an MI355X, worst error / tolerance over the arrays of each case (every case prints its own):
