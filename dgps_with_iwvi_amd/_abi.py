@@ -37,6 +37,7 @@ c_void_p, c_int, c_int64, c_float, c_double, c_size_t = (
 ERR_ARG, ERR_LAUNCH, ERR_UNSUPPORTED = -1, -2, -3      # enum iwvi_status (include/iwvi_hip.h)
 LIK_GAUSSIAN, LIK_BERNOULLI_PROBIT, LIK_STUDENT_T, LIK_MULTICLASS = 0, 1, 2, 3   # iwvi_lik_desc.type
 LIK_POISSON, LIK_EXPONENTIAL, LIK_GAMMA = 4, 5, 6                                # (exp link: csrc/likelihood_explink.hip)
+LIK_BETA, LIK_ORDINAL = 8, 9                                                     # (probit link: csrc/likelihood_bounded.hip; 7 is unassigned)
 BW_ROUTE_CHAIN, BW_ROUTE_MID, BW_ROUTE_GEMM = 1, 2, 3   # iwvi_debug_last_backward_routes
 
 

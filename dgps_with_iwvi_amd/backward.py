@@ -580,9 +580,9 @@ def iw_elbo_and_gradients(model, zs=None, mode_vi=None, exchange=None, K_total=N
     oracle/grad_oracle.py: 'l<i>.Z', 'l<i>.ls', 'l<i>.var', 'l<i>.q_mu', 'l<i>.q_sqrt', 'l<i>.W', 'l<i>.mfA' (layers with
     a mixing matrix / linear mean function), 'l<i>.encW<j>', 'l<i>.encb<j>', 'lik_var'.  ``zs``: one noise tensor per layer ([B, K, dim]) or None -> drawn.
 
-    A likelihood other than the Gaussian (``likelihoods.Bernoulli`` / ``StudentT`` / ``MultiClass`` / ``Poisson`` / ``Exponential`` / ``Gamma``): the heads never come out of the layer launch
+    A likelihood other than the Gaussian (``likelihoods.Bernoulli`` / ``StudentT`` / ``MultiClass`` / ``Poisson`` / ``Exponential`` / ``Gamma`` / ``Beta`` / ``Ordinal``): the heads never come out of the layer launch
     (``fuse_heads`` is off) but from ``iwvi_lik_elbo_backward`` on the final layer's moments; the layer adjoints are the same.  The
-    likelihood's gradient is named by its ``grad_name`` ('lik_scale' for the Student-t, 'lik_shape' for the Gamma; the others have none).  With
+    likelihood's gradient is named by its ``grad_name`` ('lik_scale' for the Student-t and the Beta, 'lik_shape' for the Gamma, 'lik_sigma' for the Ordinal; the others have none).  With
     ``MultiClass`` Y is one column of labels and the heads are [T, C]."""
     from .likelihoods import is_gaussian, output_dim
     from .models import DGP_IWVI

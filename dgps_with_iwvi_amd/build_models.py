@@ -203,7 +203,7 @@ def attach_train_op(model, ARGS):
 def _likelihood_kind(lik):
     """The checkpoint type of a likelihood: the name of the class of likelihoods.py it is or derives from (subclasses count)."""
     from . import likelihoods
-    for kind in ("Poisson", "Exponential", "Gamma", "MultiClass", "StudentT", "Bernoulli"):
+    for kind in ("Beta", "Ordinal", "Poisson", "Exponential", "Gamma", "MultiClass", "StudentT", "Bernoulli"):
         if isinstance(lik, getattr(likelihoods, kind)):
             return kind
     return "Gaussian"
@@ -216,7 +216,8 @@ def likelihood_state(lik):
     if kind == "Gaussian":
         return {"likelihood.variance": np.float64(lik.variance)}
     params = {"MultiClass": lambda: [lik.num_classes, lik.epsilon], "StudentT": lambda: [lik.scale, lik.df], "Bernoulli": lambda: [],
-              "Poisson": lambda: [lik.binsize], "Exponential": lambda: [], "Gamma": lambda: [lik.shape]}[kind]()
+              "Poisson": lambda: [lik.binsize], "Exponential": lambda: [], "Gamma": lambda: [lik.shape],
+              "Beta": lambda: [lik.scale], "Ordinal": lambda: [lik.sigma] + lik.bin_edges.tolist()}[kind]()
     return {"likelihood.type": np.str_(kind), "likelihood.params": np.array(params, dtype=np.float64)}
 
 
@@ -239,6 +240,13 @@ def load_likelihood_state(lik, state):
         lik.binsize, = params
     elif kind == "Gamma":
         lik.shape, = params
+    elif kind == "Beta":
+        lik.scale, = params
+    elif kind == "Ordinal":
+        if len(params) - 1 != lik.bin_edges.size:
+            raise ValueError("the checkpoint holds an Ordinal with %d bin edges, the model one with %d" % (len(params) - 1, lik.bin_edges.size))
+        lik.set_bin_edges(params[1:])
+        lik.sigma = params[0]
     elif kind == "Gaussian":
         lik.variance = float(state["likelihood.variance"])
 

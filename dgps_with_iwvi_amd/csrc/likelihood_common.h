@@ -1,9 +1,10 @@
-// What csrc/likelihood_tail.hip, csrc/likelihood_multiclass.hip and csrc/likelihood_explink.hip share: the Gauss-Hermite tables, the
+// What csrc/likelihood_tail.hip, csrc/likelihood_multiclass.hip, csrc/likelihood_explink.hip and csrc/likelihood_bounded.hip share: the
+// Gauss-Hermite tables, the quadrature's variance floor, the probit link's jitter and the float64 digamma of a launch-wide parameter, the
 // kernel-argument structs of the iwvi_lik_* entry points and the segment reductions (moved here verbatim from likelihood_tail.hip), the
 // point loop of iwvi_lik_predict_mixture for the types whose outputs are independent (mix_points), the bound's reduction and the heads of its
 // adjoint for every type (elbo_points, elbo_bwd_point: one core each over a small compile-time policy per family), the SEG and the mode
-// dispatch of the launchers, and the launchers of the multi-class and the exp-link kernels, which the entry points of likelihood_tail.hip
-// call for IWVI_LIK_MULTICLASS and for IWVI_LIK_POISSON / _EXPONENTIAL / _GAMMA.
+// dispatch of the launchers, and the launchers of the multi-class, the exp-link and the bounded-target kernels, which the entry points of
+// likelihood_tail.hip call for IWVI_LIK_MULTICLASS, for IWVI_LIK_POISSON / _EXPONENTIAL / _GAMMA and for IWVI_LIK_BETA / _ORDINAL.
 #pragma once
 #include <type_traits>
 #include "iwvi_common.h"
@@ -18,6 +19,22 @@ __device__ __constant__ const float GH_W[10] = {2.607930634e-01f, 1.617393340e-0
                                                 1.288262800e-04f, 4.402121090e-06f, 6.127490260e-08f, 2.482062362e-10f, 1.257800672e-13f};
 __device__ __constant__ const float GH_LOGW[10] = {-1.344028046e+00f, -1.821769289e+00f, -2.788614499e+00f, -4.268852429e+00f, -6.303382958e+00f,
                                                    -8.957045728e+00f, -1.233342407e+01f, -1.660789550e+01f, -2.211676112e+01f, -2.970424151e+01f};
+
+// dE/dv = sum_i w_i g'(f_i) x_i / sqrt(2 v) is 0/0 at v = 0 (the forward clamps a float32 variance that undershot at exactly 0); its limit is
+// g''(mu) / 2.  The variance is floored here, for the value and the heads alike (the heads stay the gradient of the value that is
+// computed): sqrt(2 v) >= 1.4e-4, which moves E by g'' 5e-9 -- below float32 resolution -- and leaves the quotient finite.
+constexpr float LIK_V_FLOOR = 1e-8f;
+constexpr float LIK_JIT = 1e-3f;                  // GPflow's inv_probit jitter: p = Phi(f) (1 - 2 jit) + jit
+
+// psi(x), x > 0, float64 -- for a launch-wide parameter (the Gamma's shape, the Beta's scale), once per wave: the recurrence
+// psi(x) = psi(x + 1) - 1 / x up to x >= 6 (six steps at the most: the loop is bounded whatever the device scalar holds), then the
+// asymptotic series (next term 691 / (32760 x^12) < 1e-11)
+__device__ __forceinline__ double digamma_f64(double x) {
+    double r = 0.0;
+    for (int i = 0; i < 6 && x < 6.0; ++i) { r -= 1.0 / x; x += 1.0; }
+    const double i = 1.0 / x, i2 = i * i;
+    return r + log(x) - 0.5 * i - i2 * (1.0 / 12.0 - i2 * (1.0 / 120.0 - i2 * (1.0 / 252.0 - i2 * (1.0 / 240.0 - i2 * (1.0 / 132.0)))));
+}
 
 struct Lik { int type; float p0, p1, lgc; const float* p0_dev; };
 
@@ -149,7 +166,8 @@ struct LikBwdArgs {
 
 // ------------------------------------------------------------------------------------------
 // The bound's reduction and the heads of its adjoint, ONE core each for every likelihood.  What differs between the families is a policy OPS
-// (LikQuadOps in likelihood_tail.hip, McOps in likelihood_multiclass.hip, XlOps in likelihood_explink.hip; no runtime branch on the type here):
+// (LikQuadOps in likelihood_tail.hip, McOps in likelihood_multiclass.hip, XlOps in likelihood_explink.hip, BoOps<TYPE> in
+// likelihood_bounded.hip; no runtime branch on the type here):
 //   Point point<SEG, GRAD>(Y, b, live, sl)   a data point's state, formed once by the SEG lanes that own it: nothing (Gaussian, Bernoulli,
 //                                            Student-t), the clamped label (MultiClass), cb = sum_d c0(y_bd) in float32 (exp link; GRAD: also
 //                                            the point's part of d / d shape)
@@ -342,5 +360,14 @@ int xl_launch_elbo_bwd(const LikBwdArgs& a, hipStream_t stream);                
 int xl_launch_elem(const char* what, int mode, const Lik& L, const float* Fmu, const float* Fvar, const float* Y, long long T, int Dy,
                    long long row_div, long long row_mod, float* out, float* out2, hipStream_t stream);
 int xl_launch_mix(const LikMixArgs& g, hipStream_t stream);                       // k_xl_mix<SEG>
+
+// ---- csrc/likelihood_bounded.hip (IWVI_LIK_BETA: lik.p0 / *lik.p0_dev = scale; _ORDINAL: lik.p0_dev = [sigma, e_0 .. e_(n-1)], lik.p1 = n) ----
+inline bool bo_type(int type) { return type == IWVI_LIK_BETA || type == IWVI_LIK_ORDINAL; }
+int bo_launch_elbo(const LikReduceArgs& g, hipStream_t stream);                   // k_bo_elbo<TYPE, SEG>
+int bo_launch_elbo_bwd(const LikBwdArgs& a, hipStream_t stream);                  // k_bo_elbo_bwd<TYPE> (the caller launches k_lik_finish behind it)
+// mode 0: variational_expectations, 1: predict_density (Fvar == NULL: logp), 2: predict_mean_and_var (out, out2) -- all [T, Dy]
+int bo_launch_elem(const char* what, int mode, const Lik& L, const float* Fmu, const float* Fvar, const float* Y, long long T, int Dy,
+                   long long row_div, long long row_mod, float* out, float* out2, hipStream_t stream);
+int bo_launch_mix(const LikMixArgs& g, hipStream_t stream);                       // k_bo_mix<TYPE, SEG>
 
 }  // namespace iwvi

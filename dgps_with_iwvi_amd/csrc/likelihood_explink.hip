@@ -20,15 +20,6 @@
 
 namespace iwvi {
 
-// psi(x), x > 0: the recurrence psi(x) = psi(x + 1) - 1 / x up to x >= 6 (six steps at the most: the loop is bounded whatever the device
-// scalar holds), then the asymptotic series (next term 691 / (32760 x^12) < 1e-11)
-__device__ __forceinline__ double xl_digamma(double x) {
-    double r = 0.0;
-    for (int i = 0; i < 6 && x < 6.0; ++i) { r -= 1.0 / x; x += 1.0; }
-    const double i = 1.0 / x, i2 = i * i;
-    return r + log(x) - 0.5 * i - i2 * (1.0 / 12.0 - i2 * (1.0 / 120.0 - i2 * (1.0 / 252.0 - i2 * (1.0 / 240.0 - i2 * (1.0 / 132.0)))));
-}
-
 // the launch's view of the descriptor (wave-uniform)
 struct XlPar {
     int type;
@@ -49,7 +40,7 @@ __device__ __forceinline__ XlPar xl_par(const Lik& L) {
         const float a = L.p0_dev ? *L.p0_dev : L.p0;
         P.cmu = -a; P.am1 = a - 1.f;
         if (LGA) P.lga = (float)lgamma((double)a);
-        if (PSI) P.psi = xl_digamma((double)a);
+        if (PSI) P.psi = digamma_f64((double)a);
     }
     return P;
 }

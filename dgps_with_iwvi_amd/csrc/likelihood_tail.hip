@@ -2,17 +2,12 @@
 // likelihood's methods as elementwise callables.  The reference passes any GPflow-1.x likelihood to its models (models.py:66,105,134);
 // the non-conjugate ones -- Bernoulli with the probit link, Student-t -- integrate by GPflow's ndiagquad: Gauss-Hermite, 20 points.
 // The entry points at the end of this file serve every type of include/iwvi_hip.h: Gaussian, Bernoulli and Student-t by the kernels here,
-// MultiClass by csrc/likelihood_multiclass.hip, Poisson / Exponential / Gamma (exp link, closed-form expectations) by csrc/likelihood_explink.hip.
+// MultiClass by csrc/likelihood_multiclass.hip, Poisson / Exponential / Gamma (exp link, closed-form expectations) by csrc/likelihood_explink.hip,
+// Beta / Ordinal (probit link, quadrature) by csrc/likelihood_bounded.hip.
 // The layer stack is untouched: these kernels read the final layer's moments (and the local regularisers) the layer launch left in HBM.
-#include "likelihood_common.h"   // the node tables GH_X / GH_W / GH_LOGW, Lik, the argument structs, lseg_*
+#include "likelihood_common.h"   // the node tables GH_X / GH_W / GH_LOGW, LIK_V_FLOOR, LIK_JIT, Lik, the argument structs, lseg_*
 
 namespace iwvi {
-
-// dE/dv = sum_i w_i g'(f_i) x_i / sqrt(2 v) is 0/0 at v = 0 (the forward clamps a float32 variance that undershot at exactly 0); its limit is
-// g''(mu) / 2.  The variance is floored here, for the value and the heads alike (the heads stay the gradient of the value that is
-// computed): sqrt(2 v) >= 1.4e-4, which moves E by g'' 5e-9 -- below float32 resolution -- and leaves the quotient finite.
-constexpr float LIK_V_FLOOR = 1e-8f;
-constexpr float LIK_JIT = 1e-3f;                  // GPflow's inv_probit jitter: p = Phi(f) (1 - 2 jit) + jit
 
 // g(f) = logp(f, y);  GRAD: also g'(f) and d g / d param[0]
 template <bool GRAD>
@@ -311,7 +306,23 @@ static int take_lik(const iwvi_lik_desc* d, Lik& L, const char* what, bool need_
         case IWVI_LIK_GAMMA:
             if (!(d->param[0] > 0.f)) { set_error("%s: Gamma shape (param[0]) must be positive, got %g", what, (double)d->param[0]); return IWVI_ERR_ARG; }
             return IWVI_OK;
-        default:
+        case IWVI_LIK_BETA:
+            if (!(d->param[0] > 0.f)) { set_error("%s: Beta scale (param[0]) must be positive, got %g", what, (double)d->param[0]); return IWVI_ERR_ARG; }
+            return IWVI_OK;
+        case IWVI_LIK_ORDINAL: {
+            const float n = d->param[1];
+            if (!(n >= 1.f && n <= (float)(IWVI_MAX_P - 1)) || n != (float)(int)n) {
+                set_error("%s: Ordinal needs an integral number of bin edges (param[1]) in 1..%d, got %g", what, IWVI_MAX_P - 1, (double)n);
+                return IWVI_ERR_ARG;
+            }
+            if (!d->param0_dev) {
+                set_error("%s: Ordinal needs param0_dev: %d device floats [sigma, e_0 .. e_%d]", what, 1 + (int)n, (int)n - 1);
+                return IWVI_ERR_ARG;
+            }
+            if (!(d->param[0] > 0.f)) { set_error("%s: Ordinal sigma (param[0]) must be positive, got %g", what, (double)d->param[0]); return IWVI_ERR_ARG; }
+            return IWVI_OK;
+        }
+        default:                                             // (7 is unassigned: include/iwvi_hip.h)
             set_error("%s: unknown likelihood type %d", what, d->type); return IWVI_ERR_ARG;
     }
 }
@@ -359,6 +370,7 @@ extern "C" int iwvi_lik_elbo_reduce(const iwvi_lik_desc* lik, const float* fmean
         return mc_launch_elbo(g, stream);
     }
     if (xl_type(g.lik.type)) return xl_launch_elbo(g, stream);
+    if (bo_type(g.lik.type)) return bo_launch_elbo(g, stream);
     return seg_dispatch(K, [&](auto seg) {
         constexpr int SEG = decltype(seg)::value;
         hipLaunchKernelGGL(k_lik_elbo<SEG>, dim3((unsigned)lik_passes(B, SEG)), dim3(LIK_THREADS), 0, stream, g);
@@ -399,6 +411,8 @@ extern "C" int iwvi_lik_elbo_backward(const iwvi_lik_desc* lik, const float* fme
         if ((rc = mc_launch_elbo_bwd(a, st)) != IWVI_OK) return rc;
     } else if (xl_type(a.lik.type)) {
         if ((rc = xl_launch_elbo_bwd(a, st)) != IWVI_OK) return rc;
+    } else if (bo_type(a.lik.type)) {
+        if ((rc = bo_launch_elbo_bwd(a, st)) != IWVI_OK) return rc;
     } else {
         hipLaunchKernelGGL(k_lik_elbo_bwd, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a);
     }
@@ -420,6 +434,8 @@ static int lik_elementwise(const char* what, const iwvi_lik_desc* lik, const flo
         return mc_launch_elem(what, MODE, L, Fmu, Fvar, Y, (long long)T, Dy, (long long)row_div, (long long)row_mod, out, out2, (hipStream_t)stream_);
     if (xl_type(L.type))
         return xl_launch_elem(what, MODE, L, Fmu, Fvar, Y, (long long)T, Dy, (long long)row_div, (long long)row_mod, out, out2, (hipStream_t)stream_);
+    if (bo_type(L.type))
+        return bo_launch_elem(what, MODE, L, Fmu, Fvar, Y, (long long)T, Dy, (long long)row_div, (long long)row_mod, out, out2, (hipStream_t)stream_);
     const long long n = (long long)T * Dy;
     hipLaunchKernelGGL(k_lik_elem<MODE>, dim3(elem_blocks(n)), dim3(256), 0, (hipStream_t)stream_, L, Fmu, Fvar, Y, n, Dy,
                        (long long)row_div, (long long)row_mod, out, out2);
@@ -472,6 +488,7 @@ extern "C" int iwvi_lik_predict_mixture(const iwvi_lik_desc* lik, const float* f
     g.logp = out_logp; g.mean = out_mean; g.var = out_var;
     if (g.lik.type == IWVI_LIK_MULTICLASS) return mc_launch_mix(g, stream);
     if (xl_type(g.lik.type)) return xl_launch_mix(g, stream);
+    if (bo_type(g.lik.type)) return bo_launch_mix(g, stream);
     return seg_dispatch(S, [&](auto seg) {
         constexpr int SEG = decltype(seg)::value;
         hipLaunchKernelGGL(k_lik_mix<SEG>, dim3(mix_blocks(N, SEG)), dim3(LIK_THREADS), 0, stream, g);

@@ -4,7 +4,7 @@ The layer kernel's hot variants sit at the 256-VGPR limit: a source change anywh
 scratch, and a variant that only the large configs take then regresses unnoticed (round 4: the five-sub-tile large-M variant went
 216 B into scratch, configs[3] 1.27 -> 1.43 ms, for four commits).  ``check()`` is run by ``__graft_entry__.build()`` and by
 tests/test_kernel_resources.py: it fails when a ``k_dgp_forward`` or ``k_bw_chain`` instantiation (the predictive and sampling variants of the
-forward included), ``k_sample_stats``, ``k_kde_grid`` or a likelihood-tail kernel (every ``k_lik_*``, ``k_mc_*``, ``k_xl_*``, the ``*_mix`` kernels of the predictive mixture included) the SGHMC update ``k_sghmc_step`` or a CVAE kernel (``k_cvae_*``) uses scratch memory
+forward included), ``k_sample_stats``, ``k_kde_grid`` or a likelihood-tail kernel (every ``k_lik_*``, ``k_mc_*``, ``k_xl_*``, ``k_bo_*``, the ``*_mix`` kernels of the predictive mixture included) the SGHMC update ``k_sghmc_step`` or a CVAE kernel (``k_cvae_*``) uses scratch memory
 (``.private_segment_fixed_size`` > 0) beyond what ``ALLOWED_SCRATCH`` lists, when a listed spill count grows, or when a kernel listed in ``MAX_VGPRS`` exceeds its VGPR ceiling.
 
   python -m dgps_with_iwvi_amd.kernel_resources [--write profiles/<tag>_kernel_resources.txt]
@@ -28,12 +28,14 @@ FIELDS = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_sp
 # (k_lik_*: csrc/likelihood_tail.hip -- twenty quadrature nodes unrolled per element: no scratch, and a VGPR ceiling each, MAX_VGPRS below;
 #  k_mc_*: csrc/likelihood_multiclass.hip -- twenty running products per sample, which must stay in registers;
 #  k_xl_*: csrc/likelihood_explink.hip -- closed forms, and a float64 lgamma / digamma of the shape per wave.
-#  The *_elbo and *_elbo_bwd kernels of the three files are ONE core each, csrc/likelihood_common.h: elbo_points / elbo_bwd_point, inlined over a
+#  k_bo_*: csrc/likelihood_bounded.hip -- Beta and Ordinal, the type a template argument (8 / 9): rolled node loops over erfc / lgamma / digamma.
+#  The *_elbo and *_elbo_bwd kernels of the four files are ONE core each, csrc/likelihood_common.h: elbo_points / elbo_bwd_point, inlined over a
 #  policy per family -- but for k_lik_elbo_bwd, which keeps a body of its own --: a change to a core moves every family's rows;
 #  profiles/likcore_kernel_resources.txt has them side by side)
 NO_SCRATCH = ("k_dgp_forward", "k_bw_chain", "k_sample_stats", "k_lik_elbo", "k_lik_elbo_bwd", "k_lik_elem", "k_lik_finish", "k_kde_grid",
               "k_mc_elbo", "k_mc_elbo_bwd", "k_mc_elem", "k_xl_elbo", "k_xl_elbo_bwd", "k_xl_elem",
               "k_lik_mix", "k_mc_mix", "k_xl_mix",
+              "k_bo_elbo", "k_bo_elbo_bwd", "k_bo_elem", "k_bo_mix",
               "k_sghmc_step",          # csrc/sghmc.hip: the sampler's update, replayed 10 000 times per evaluation (56 VGPRs today)
               # csrc/cvae.hip: a map's weights travel in registers (32 / 64 per lane) between LDS stagings; they must stay there
               "k_cvae_rows", "k_cvae_wgrad", "k_cvae_finish", "k_cvae_sample")
@@ -63,10 +65,12 @@ MAX_SPILLS = {
 # The exp-link kernels (k_xl_*) do a handful of FMAs and one exp per element: their ceilings are the compiled counts (k_xl_elbo 79-89,
 # k_xl_elem 37-63, k_xl_mix 95; k_xl_elbo_bwd 65 when the ceiling was set, 54 today) rounded up to a multiple of 8, so a change that costs them
 # a wave of occupancy shows.
+# The bounded-target kernels (k_bo_*) likewise: k_bo_elbo 52-68, k_bo_elbo_bwd 68-117, k_bo_elem 34-50, k_bo_mix 68-88 (Ordinal - Beta).
 MAX_VGPRS = {"k_lik_elbo": 128, "k_lik_elbo_bwd": 128, "k_lik_elem": 128, "k_lik_finish": 32,
              "k_mc_elbo": 128, "k_mc_elbo_bwd": 128, "k_mc_elem": 128,
              "k_xl_elbo": 96, "k_xl_elbo_bwd": 72, "k_xl_elem": 64,
              "k_lik_mix": 128, "k_mc_mix": 128, "k_xl_mix": 96,
+             "k_bo_elbo": 72, "k_bo_elbo_bwd": 120, "k_bo_elem": 56, "k_bo_mix": 88,
              "k_sghmc_step": 64}
 
 

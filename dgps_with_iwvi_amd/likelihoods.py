@@ -17,7 +17,12 @@ layer: ``Y`` is ONE column of class labels 0 .. C-1 while the layer has C output
 / ``output_dim`` below translate, and a likelihood says which it is by a ``num_classes`` attribute.
 
 ``Poisson``, ``Exponential`` and ``Gamma`` (exp link, GPflow's default; ``csrc/likelihood_explink.hip``) have closed-form variational
-expectations -- one ``exp`` per element, no quadrature --; ``Gamma.shape`` is the one trained scalar (``grad_name`` 'lik_shape')."""
+expectations -- one ``exp`` per element, no quadrature --; ``Gamma.shape`` is the one trained scalar (``grad_name`` 'lik_shape').
+
+``Beta`` (targets in [0, 1]) and ``Ordinal`` (ordered grades 0 .. n) squash the latent through the probit link; everything is the 20-point
+rule again (``csrc/likelihood_bounded.hip``).  ``Beta.scale`` ('lik_scale') and ``Ordinal.sigma`` ('lik_sigma') are trained.  The Ordinal
+keeps ONE device buffer [sigma, e_0 .. e_(n-1)] that every launch reads, and hands whoever trains sigma the 1-element view of its head
+(``trained_scalar_view``) instead of being bound to a tensor of the trainer's."""
 import math
 
 import torch
@@ -406,6 +411,145 @@ class Gamma(_QuadratureLikelihood, DeviceScalarVariance):
         import numpy as np
         Yh = _host_targets(Y)
         _refuse_targets("Gamma", "finite and > 0", Yh, ~(np.isfinite(Yh) & (Yh > 0)))
+
+
+def _probit_link_only(cls_name, invlink):
+    if invlink is not None and getattr(invlink, "__name__", invlink) != "inv_probit":
+        raise NotImplementedError("%s(invlink=%r): only the probit link (GPflow's default, inv_probit) is implemented"
+                                  % (cls_name, getattr(invlink, "__name__", invlink)))
+
+
+class Beta(_QuadratureLikelihood, DeviceScalarVariance):
+    """gpflow 1.x ``Beta(invlink=inv_probit, scale=1.0)``: Y ~ Beta(alpha, beta) with mean m = inv_probit(F), alpha = m scale, beta = scale -
+    alpha; logp = (alpha - 1) log Yc + (beta - 1) log(1 - Yc) + lgamma(scale) - lgamma(alpha) - lgamma(beta), Yc = clip(Y, 1e-6, 1 - 1e-6).
+    Everything but ``logp`` is GPflow's default by the 20-point rule.  ``scale`` is trainable (positive): lgamma and digamma of it are
+    evaluated on the device from the value a launch reads."""
+    # the one trained scalar: the lazily refreshed host copy / device master of DeviceScalarVariance, as StudentT.scale
+    scale = property(DeviceScalarVariance.host_value, DeviceScalarVariance.variance.fset)
+
+    def __init__(self, invlink=None, scale=1.0, name=None):
+        _probit_link_only("Beta", invlink)
+        if not float(scale) > 0.0:
+            raise ValueError("Beta: scale must be positive, got %r" % (scale,))
+        self.scale = float(scale)
+        self.name = name
+
+    @property
+    def variance(self):
+        raise AttributeError("Beta has no 'variance': its parameter is 'scale'")
+
+    def lik_desc(self):
+        d = _abi.LikDesc()
+        d.type = _abi.LIK_BETA
+        d.param[0], d.param0_dev = self.desc_variance()
+        return d
+
+    grad_name = "lik_scale"
+
+    def trained_scalar(self):
+        return self.grad_name, self.scale
+
+    def check_targets(self, Y):
+        """Finite and in [0, 1] (0 and 1 themselves are clipped to 1e-6 and 1 - 1e-6 inside the density, as GPflow does); the models call
+        this once on the host when they are built."""
+        import numpy as np
+        Yh = _host_targets(Y)
+        _refuse_targets("Beta", "finite and in [0, 1]", Yh, ~(np.isfinite(Yh) & (Yh >= 0) & (Yh <= 1)))
+
+
+class Ordinal(_QuadratureLikelihood):
+    """gpflow 1.x ``Ordinal(bin_edges)``: n strictly increasing edges make n + 1 bins, Y holds the bin 0 .. n.  With l = e_Y / sigma (+inf
+    for the top bin) and r = e_(Y-1) / sigma (-inf for the bottom one), P_Y(F) = inv_probit(l - F / sigma) - inv_probit(r - F / sigma) and
+    logp = log(P_Y + 1e-6); the bins sum to 0.998, as GPflow's do.  Everything but ``logp`` is GPflow's default by the 20-point rule.
+    ``sigma`` (1.0 at first) is trainable (positive); the edges are fixed.  Both live in ONE device buffer [sigma, e_0 .. e_(n-1)], created
+    on the current device at the first use and moved by ``to`` (``model.to`` calls it)."""
+
+    def __init__(self, bin_edges, name=None):
+        self.bin_edges = self._checked_edges(bin_edges)
+        self._sigma_host, self._stale, self._buf = 1.0, False, None
+        self.name = name
+
+    @staticmethod
+    def _checked_edges(bin_edges):
+        import numpy as np
+        edges = np.array(_host_targets(bin_edges), dtype=np.float64).reshape(-1)
+        if not 1 <= edges.size <= _abi.MAX_P - 1:
+            raise ValueError("Ordinal: 1 to %d bin edges, got %d" % (_abi.MAX_P - 1, edges.size))
+        e32 = edges.astype(np.float32)                           # (what the kernels read)
+        if not (np.isfinite(e32).all() and (np.diff(e32) > 0).all()):
+            raise ValueError("Ordinal: bin edges must be finite and strictly increasing (in float32), got %r" % (edges.tolist(),))
+        edges.setflags(write=False)
+        return edges
+
+    num_bins = property(lambda self: self.bin_edges.size + 1)
+
+    def _buffer(self):
+        if self._buf is None:
+            self._buf = torch.tensor([self._sigma_host] + self.bin_edges.tolist(), dtype=settings.float_type, device=settings.default_device())
+        return self._buf
+
+    def to(self, device):
+        if self._buf is not None:
+            self._buf = self._buf.to(device)
+        return self
+
+    def host_value(self):
+        """sigma's host copy, refreshed from the device buffer when a trainer has moved it since the last read."""
+        if self._stale:
+            self._sigma_host = float(self._buf[0].item())
+            self._stale = False
+        return self._sigma_host
+
+    def _set_sigma(self, v):
+        if not float(v) > 0.0:
+            raise ValueError("Ordinal: sigma must be positive, got %r" % (v,))
+        self._sigma_host, self._stale = float(v), False
+        if self._buf is not None:
+            self._buf[:1].fill_(self._sigma_host)
+
+    sigma = property(host_value, _set_sigma)
+
+    def set_bin_edges(self, bin_edges):
+        """New edges of the SAME count, written into the buffer in place (a checkpoint's; a captured graph keeps reading the buffer)."""
+        edges = self._checked_edges(bin_edges)
+        if edges.size != self.bin_edges.size:
+            raise ValueError("Ordinal: %d bin edges cannot replace %d" % (edges.size, self.bin_edges.size))
+        self.bin_edges = edges
+        if self._buf is not None:
+            self._buf[1:].copy_(torch.tensor(edges.tolist(), dtype=settings.float_type))
+
+    # what a trainer needs of DeviceScalarVariance: it takes the view below for its Adam entry, so there is nothing to bind
+    def trained_scalar_view(self, device=None):
+        """The 1-element view of sigma in the device buffer: a trainer updates it in place and every launch reads it there."""
+        if device is not None and self._buffer().device != torch.device(device):
+            self.to(device)
+        return self._buffer()[:1]
+
+    def bind_device_variance(self, t):
+        if t.data_ptr() != self._buffer().data_ptr():
+            raise ValueError("Ordinal: sigma lives in the likelihood's own device buffer; train trained_scalar_view()")
+
+    def mark_device_variance_changed(self):
+        self._stale = True
+
+    def lik_desc(self):
+        d = _abi.LikDesc()
+        d.type = _abi.LIK_ORDINAL
+        d.param[0], d.param[1] = self._sigma_host, float(self.bin_edges.size)      # (param[0]: possibly stale; it only refuses sigma <= 0)
+        d.param0_dev = self._buffer().data_ptr()
+        return d
+
+    grad_name = "lik_sigma"
+
+    def trained_scalar(self):
+        return self.grad_name, self.sigma
+
+    def check_targets(self, Y):
+        """Finite integers in [0, n]: the kernels index the edge array with them (the models call this once on the host when they are built)."""
+        import numpy as np
+        Yh = _host_targets(Y)
+        n = self.bin_edges.size
+        _refuse_targets("Ordinal", "integers in [0, %d]" % n, Yh, ~(np.isfinite(Yh) & (Yh >= 0) & (Yh <= n) & (Yh == np.floor(Yh))))
 
 
 def exp(x):

@@ -9,7 +9,7 @@ encoders of the latent-variable layers) and ``iwvi_dgp_forward``, whose workgrou
 tiling of X/Y over K, every layer, the Gaussian variational expectation and the local regularisers in LDS; the last workgroup
 to finish does the log-sum-exp over K, the scaled sum and subtracts the global KLs.
 
-A likelihood other than the Gaussian (``likelihoods.Bernoulli`` / ``StudentT`` / ``MultiClass`` / ``Poisson`` / ``Exponential`` / ``Gamma``) takes THREE: the layer launch runs without its tail and leaves
+A likelihood other than the Gaussian (``likelihoods.Bernoulli`` / ``StudentT`` / ``MultiClass`` / ``Poisson`` / ``Exponential`` / ``Gamma`` / ``Beta`` / ``Ordinal``) takes THREE: the layer launch runs without its tail and leaves
 the final layer's moments and the local regularisers, ``iwvi_lik_elbo_reduce`` does the rest (Gauss-Hermite variational expectations -- closed
 forms for the exp-link three --, the log-sum-exp, the bound).  For a Gaussian nothing differs from the two-launch form.  ``MultiClass`` alone has targets narrower than the
 final layer -- Y is one column of class labels, the layer has one output per class --: ``likelihoods.target_dim`` / ``output_dim`` translate.
@@ -95,6 +95,8 @@ class DGP_VI:
         self._mb_serial += 1
         for layer in self.layers:
             layer.to(device)
+        if hasattr(self.likelihood, "to"):                            # (an Ordinal's device buffer [sigma, edges])
+            self.likelihood.to(device)
         return self
 
     def _words(self):

@@ -52,7 +52,8 @@ class _HyperAdam:
         lik = model.likelihood
         lik_par = lik.trained_scalar() if hasattr(lik, "trained_scalar") else ("lik_var", lik.variance)
         if lik_par is not None:
-            t = torch.full((1,), lik_par[1], dtype=ft, device=dev)
+            # (an Ordinal's sigma lives at the head of the likelihood's own device buffer: its view is trained in place)
+            t = lik.trained_scalar_view(dev) if hasattr(lik, "trained_scalar_view") else torch.full((1,), lik_par[1], dtype=ft, device=dev)
             self.entries.append((lik_par[0], t, 1))
             lik.bind_device_variance(t)
             self.scalars.append((t, lik))

@@ -701,9 +701,34 @@ int iwvi_kde_density_grid(const float* samples, int64_t sample_stride, int64_t p
  *              enter out_lse_ms[:, 0], so out_lse_ms[:, 0] + log out_lse_ms[:, 1] - log K is still the point's log p.  Targets: POISSON
  *              integers >= 0, EXPONENTIAL >= 0, GAMMA > 0 (the caller's to check).  No clamp: where exp overflows float32 (|mu +- v/2| above
  *              about 88) the formulas give +-inf or NaN, as GPflow's do in float64 at 709.
+ *
+ *   BETA, ORDINAL   GPflow's Beta(scale) and Ordinal(bin_edges), both through the probit link with GPflow's jitter,
+ *              ip(x) = Phi(x) (1 - 2e-3) + 1e-3 (csrc/likelihood_bounded.hip).  Their values are 8 and 9: 7 is UNASSIGNED and refused as an
+ *              unknown type.  Neither has a closed form: variational expectation, predict_density (in log space; Fvar == NULL: logp) and
+ *              predict_mean_and_var are GPflow's base-class defaults by the 20-point rule above, as written out for the exp-link types,
+ *              and the heads are its reparameterised first-derivative form (iwvi_lik_elbo_backward below), v floored at 1e-8.
+ *                BETA      m = ip(F), alpha = m s, beta = s - alpha, Yc = clip(Y, 1e-6, 1 - 1e-6):
+ *                          logp = (alpha - 1) log Yc + (beta - 1) log(1 - Yc) + lgamma(s) - lgamma(alpha) - lgamma(beta);
+ *                          conditional mean m, variance (m - m^2) / (s + 1).
+ *                          param[0] = s = scale > 0, param0_dev honoured (the one trained scalar); lgamma(s) and digamma(s) are evaluated
+ *                          on the device, in float64, from the value the launch reads; digamma(alpha), digamma(beta) per node in float32.
+ *                          out_sums[1] = d ELBO / d scale.  Targets in [0, 1] (the caller's to check).  param[1] and lgc are unused.
+ *                ORDINAL   n strictly increasing edges e_0 .. e_(n-1) make n + 1 bins; Y holds the bin 0 .. n (as a float).  With
+ *                          l = e_Y / sigma (+inf for the top bin) and r = e_(Y-1) / sigma (-inf for the bottom bin):
+ *                          P_Y(F) = ip(l - F / sigma) - ip(r - F / sigma),  logp = log(P_Y + 1e-6);  the bins sum to 0.998.
+ *                          conditional mean sum_j j P_j, variance sum_j j^2 P_j - mean^2.
+ *                          param[1] = n, integral, 1 <= n <= IWVI_MAX_P - 1.  param0_dev is REQUIRED: 1 + n device floats
+ *                          [sigma, e_0 .. e_(n-1)]; sigma (> 0, the one trained scalar) is read there by every launch and the edges behind
+ *                          it.  param[0] is the host's copy of sigma and serves only to refuse sigma <= 0 before a launch.  lgc is unused.
+ *                          out_sums[1] = d ELBO / d sigma.  The jitter cancels in P_Y = (1 - 2e-3)(Phi(l') - Phi(r')), and the difference is
+ *                          formed on one side of 0 from erfc (across 0: from erf), never from two values near 1: float32 relative
+ *                          accuracy at any distance from the bin.  A label outside 0 .. n is read as the nearest bin.
+ *              IWVI_ERR_ARG (with iwvi_last_error) before any launch: BETA with param[0] <= 0 or NaN; ORDINAL with param[1] not an integer
+ *              in 1..31, with param0_dev == NULL, or with param[0] <= 0 or NaN.
  * ---------------------------------------------------------------------- */
 enum { IWVI_LIK_GAUSSIAN = 0, IWVI_LIK_BERNOULLI_PROBIT = 1, IWVI_LIK_STUDENT_T = 2, IWVI_LIK_MULTICLASS = 3,
-       IWVI_LIK_POISSON = 4, IWVI_LIK_EXPONENTIAL = 5, IWVI_LIK_GAMMA = 6 };
+       IWVI_LIK_POISSON = 4, IWVI_LIK_EXPONENTIAL = 5, IWVI_LIK_GAMMA = 6, /* 7: unassigned, refused as unknown */
+       IWVI_LIK_BETA = 8, IWVI_LIK_ORDINAL = 9 };
 typedef struct iwvi_lik_desc {
     int32_t type;
     float param[2];
@@ -721,7 +746,7 @@ int iwvi_lik_elbo_reduce(const iwvi_lik_desc* lik, const float* fmean, const flo
                          float* out_lse_ms, float* out_logp, double* out_elbo, uint64_t* ticket, void* stream);
 
 /* iwvi_iw_elbo_backward_dev with a likelihood descriptor: out_w, d_mean, d_var, out_sums[0] and [2] as there, out_sums[1] =
- * d ELBO / d param[0] (0 for the Bernoulli).  The heads use the reparameterised form of the rule, first derivatives only:
+ * d ELBO / d param[0] (0 for the Bernoulli; BETA: d / d scale; ORDINAL: d / d sigma, the head of param0_dev).  The heads use the reparameterised form of the rule, first derivatives only:
  *   dE/dmu = sum_i w_i g'(f_i),   dE/dv = sum_i w_i g'(f_i) x_i / sqrt(2 v)   with v floored at 1e-8. */
 int iwvi_lik_elbo_backward(const iwvi_lik_desc* lik, const float* fmean, const float* fvar, const float* Y, int Dy,
                            const float* const* kl_local, const int32_t* kl_dims, int n_local,
@@ -735,7 +760,7 @@ int iwvi_lik_elbo_backward(const iwvi_lik_desc* lik, const float* fmean, const f
  * iwvi_gaussian_var_exp.  iwvi_lik_predict_density: log of the predictive density (the Bernoulli's closed form at
  * p = inv_probit(Fmu / sqrt(1 + Fvar)), the Student-t's log-space quadrature of logp); Fvar == NULL: logp(Fmu, Y).
  * iwvi_lik_predict_mean_and_var (n elements): Bernoulli (p, p - p^2) at that p; Student-t (Fmu, E[s^2 nu/(nu - 2) + F^2] - Fmu^2) by the
- * rule, nu > 2 required; Gaussian (Fmu, Fvar + variance). */
+ * rule, nu > 2 required; Gaussian (Fmu, Fvar + variance); the exp-link types, BETA and ORDINAL: the rule over the conditional moments. */
 int iwvi_lik_var_exp(const iwvi_lik_desc* lik, const float* Fmu, const float* Fvar, const float* Y,
                      int64_t T, int Dy, int64_t row_div, int64_t row_mod, float* out, void* stream);
 int iwvi_lik_predict_density(const iwvi_lik_desc* lik, const float* Fmu, const float* Fvar, const float* Y,
@@ -756,7 +781,7 @@ int iwvi_lik_predict_mean_and_var(const iwvi_lik_desc* lik, const float* Fmu, co
  * log-sum-exp is shifted by the running float32 maximum and summed in float64 (a point whose every draw has density -inf gives -inf, not
  * NaN); sum_s E_s and sum_s (Var_s + E_s^2) accumulate in float64 and out_var is formed there and rounded once.  The exp-link types add a
  * point's target-only terms (sum_d c0(y_d)) once, outside the log-sum-exp.
- * Any output may be NULL, at least one must be given, out_mean and out_var go together.  All seven types are accepted -- the Gaussian's
+ * Any output may be NULL, at least one must be given, out_mean and out_var go together.  All nine types are accepted -- the Gaussian's
  * out_logp is what iwvi_dgp_predict_density computes from the same moments: a cross-check.  A Student-t with df <= 2 is refused only when
  * the moments are asked for.  IWVI_ERR_ARG (with iwvi_last_error) before any launch for: a null or invalid descriptor, N < 0, S < 1, Dy
  * outside 1..IWVI_MAX_P, MULTICLASS with Dy != C, out_logp without Y or Y without out_logp, out_mean without out_var or the reverse, no
