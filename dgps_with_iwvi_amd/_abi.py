@@ -39,6 +39,7 @@ LIK_GAUSSIAN, LIK_BERNOULLI_PROBIT, LIK_STUDENT_T, LIK_MULTICLASS = 0, 1, 2, 3  
 LIK_POISSON, LIK_EXPONENTIAL, LIK_GAMMA = 4, 5, 6                                # (exp link: csrc/likelihood_explink.hip)
 LIK_BETA, LIK_ORDINAL = 8, 9                                                     # (probit link: csrc/likelihood_bounded.hip; 7 is unassigned)
 BW_ROUTE_CHAIN, BW_ROUTE_MID, BW_ROUTE_GEMM = 1, 2, 3   # iwvi_debug_last_backward_routes
+FW_TAIL_BOUND, FW_TAIL_DENSITY, FW_TAIL_SAMPLES = 0, 1, 2   # iwvi_debug_forward_plan
 
 
 class IwviError(RuntimeError):
@@ -227,6 +228,9 @@ PROTOTYPES = {
     "iwvi_dgp_forward": (c_int, [ctypes.POINTER(LayerDesc), c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                  c_int64, c_int64, c_int64, c_float, ctypes.c_uint64, c_void_p, c_void_p,
                                  ctypes.POINTER(ElboDesc), c_void_p]),
+    "iwvi_debug_forward_plan": (c_int, [ctypes.POINTER(LayerDesc), c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                        c_int64, c_int64, c_int64, c_float, ctypes.c_uint64, c_void_p, c_void_p,
+                                        ctypes.POINTER(ElboDesc), c_void_p, c_int, ctypes.POINTER(c_int64)]),
     "iwvi_logw_reduce": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, ctypes.POINTER(c_void_p),
                                  ctypes.POINTER(ctypes.c_int32), c_int, c_double, c_int, c_int,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -2639,15 +2639,6 @@ __global__ __launch_bounds__(FW_THREADS) void k_dgp_forward(const FwArgs gk) {
     if constexpr (!LEAN) { fw_arrive<NS>(gk, sm, tid, chunk_id); FW_STAMP(63); }
 }
 
-// the packed arrival (fw_arrive_fast) applies when every point's K samples sit in one chunk (the kernel's local_lse), the launch finishes the
-// ELBO itself, its arrivals fit the 9-bit count and the scratch holds a tagged slot per chunk for the exact (overflow) path
-static void fw_decide_fast(FwArgs& a, unsigned grid, int nsamp, int64_t T) {
-    const FwElbo& E = a.h.e;
-    const int64_t ws_len = (T + 15) / 16;
-    a.h.e.fast = (E.enabled && E.ws && E.elbo && !E.mode_vi && E.stride_k == 1 && E.stride_b == E.K && E.K > 0 && (nsamp % E.K) == 0 &&
-                  a.h.rng_state && grid <= 511u && 2 * (int64_t)a.h.nchunks <= ws_len && E.kl_total <= 64 && !dbg_opt("IWVI_FW_SLOW_TAIL")) ? 1 : 0;
-}
-
 template <int NS, bool S16, bool BIG, int LEAN_MODE = 0, bool F64 = false>
 static int launch_forward(const FwArgs& a, unsigned grid, size_t lds_bytes, hipStream_t stream) {
     static size_t attr_set = 0;
@@ -2748,7 +2739,8 @@ static void plan_stage2(FwGp& G) {
 }
 
 // LDS image for a chunk of nsamp samples; fills the per-layer offsets of `a`.  stage_zt: keep every GP layer's
-// Gram operand Z~ in LDS for the whole launch.
+// Gram operand Z~ in LDS for the whole launch.  Returns the image's bytes, or 0 (error text set) for a stack
+// whose prologue copy list would pass FW_MAX_COPY entries.
 static size_t fw_plan_lds(FwArgs& a, int nsamp, int maxR, int maxP, bool stage_zt, bool stage_ls) {
     int scratch = 0, zdims = 0, o = 0, ls_max = 0;
     FwLds& l = a.h.lds;
@@ -2760,9 +2752,9 @@ static size_t fw_plan_lds(FwArgs& a, int nsamp, int maxR, int maxP, bool stage_z
     l.rowi = o; o += nsamp;
     l.pidx = o; o += nsamp;
     {
-        bool big = false;                                   // a layer with M > 128: one |a|^2 slot per wave besides the two
-        for (int i = 0; i < a.h.n_layers; ++i) if (a.L[i].type == IWVI_LAYER_GP && (a.L[i].gp.nbk >= FW_SB_MIN_NBK || inv8_layer(a.L[i].gp.nbk))) big = true;
-        l.asq = o; o += (big ? 2 + FW_WAVES : 2) * nsamp;
+        bool asq_per_wave = false;                          // a super-block (M > 240) or inv8 layer: one |a|^2 slot per wave besides the two
+        for (int i = 0; i < a.h.n_layers; ++i) if (a.L[i].type == IWVI_LAYER_GP && (a.L[i].gp.nbk >= FW_SB_MIN_NBK || inv8_layer(a.L[i].gp.nbk))) asq_per_wave = true;
+        l.asq = o; o += (asq_per_wave ? 2 + FW_WAVES : 2) * nsamp;
     }
     l.meanp = o; o += maxR * nsamp;
     l.gbuf = o; o += 3 * maxR * nsamp;
@@ -2816,11 +2808,14 @@ static size_t fw_plan_lds(FwArgs& a, int nsamp, int maxR, int maxP, bool stage_z
     o += up4(zdims * nsamp);
     // work lists of the prologue
     a.h.ncopy = 0;
+    int wanted = 0;                                     // entries asked for; the list holds FW_MAX_COPY of them, a longer one is counted and refused below
+    auto append = [&](const float* src, int n, int dst) {
+        if (wanted++ < FW_MAX_COPY) { FwCopy& c = a.C[a.h.ncopy++]; c.src = src; c.n = n; c.dst = dst; }
+    };
     auto add_copy = [&](const float* src, int n, int dst, bool vec) {
         if (!src || n <= 0) return;
-        FwCopy& c = a.C[a.h.ncopy++];
         const bool v16 = vec && (n % 4 == 0) && (dst % 4 == 0) && (((uintptr_t)src) % 16 == 0);
-        c.src = src; c.n = v16 ? -n : n; c.dst = dst;
+        append(src, v16 ? -n : n, dst);
     };
     // the first staged GP layer's forward-substitution stream rides in the prologue; every later one is fetched by
     // the GP layer before it, once that layer's solve has released the buffer
@@ -2878,7 +2873,7 @@ static size_t fw_plan_lds(FwArgs& a, int nsamp, int maxR, int maxP, bool stage_z
                 const int nW = V.dims[k] * V.dims[k + 1], nb = V.dims[k + 1];
                 add_copy(V.W[k], nW, L.c_off + off, true);
                 if (V.b[k]) add_copy(V.b[k], nb, L.c_off + off + nW, true);
-                else { FwCopy& c = a.C[a.h.ncopy++]; c.src = nullptr; c.n = nb; c.dst = L.c_off + off + nW; }
+                else append(nullptr, nb, L.c_off + off + nW);          // (no source: the kernel zeroes the bias)
                 off += nW + nb;
             }
         }
@@ -2898,7 +2893,8 @@ static size_t fw_plan_lds(FwArgs& a, int nsamp, int maxR, int maxP, bool stage_z
             if (a.h.zt_mask >> i & 1) add_copy(a.L[i].gp.ZtP, a.L[i].gp.nbk * a.L[i].gp.nsteps * 64, a.L[i].gp.zt_off, true);
         a.h.n_early = 0; a.h.zt_mask = 0;
     }
-    l.cnt = o; o += 24;                                  // 12 counters / scalars, then one kernel variance per layer (device scalars, fetched in the prologue)
+    if (wanted > FW_MAX_COPY) { set_error("iwvi_dgp_forward: the prologue's copy list needs %d entries (FW_MAX_COPY = %d)", wanted, FW_MAX_COPY); return 0; }
+    l.cnt = o; o += 24;                                 // 12 counters / scalars, then one kernel variance per layer (device scalars, fetched in the prologue)
     l.scratch = o; o += up4(scratch);
     l.total = o;
     return (size_t)o * sizeof(float);
@@ -2918,157 +2914,206 @@ __global__ __launch_bounds__(256) void k_pred_lse_merge(const float2* __restrict
     out[n] = (m == -INFINITY) ? -INFINITY : m + logf(ssum) - logf((float)S);
 }
 
-struct FwPredict { int64_t N, S; float* out_logp; void* ws; float* out_y; const float* z_y; };   // out_y: the sampling tail (FW_MODE_SAMPLE) instead
+// ---- the host driver: everything about a call is decided into one FwPlan before the first HIP call, then launched ------------------------
+struct FwPredict { int mode; int64_t N, S; float* out_logp; void* ws; float* out_y; const float* z_y; };   // mode: FW_MODE_PREDICT (out_logp, ws) or FW_MODE_SAMPLE (out_y, z_y)
+struct FwCall {                          // a forward entry's arguments as given; pred: one of the two predictive tails instead of the bound's
+    const iwvi_layer_desc* layers; int n_layers; const float* X; int Dx; const float* XY; int XYdim; const float* Y; int Dy;
+    int64_t T, row_div, row_mod; float lik_variance; uint64_t seed; uint64_t* rng_state; float* out_logw; const iwvi_elbo_desc* elbo;
+    const FwPredict* pred; const float* lik_variance_dev;
+};
+struct FwVariant { int ns; bool s16, big, f64; int mode; };   // one k_dgp_forward instantiation; mode: 0, 1 (LEAN), 2 (SHP), FW_MODE_PREDICT, FW_MODE_SAMPLE
+struct FwPlan {
+    FwArgs a; FwVariant v; unsigned grid; size_t lds_bytes;
+    // decided once, from the descriptors: stage 2 on split-f16 operands in every GP layer (an even number of 16-row blocks each, no layer asks
+    // for another arithmetic); a layer on the float64 stage-1 route; a layer asks for the fp32-MFMA stage 2; a layer with M > 128 (nbk > 8)
+    bool s16_all, f64_any, f32_req, big;
+    int D, maxR, maxP; bool need_rng;    // running over the layers: columns of the next layer's input, widest R and P, a layer draws its own noise
+};
 
-static int dgp_forward_core(const iwvi_layer_desc* layers, int n_layers, const float* X, int Dx, const float* XY, int XYdim,
-                            const float* Y, int Dy, int64_t T, int64_t row_div, int64_t row_mod, float lik_variance,
-                            uint64_t seed, uint64_t* rng_state, float* out_logw, const iwvi_elbo_desc* elbo, hipStream_t stream,
-                            const FwPredict* pred, const float* lik_variance_dev) {
-    if (T <= 0) return IWVI_OK;                         // empty batch: nothing to do
-    if (!layers || n_layers <= 0 || n_layers > IWVI_MAX_STACK) { set_error("iwvi_dgp_forward: %d layers (1..%d supported)", n_layers, IWVI_MAX_STACK); return IWVI_ERR_ARG; }
-    if (!X || Dx <= 0 || Dx > IWVI_MAX_D) { set_error("iwvi_dgp_forward: null X or Dx=%d out of range (1..%d)", Dx, IWVI_MAX_D); return IWVI_ERR_ARG; }
-    if (row_div < 1 || row_mod < 1) { set_error("iwvi_dgp_forward: row_div=%lld / row_mod=%lld must be >= 1", (long long)row_div, (long long)row_mod); return IWVI_ERR_ARG; }
-    if (row_mod > 0x7fffffffLL || row_div > 0x7fffffffLL || T > 0x7fffffffLL - 4096) { set_error("iwvi_dgp_forward: more than 2^31 rows / samples"); return IWVI_ERR_ARG; }
-    if (out_logw && (!Y || Dy <= 0 || Dy > IWVI_MAX_P || !(lik_variance > 0.f))) { set_error("iwvi_dgp_forward: out_logw needs Y, 1 <= Dy <= %d and a positive likelihood variance", IWVI_MAX_P); return IWVI_ERR_ARG; }
-    FwArgs a{};
-    a.h.n_layers = n_layers; a.h.X = X; a.h.XY = nullptr; a.h.Y = Y; a.h.Dx = Dx; a.h.XYdim = XYdim; a.h.Dy = Dy;
-    a.h.T = T; a.h.row_div = (unsigned)row_div; a.h.row_mod = (unsigned)row_mod; a.h.lik_variance = lik_variance;
-    a.h.seed = seed; a.h.rng_state = (unsigned long long*)rng_state; a.h.out_logw = out_logw;
-    int D = Dx, maxR = 1, maxP = 1;
-    bool need_rng = false;
-    // stage 2 on split-f16 operands (one kernel variant for the launch): every GP layer must have an even number of 16-row blocks
-    bool s16_all = true;                                         // ... and none asks for the fp32 variant (IWVI_LAYER_F32_STAGE2: per call, not per process)
-    for (int i = 0; i < n_layers; ++i) if (layers[i].type == IWVI_LAYER_GP && (layers[i].flags & IWVI_LAYER_F32_STAGE2)) s16_all = false;
-    for (int i = 0; i < n_layers; ++i) if (layers[i].type == IWVI_LAYER_GP && ((round_up(layers[i].M, 16) / 16) & 1)) s16_all = false;
-    // float64 stage-1 route (IWVI_LAYER_F64_STAGE1 on any GP layer): the F64 kernel variants -- fp32 stage 2, the flagged layers' Gram and solve in float64
-    bool f64_any = false;
-    for (int i = 0; i < n_layers; ++i) if (layers[i].type == IWVI_LAYER_GP && (layers[i].flags & IWVI_LAYER_F64_STAGE1)) f64_any = true;
-    if (f64_any) s16_all = false;
-    for (int i = 0; i < n_layers; ++i) {
-        const iwvi_layer_desc& d = layers[i];
-        FwLayer& L = a.L[i];
-        L.type = d.type; L.D = D; L.zero_noise = d.zero_noise;
+static int plan_check_call(const FwCall& c, FwPlan& p) {
+    const int n_layers = c.n_layers, Dx = c.Dx, Dy = c.Dy;
+    if (!c.layers || n_layers <= 0 || n_layers > IWVI_MAX_STACK) { set_error("iwvi_dgp_forward: %d layers (1..%d supported)", n_layers, IWVI_MAX_STACK); return IWVI_ERR_ARG; }
+    if (!c.X || Dx <= 0 || Dx > IWVI_MAX_D) { set_error("iwvi_dgp_forward: null X or Dx=%d out of range (1..%d)", Dx, IWVI_MAX_D); return IWVI_ERR_ARG; }
+    if (c.row_div < 1 || c.row_mod < 1) { set_error("iwvi_dgp_forward: row_div=%lld / row_mod=%lld must be >= 1", (long long)c.row_div, (long long)c.row_mod); return IWVI_ERR_ARG; }
+    if (c.row_mod > 0x7fffffffLL || c.row_div > 0x7fffffffLL || c.T > 0x7fffffffLL - 4096) { set_error("iwvi_dgp_forward: more than 2^31 rows / samples"); return IWVI_ERR_ARG; }
+    if (c.out_logw && (!c.Y || Dy <= 0 || Dy > IWVI_MAX_P || !(c.lik_variance > 0.f))) { set_error("iwvi_dgp_forward: out_logw needs Y, 1 <= Dy <= %d and a positive likelihood variance", IWVI_MAX_P); return IWVI_ERR_ARG; }
+    FwHead& h = p.a.h;
+    h.n_layers = n_layers; h.X = c.X; h.XY = nullptr; h.Y = c.Y; h.Dx = Dx; h.XYdim = c.XYdim; h.Dy = Dy;
+    h.T = c.T; h.row_div = (unsigned)c.row_div; h.row_mod = (unsigned)c.row_mod; h.lik_variance = c.lik_variance;
+    h.seed = c.seed; h.rng_state = (unsigned long long*)c.rng_state; h.out_logw = c.out_logw;
+    // one kernel variant for the launch (per call, not per process): split-f16 stage 2 needs an even number of 16-row blocks in every GP layer
+    // and no layer that asks for the fp32 variant (IWVI_LAYER_F32_STAGE2) or the float64 stage-1 route (IWVI_LAYER_F64_STAGE1 on any GP layer:
+    // the F64 kernel variants -- fp32 stage 2, the flagged layers' Gram and solve in float64)
+    p.s16_all = true;
+    for (int i = 0; i < n_layers; ++i) if (c.layers[i].type == IWVI_LAYER_GP) {
+        if (c.layers[i].flags & IWVI_LAYER_F32_STAGE2) p.f32_req = true;
+        if (c.layers[i].flags & IWVI_LAYER_F64_STAGE1) p.f64_any = true;
+        if ((round_up(c.layers[i].M, 16) / 16) & 1) p.s16_all = false;
+    }
+    if (p.f32_req || p.f64_any) p.s16_all = false;
+    p.D = Dx; p.maxR = p.maxP = 1;
+    return IWVI_OK;
+}
+
+static int plan_gp_layer(const FwCall& c, int i, FwPlan& p) {
+    const iwvi_layer_desc& d = c.layers[i];
+    const int D = p.D;
+    if (d.D != D) { set_error("iwvi_dgp_forward: layer %d expects D=%d but its input has %d columns", i, d.D, D); return IWVI_ERR_ARG; }
+    if (!d.state) { set_error("iwvi_dgp_forward: layer %d has no precomputed state", i); return IWVI_ERR_ARG; }
+    if (d.M <= 0 || d.M > IWVI_MAX_M || D > IWVI_MAX_D || d.R <= 0 || d.R > IWVI_MAX_R || d.P <= 0 || d.P > IWVI_MAX_P) {
+        set_error("iwvi_gp_layer_forward: size out of range (M=%d D=%d R=%d P=%d)", d.M, D, d.R, d.P); return IWVI_ERR_ARG;
+    }
+    if (!d.W && d.P != d.R) { set_error("iwvi_gp_layer_forward: P=%d must equal R=%d without a mixing matrix", d.P, d.R); return IWVI_ERR_ARG; }
+    if (d.mf_type == IWVI_MF_IDENTITY && d.P != D) { set_error("iwvi_gp_layer_forward: Identity mean function needs P == D (%d vs %d)", d.P, D); return IWVI_ERR_ARG; }
+    if (d.mf_type == IWVI_MF_LINEAR && !d.mf_A) { set_error("iwvi_gp_layer_forward: Linear mean function without A"); return IWVI_ERR_ARG; }
+    if (d.mf_type < IWVI_MF_ZERO || d.mf_type > IWVI_MF_LINEAR) { set_error("iwvi_gp_layer_forward: unknown mean function %d", d.mf_type); return IWVI_ERR_UNSUPPORTED; }
+    if (d.kern_type != IWVI_KERN_RBF && d.kern_type != IWVI_KERN_MATERN52) { set_error("iwvi_gp_layer_forward: unknown kernel type %d", d.kern_type); return IWVI_ERR_UNSUPPORTED; }
+    const StateLayout s = state_layout(d.M, d.R);
+    const char* st = (const char*)d.state;
+    FwGp& G = p.a.L[i].gp;
+    G.LsP = (const f32x4*)(st + s.off_LsP); G.LrTP = (const f32x4*)(st + s.off_LrTP);
+    G.QmuP = (const f32x4*)(st + s.off_QmuP); G.ZtP = (const float*)(st + s.off_ZtP);
+    G.cst = (const float*)(st + s.off_cst);
+    G.W = d.W; G.mfA = d.mf_A; G.mfb = d.mf_b; G.a_out = d.a_out; G.u_out = d.u_out;
+    G.M = d.M; G.Mp = s.Mp; G.nbk = s.nbk; G.nrb = s.nrb; G.nsteps = round_up(D + 2, 4) / 4;
+    G.R = d.R; G.P = d.P; G.kern_type = d.kern_type; G.mf_type = d.mf_type; G.variance = d.variance;
+    p.a.h.var_dev[i] = d.variance_dev;
+    if (d.variance_dev) p.a.h.var_dev_mask |= 1u << i;
+    G.s16 = p.s16_all ? 1 : 0;
+    G.f64 = (d.flags & IWVI_LAYER_F64_STAGE1) ? 1 : 0;
+    if (G.s16) { G.LrTP = (const f32x4*)(st + s.off_LrT16); G.QmuP = (const f32x4*)(st + s.off_Qmu16); }
+    plan_stage2(G);
+    if (G.nbk > 8) p.big = true;
+    if (d.R > p.maxR) p.maxR = d.R;
+    if (d.P > p.maxP) p.maxP = d.P;
+    p.D = d.P;
+    return IWVI_OK;
+}
+
+static int plan_lv_layer(const FwCall& c, int i, FwPlan& p) {
+    const iwvi_layer_desc& d = c.layers[i];
+    const int D = p.D;
+    FwLv& V = p.a.L[i].lv;
+    if (d.latent_dim <= 0 || D + d.latent_dim > IWVI_MAX_D) { set_error("iwvi_lv_layer_forward: bad D=%d (1..32) or latent_dim=%d", D, d.latent_dim); return IWVI_ERR_ARG; }
+    V.Lw = d.latent_dim; V.sampled_kl = d.sampled_kl; V.kl_local = d.kl_local;
+    V.n_enc = 0; V.wtotal = 0; V.maxdim = 2 * d.latent_dim; V.enc_out = d.enc_out;
+    if (d.enc_W && !d.enc_out) {
+        if (!c.XY || c.XYdim <= 0) { set_error("iwvi_dgp_forward: layer %d has an encoder but there are no encoder inputs", i); return IWVI_ERR_ARG; }
+        if (!d.enc_dims || d.n_enc <= 0 || d.n_enc > IWVI_MAX_ENC) { set_error("iwvi_lv_layer_forward: encoder with %d layers (1..%d supported)", d.n_enc, IWVI_MAX_ENC); return IWVI_ERR_ARG; }
+        if (d.enc_dims[0] != c.XYdim) { set_error("iwvi_lv_layer_forward: encoder expects %d inputs, XY has %d", d.enc_dims[0], c.XYdim); return IWVI_ERR_ARG; }
+        if (d.enc_dims[d.n_enc] != 2 * d.latent_dim) { set_error("iwvi_lv_layer_forward: encoder output %d != 2*latent_dim %d", d.enc_dims[d.n_enc], 2 * d.latent_dim); return IWVI_ERR_ARG; }
+        for (int k = 0; k <= d.n_enc; ++k) {
+            if (d.enc_dims[k] <= 0 || d.enc_dims[k] > 64) { set_error("iwvi_lv_layer_forward: encoder width %d out of range (1..64)", d.enc_dims[k]); return IWVI_ERR_ARG; }
+            V.dims[k] = d.enc_dims[k];
+            if (d.enc_dims[k] > V.maxdim) V.maxdim = d.enc_dims[k];
+        }
+        for (int k = 0; k < d.n_enc; ++k) {
+            if (!d.enc_W[k]) { set_error("iwvi_lv_layer_forward: null encoder weight %d", k); return IWVI_ERR_ARG; }
+            V.W[k] = d.enc_W[k]; V.b[k] = d.enc_b ? d.enc_b[k] : nullptr;
+            V.wtotal += d.enc_dims[k] * d.enc_dims[k + 1] + d.enc_dims[k + 1];
+        }
+        V.n_enc = d.n_enc; V.act = d.enc_act;
+        if (d.enc_act < IWVI_ACT_TANH || d.enc_act > IWVI_ACT_IDENTITY) { set_error("iwvi_lv_layer_forward: unknown activation %d", d.enc_act); return IWVI_ERR_UNSUPPORTED; }
+        p.a.h.XY = c.XY;
+    }
+    if (D + d.latent_dim > p.maxP) p.maxP = D + d.latent_dim;
+    p.D += d.latent_dim;
+    return IWVI_OK;
+}
+
+static int plan_layers(const FwCall& c, FwPlan& p) {
+    for (int i = 0; i < c.n_layers; ++i) {
+        const iwvi_layer_desc& d = c.layers[i];
+        FwLayer& L = p.a.L[i];
+        L.type = d.type; L.D = p.D; L.zero_noise = d.zero_noise;
         L.noise = d.noise; L.noise_out = d.noise_out; L.sample = d.sample; L.mean = d.mean; L.var = d.var;
         L.gmv_out = (d.type == IWVI_LAYER_GP) ? d.gmv_out : nullptr;
-        if (!d.noise && !d.zero_noise) need_rng = true;
-        if (d.type == IWVI_LAYER_GP) {
-            if (d.D != D) { set_error("iwvi_dgp_forward: layer %d expects D=%d but its input has %d columns", i, d.D, D); return IWVI_ERR_ARG; }
-            if (!d.state) { set_error("iwvi_dgp_forward: layer %d has no precomputed state", i); return IWVI_ERR_ARG; }
-            if (d.M <= 0 || d.M > IWVI_MAX_M || D > IWVI_MAX_D || d.R <= 0 || d.R > IWVI_MAX_R || d.P <= 0 || d.P > IWVI_MAX_P) {
-                set_error("iwvi_gp_layer_forward: size out of range (M=%d D=%d R=%d P=%d)", d.M, D, d.R, d.P); return IWVI_ERR_ARG;
-            }
-            if (!d.W && d.P != d.R) { set_error("iwvi_gp_layer_forward: P=%d must equal R=%d without a mixing matrix", d.P, d.R); return IWVI_ERR_ARG; }
-            if (d.mf_type == IWVI_MF_IDENTITY && d.P != D) { set_error("iwvi_gp_layer_forward: Identity mean function needs P == D (%d vs %d)", d.P, D); return IWVI_ERR_ARG; }
-            if (d.mf_type == IWVI_MF_LINEAR && !d.mf_A) { set_error("iwvi_gp_layer_forward: Linear mean function without A"); return IWVI_ERR_ARG; }
-            if (d.mf_type < IWVI_MF_ZERO || d.mf_type > IWVI_MF_LINEAR) { set_error("iwvi_gp_layer_forward: unknown mean function %d", d.mf_type); return IWVI_ERR_UNSUPPORTED; }
-            if (d.kern_type != IWVI_KERN_RBF && d.kern_type != IWVI_KERN_MATERN52) { set_error("iwvi_gp_layer_forward: unknown kernel type %d", d.kern_type); return IWVI_ERR_UNSUPPORTED; }
-            const StateLayout s = state_layout(d.M, d.R);
-            const char* st = (const char*)d.state;
-            FwGp& G = L.gp;
-            G.LsP = (const f32x4*)(st + s.off_LsP); G.LrTP = (const f32x4*)(st + s.off_LrTP);
-            G.QmuP = (const f32x4*)(st + s.off_QmuP); G.ZtP = (const float*)(st + s.off_ZtP);
-            G.cst = (const float*)(st + s.off_cst);
-            G.W = d.W; G.mfA = d.mf_A; G.mfb = d.mf_b; G.a_out = d.a_out; G.u_out = d.u_out;
-            G.M = d.M; G.Mp = s.Mp; G.nbk = s.nbk; G.nrb = s.nrb; G.nsteps = round_up(D + 2, 4) / 4;
-            G.R = d.R; G.P = d.P; G.kern_type = d.kern_type; G.mf_type = d.mf_type; G.variance = d.variance;
-            a.h.var_dev[i] = d.variance_dev;
-            if (d.variance_dev) a.h.var_dev_mask |= 1u << i;
-            G.s16 = s16_all ? 1 : 0;
-            G.f64 = (d.flags & IWVI_LAYER_F64_STAGE1) ? 1 : 0;
-            if (G.s16) { G.LrTP = (const f32x4*)(st + s.off_LrT16); G.QmuP = (const f32x4*)(st + s.off_Qmu16); }
-            plan_stage2(G);
-            if (d.R > maxR) maxR = d.R;
-            if (d.P > maxP) maxP = d.P;
-            D = d.P;
-        } else if (d.type == IWVI_LAYER_LV) {
-            FwLv& V = L.lv;
-            if (d.latent_dim <= 0 || D + d.latent_dim > IWVI_MAX_D) { set_error("iwvi_lv_layer_forward: bad D=%d (1..32) or latent_dim=%d", D, d.latent_dim); return IWVI_ERR_ARG; }
-            V.Lw = d.latent_dim; V.sampled_kl = d.sampled_kl; V.kl_local = d.kl_local;
-            V.n_enc = 0; V.wtotal = 0; V.maxdim = 2 * d.latent_dim; V.enc_out = d.enc_out;
-            if (d.enc_W && !d.enc_out) {
-                if (!XY || XYdim <= 0) { set_error("iwvi_dgp_forward: layer %d has an encoder but there are no encoder inputs", i); return IWVI_ERR_ARG; }
-                if (!d.enc_dims || d.n_enc <= 0 || d.n_enc > IWVI_MAX_ENC) { set_error("iwvi_lv_layer_forward: encoder with %d layers (1..%d supported)", d.n_enc, IWVI_MAX_ENC); return IWVI_ERR_ARG; }
-                if (d.enc_dims[0] != XYdim) { set_error("iwvi_lv_layer_forward: encoder expects %d inputs, XY has %d", d.enc_dims[0], XYdim); return IWVI_ERR_ARG; }
-                if (d.enc_dims[d.n_enc] != 2 * d.latent_dim) { set_error("iwvi_lv_layer_forward: encoder output %d != 2*latent_dim %d", d.enc_dims[d.n_enc], 2 * d.latent_dim); return IWVI_ERR_ARG; }
-                for (int k = 0; k <= d.n_enc; ++k) {
-                    if (d.enc_dims[k] <= 0 || d.enc_dims[k] > 64) { set_error("iwvi_lv_layer_forward: encoder width %d out of range (1..64)", d.enc_dims[k]); return IWVI_ERR_ARG; }
-                    V.dims[k] = d.enc_dims[k];
-                    if (d.enc_dims[k] > V.maxdim) V.maxdim = d.enc_dims[k];
-                }
-                for (int k = 0; k < d.n_enc; ++k) {
-                    if (!d.enc_W[k]) { set_error("iwvi_lv_layer_forward: null encoder weight %d", k); return IWVI_ERR_ARG; }
-                    V.W[k] = d.enc_W[k]; V.b[k] = d.enc_b ? d.enc_b[k] : nullptr;
-                    V.wtotal += d.enc_dims[k] * d.enc_dims[k + 1] + d.enc_dims[k + 1];
-                }
-                V.n_enc = d.n_enc; V.act = d.enc_act;
-                if (d.enc_act < IWVI_ACT_TANH || d.enc_act > IWVI_ACT_IDENTITY) { set_error("iwvi_lv_layer_forward: unknown activation %d", d.enc_act); return IWVI_ERR_UNSUPPORTED; }
-                a.h.XY = XY;
-            }
-            if (D + d.latent_dim > maxP) maxP = D + d.latent_dim;
-            D += d.latent_dim;
-        } else { set_error("iwvi_dgp_forward: unknown layer type %d", d.type); return IWVI_ERR_ARG; }
+        if (!d.noise && !d.zero_noise) p.need_rng = true;
+        if (d.type != IWVI_LAYER_GP && d.type != IWVI_LAYER_LV) { set_error("iwvi_dgp_forward: unknown layer type %d", d.type); return IWVI_ERR_ARG; }
+        const int rc = d.type == IWVI_LAYER_GP ? plan_gp_layer(c, i, p) : plan_lv_layer(c, i, p);
+        if (rc != IWVI_OK) return rc;
     }
-    if (out_logw || pred) {
-        if (layers[n_layers - 1].type != IWVI_LAYER_GP || D != Dy) { set_error("iwvi_dgp_forward: the last layer must be a GP layer with P == Dy (%d vs %d)", D, Dy); return IWVI_ERR_ARG; }
+    if ((c.out_logw || c.pred) && (c.layers[c.n_layers - 1].type != IWVI_LAYER_GP || p.D != c.Dy)) {
+        set_error("iwvi_dgp_forward: the last layer must be a GP layer with P == Dy (%d vs %d)", p.D, c.Dy); return IWVI_ERR_ARG;
     }
-    if (need_rng && !rng_state) { set_error("iwvi_dgp_forward: a layer draws its own noise but rng_state is NULL"); return IWVI_ERR_ARG; }
-    if (elbo) {
-        if (!out_logw || !rng_state) { set_error("iwvi_dgp_forward: the fused ELBO needs out_logw and rng_state (its ticket word)"); return IWVI_ERR_ARG; }
-        if (elbo->B <= 0 || elbo->K <= 0 || elbo->n_glob < 0 || elbo->n_glob > FW_MAX_GLOB) { set_error("iwvi_dgp_forward: bad ELBO descriptor (B=%lld K=%d n_glob=%d)", (long long)elbo->B, elbo->K, elbo->n_glob); return IWVI_ERR_ARG; }
-        const int64_t last_row = (elbo->B - 1) * elbo->stride_b + (int64_t)(elbo->K - 1) * elbo->stride_k;
-        if (elbo->stride_b < 0 || elbo->stride_k < 0 || last_row >= T) { set_error("iwvi_dgp_forward: ELBO strides address row %lld of %lld", (long long)last_row, (long long)T); return IWVI_ERR_ARG; }
-        FwElbo& E = a.h.e;
-        E.enabled = 1; E.K = elbo->K; E.K_total = elbo->K_total > 0 ? elbo->K_total : elbo->K; E.mode_vi = elbo->mode_vi;
-        E.B = elbo->B; E.stride_b = elbo->stride_b; E.stride_k = elbo->stride_k; E.scale = elbo->scale;
-        E.n_glob = elbo->n_glob;
-        for (int i = 0; i < elbo->n_glob; ++i) {
-            if (!elbo->kl_global || !elbo->kl_global[i]) { set_error("iwvi_dgp_forward: null global KL pointer %d", i); return IWVI_ERR_ARG; }
-            E.klg[i] = elbo->kl_global[i];
-            E.klg_n[i] = elbo->kl_global_counts ? elbo->kl_global_counts[i] : 1;
-            if (E.klg_n[i] <= 0 || E.klg_n[i] > IWVI_MAX_R) { set_error("iwvi_dgp_forward: bad global KL count %d", E.klg_n[i]); return IWVI_ERR_ARG; }
-            E.kl_total += E.klg_n[i];
+    if (p.need_rng && !c.rng_state) { set_error("iwvi_dgp_forward: a layer draws its own noise but rng_state is NULL"); return IWVI_ERR_ARG; }
+    return IWVI_OK;
+}
+
+static int plan_elbo(const FwCall& c, FwPlan& p) {
+    const iwvi_elbo_desc* elbo = c.elbo;
+    if (!elbo) return IWVI_OK;
+    if (!c.out_logw || !c.rng_state) { set_error("iwvi_dgp_forward: the fused ELBO needs out_logw and rng_state (its ticket word)"); return IWVI_ERR_ARG; }
+    if (elbo->B <= 0 || elbo->K <= 0 || elbo->n_glob < 0 || elbo->n_glob > FW_MAX_GLOB) { set_error("iwvi_dgp_forward: bad ELBO descriptor (B=%lld K=%d n_glob=%d)", (long long)elbo->B, elbo->K, elbo->n_glob); return IWVI_ERR_ARG; }
+    const int64_t last_row = (elbo->B - 1) * elbo->stride_b + (int64_t)(elbo->K - 1) * elbo->stride_k;
+    if (elbo->stride_b < 0 || elbo->stride_k < 0 || last_row >= c.T) { set_error("iwvi_dgp_forward: ELBO strides address row %lld of %lld", (long long)last_row, (long long)c.T); return IWVI_ERR_ARG; }
+    FwElbo& E = p.a.h.e;
+    E.enabled = 1; E.K = elbo->K; E.K_total = elbo->K_total > 0 ? elbo->K_total : elbo->K; E.mode_vi = elbo->mode_vi;
+    E.B = elbo->B; E.stride_b = elbo->stride_b; E.stride_k = elbo->stride_k; E.scale = elbo->scale;
+    E.n_glob = elbo->n_glob;
+    for (int i = 0; i < elbo->n_glob; ++i) {
+        if (!elbo->kl_global || !elbo->kl_global[i]) { set_error("iwvi_dgp_forward: null global KL pointer %d", i); return IWVI_ERR_ARG; }
+        E.klg[i] = elbo->kl_global[i];
+        E.klg_n[i] = elbo->kl_global_counts ? elbo->kl_global_counts[i] : 1;
+        if (E.klg_n[i] <= 0 || E.klg_n[i] > IWVI_MAX_R) { set_error("iwvi_dgp_forward: bad global KL count %d", E.klg_n[i]); return IWVI_ERR_ARG; }
+        E.kl_total += E.klg_n[i];
+    }
+    E.ms = elbo->out_lse_ms; E.logp = elbo->out_logp; E.elbo = elbo->out_elbo; E.ws = elbo->ws;
+    E.adj_w = elbo->adj_w; E.adj_dmean = elbo->adj_dmean; E.adj_dvar = elbo->adj_dvar; E.adj_sums = elbo->adj_sums;
+    if (E.adj_w || E.adj_dmean || E.adj_dvar || E.adj_sums) {
+        if (!(E.adj_w && E.adj_dmean && E.adj_dvar && E.adj_sums)) { set_error("iwvi_dgp_forward: the adjoint heads adj_w / adj_dmean / adj_dvar / adj_sums come together"); return IWVI_ERR_ARG; }
+        if (E.mode_vi || !E.ws || E.stride_k != 1 || E.stride_b != E.K || E.K_total != E.K) {
+            set_error("iwvi_dgp_forward: the fused adjoint heads need the importance-weighted bound with contiguous samples, ws, and no sharded exchange");
+            return IWVI_ERR_UNSUPPORTED;
         }
-        E.ms = elbo->out_lse_ms; E.logp = elbo->out_logp; E.elbo = elbo->out_elbo; E.ws = elbo->ws;
-        E.adj_w = elbo->adj_w; E.adj_dmean = elbo->adj_dmean; E.adj_dvar = elbo->adj_dvar; E.adj_sums = elbo->adj_sums;
-        if (E.adj_w || E.adj_dmean || E.adj_dvar || E.adj_sums) {
-            if (!(E.adj_w && E.adj_dmean && E.adj_dvar && E.adj_sums)) { set_error("iwvi_dgp_forward: the adjoint heads adj_w / adj_dmean / adj_dvar / adj_sums come together"); return IWVI_ERR_ARG; }
-            if (E.mode_vi || !E.ws || E.stride_k != 1 || E.stride_b != E.K || E.K_total != E.K) {
-                set_error("iwvi_dgp_forward: the fused adjoint heads need the importance-weighted bound with contiguous samples, ws, and no sharded exchange");
-                return IWVI_ERR_UNSUPPORTED;
-            }
-        }
-        a.h.lw_init = elbo->lw_init; a.h.layer_base = elbo->noise_layer_base; a.h.x_per_sample = elbo->x_per_sample;
-        a.h.lik_var_dev = elbo->lik_variance_dev;
     }
-    {   // activation row stride: room for the widest layer input + 2 (x~), padded to a multiple of 4, and the widest output; odd
-        int wmax = Dx + 2, dcur = Dx;
-        for (int i = 0; i < n_layers; ++i) {
-            const FwLayer& L = a.L[i];
-            dcur = (L.type == IWVI_LAYER_GP) ? L.gp.P : dcur + L.lv.Lw;
-            if (dcur + 2 > wmax) wmax = dcur + 2;
-        }
-        a.h.xstr = round_up(wmax, 4) + 1;
-        if (a.h.xstr > XSTR_MAX) a.h.xstr = XSTR_MAX;
+    FwHead& h = p.a.h;
+    h.lw_init = elbo->lw_init; h.layer_base = elbo->noise_layer_base; h.x_per_sample = elbo->x_per_sample;
+    h.lik_var_dev = elbo->lik_variance_dev;
+    return IWVI_OK;
+}
+
+// activation row stride: room for the widest layer input + 2 (x~), padded to a multiple of 4, and the widest output; odd
+static int plan_xstr(FwPlan& p) {
+    FwArgs& a = p.a;
+    int wmax = a.h.Dx + 2, dcur = a.h.Dx;
+    for (int i = 0; i < a.h.n_layers; ++i) {
+        const FwLayer& L = a.L[i];
+        dcur = (L.type == IWVI_LAYER_GP) ? L.gp.P : dcur + L.lv.Lw;
+        if (dcur + 2 > wmax) wmax = dcur + 2;
     }
-    // chunk size: 16*NS samples per workgroup, NS no larger than what gives every CU a workgroup, then the
-    // largest that fits the LDS (with Z~ staged if that fits too)
+    a.h.xstr = round_up(wmax, 4) + 1;
+    if (a.h.xstr > XSTR_MAX) a.h.xstr = XSTR_MAX;
+    return IWVI_OK;
+}
+
+// chunk size: 16*NS samples per workgroup, NS no larger than what gives every CU a workgroup, then the
+// largest that fits the LDS (with Z~ and the solve stream staged if that fits, then Z~ alone, then neither)
+static int plan_fit(const FwCall& c, FwPlan& p) {
     const size_t LDS_MAX = 160 * 1024;
-    int ns = (int)((T + 16 * 256 - 1) / (16 * 256));
+    int ns = (int)((c.T + 16 * 256 - 1) / (16 * 256));
     if (ns > FW_MAXNS) ns = FW_MAXNS;
     { const int cap = dbg_opt("IWVI_FW_MAX_NS"); if (cap > 0 && ns > cap) ns = cap; }   // development: fewer samples per workgroup than would fit
     if (ns < 1) ns = 1;
-    if (pred && !(ns & 1)) --ns;                         // the predictive variants exist for 1, 3 and 5 sub-tiles per workgroup
+    if (c.pred && !(ns & 1)) --ns;                       // the predictive variants exist for 1, 3 and 5 sub-tiles per workgroup
     size_t lds_bytes = 0;
-    for (; ns >= 1; ns -= pred ? 2 : 1) {
-        lds_bytes = fw_plan_lds(a, 16 * ns, maxR, maxP, true, true);
-        if (lds_bytes <= LDS_MAX) break;
-        lds_bytes = fw_plan_lds(a, 16 * ns, maxR, maxP, true, false);
-        if (lds_bytes <= LDS_MAX) break;
-        lds_bytes = fw_plan_lds(a, 16 * ns, maxR, maxP, false, false);
+    for (; ns >= 1; ns -= c.pred ? 2 : 1) {              // (the accepted plan is the last call's: fw_plan_lds leaves its offsets and lists in `a`)
+        for (int drop = 0; drop < 3; ++drop) {
+            lds_bytes = fw_plan_lds(p.a, 16 * ns, p.maxR, p.maxP, drop < 2, drop < 1);
+            if (!lds_bytes) return IWVI_ERR_UNSUPPORTED;
+            if (lds_bytes <= LDS_MAX) break;
+        }
         if (lds_bytes <= LDS_MAX) break;
     }
     if (ns < 1) { set_error("iwvi_dgp_forward: the layer stack needs %zu B of LDS per 16 samples (> 160 KiB)", lds_bytes); return IWVI_ERR_UNSUPPORTED; }
-    for (int i = 0; i < n_layers; ++i) {                 // the scalar-path copy of what the layer loop reads (after the LDS plan)
+    p.v.ns = ns; p.lds_bytes = lds_bytes;
+    return IWVI_OK;
+}
+
+// the scalar-path copy of what the layer loop reads (after the LDS plan)
+static int plan_hot(FwPlan& p) {
+    FwArgs& a = p.a;
+    for (int i = 0; i < a.h.n_layers; ++i) {
         const FwLayer& L = a.L[i];
         FwHot& H = a.H[i];
         H = FwHot{};
@@ -3098,133 +3143,168 @@ static int dgp_forward_core(const iwvi_layer_desc* layers, int n_layers, const f
         H.flags = fl;
         if (fl & FWF_PRE_ENC) a.h.pre_enc_mask |= 1u << i;
     }
-    const long long chunks = (T + 16 * ns - 1) / (16 * ns);
+    return IWVI_OK;
+}
+
+// grid, diagnostics, and the packed arrival (fw_arrive_fast): it applies when every point's K samples sit in one chunk (the kernel's
+// local_lse), the launch finishes the ELBO itself, its arrivals fit the 9-bit count and the scratch holds a tagged slot per chunk for the
+// exact (overflow) path
+static int plan_grid(const FwCall& c, FwPlan& p) {
+    FwHead& h = p.a.h;
+    const int nsamp = 16 * p.v.ns;
+    const long long chunks = (c.T + nsamp - 1) / nsamp;
     if (chunks > 0x7fffffffLL) { set_error("iwvi_dgp_forward: T too large"); return IWVI_ERR_ARG; }
-    a.h.nchunks = (int)chunks;
-    a.h.stamps = (g_stamp_buf && chunks + IWVI_MAX_STACK <= g_stamp_wgs) ? g_stamp_buf : nullptr;
-    a.h.dbg_exit = g_dbg_exit;
-    fw_decide_fast(a, (unsigned)chunks, 16 * ns, T);
-    if (pred && pred->out_y) {                           // the sampling tail (FW_MODE_SAMPLE): one launch, nothing to merge
-        a.h.lik_var_dev = lik_variance_dev;
-        a.h.e.ms = pred->out_y;
-        a.h.e.logp = const_cast<float*>(pred->z_y);
-        if (f64_any) {
-            g_last_variant = ns | 1 << 9 | 1 << 12;
-            return ns == 1 ? launch_forward<1, false, true, FW_MODE_SAMPLE, true>(a, (unsigned)chunks, lds_bytes, stream)
-                 : ns == 3 ? launch_forward<3, false, true, FW_MODE_SAMPLE, true>(a, (unsigned)chunks, lds_bytes, stream)
-                           : launch_forward<5, false, true, FW_MODE_SAMPLE, true>(a, (unsigned)chunks, lds_bytes, stream);
-        }
-        bool bg = false;
-        for (int i = 0; i < n_layers; ++i) if (a.L[i].type == IWVI_LAYER_GP && a.L[i].gp.nbk > 8) bg = true;
-        g_last_variant = ns | (s16_all ? 1 << 8 : 0) | (bg ? 1 << 9 : 0);
-#define FW_SAMP(NS_) (s16_all ? (bg ? launch_forward<NS_, true, true, FW_MODE_SAMPLE>(a, (unsigned)chunks, lds_bytes, stream)      \
-                                    : launch_forward<NS_, true, false, FW_MODE_SAMPLE>(a, (unsigned)chunks, lds_bytes, stream))     \
-                              : (bg ? launch_forward<NS_, false, true, FW_MODE_SAMPLE>(a, (unsigned)chunks, lds_bytes, stream)     \
-                                    : launch_forward<NS_, false, false, FW_MODE_SAMPLE>(a, (unsigned)chunks, lds_bytes, stream)))
-        return ns == 1 ? FW_SAMP(1) : ns == 3 ? FW_SAMP(3) : FW_SAMP(5);
-#undef FW_SAMP
+    p.grid = (unsigned)chunks;
+    h.nchunks = (int)chunks;
+    h.stamps = (g_stamp_buf && chunks + IWVI_MAX_STACK <= g_stamp_wgs) ? g_stamp_buf : nullptr;
+    h.dbg_exit = g_dbg_exit;
+    const FwElbo& E = h.e;
+    const int64_t ws_len = (c.T + 15) / 16;
+    h.e.fast = (E.enabled && E.ws && E.elbo && !E.mode_vi && E.stride_k == 1 && E.stride_b == E.K && E.K > 0 && (nsamp % E.K) == 0 &&
+                h.rng_state && p.grid <= 511u && 2 * (int64_t)h.nchunks <= ws_len && E.kl_total <= 64 && !dbg_opt("IWVI_FW_SLOW_TAIL")) ? 1 : 0;
+    return IWVI_OK;
+}
+
+// what the tail of the launch reads: the sampling tail's output and noise, the predictive tail's partials, or the adjoint heads' condition
+static int plan_tail(const FwCall& c, FwPlan& p) {
+    FwHead& h = p.a.h;
+    if (c.pred) {
+        h.lik_var_dev = c.lik_variance_dev;
+        if (c.pred->mode == FW_MODE_SAMPLE) { h.e.ms = c.pred->out_y; h.e.logp = const_cast<float*>(c.pred->z_y); }   // one launch, nothing to merge
+        else h.e.ws = (double*)c.pred->ws;               // then the per-point merge of its partials (k_pred_lse_merge)
+        return IWVI_OK;
     }
-    if (pred) {                                          // the predictive tail (FW_MODE_PREDICT), then the per-point merge of its partials
-        a.h.lik_var_dev = lik_variance_dev;
-        a.h.e.ws = (double*)pred->ws;
-        int rc;
-        if (f64_any) {
-            g_last_variant = ns | 1 << 9 | 1 << 12;
-            rc = ns == 1 ? launch_forward<1, false, true, FW_MODE_PREDICT, true>(a, (unsigned)chunks, lds_bytes, stream)
-               : ns == 3 ? launch_forward<3, false, true, FW_MODE_PREDICT, true>(a, (unsigned)chunks, lds_bytes, stream)
-                         : launch_forward<5, false, true, FW_MODE_PREDICT, true>(a, (unsigned)chunks, lds_bytes, stream);
-        } else {
-            bool bg = false;
-            for (int i = 0; i < n_layers; ++i) if (a.L[i].type == IWVI_LAYER_GP && a.L[i].gp.nbk > 8) bg = true;
-            g_last_variant = ns | (s16_all ? 1 << 8 : 0) | (bg ? 1 << 9 : 0);
-#define FW_PRED(NS_) (s16_all ? (bg ? launch_forward<NS_, true, true, FW_MODE_PREDICT>(a, (unsigned)chunks, lds_bytes, stream)      \
-                                    : launch_forward<NS_, true, false, FW_MODE_PREDICT>(a, (unsigned)chunks, lds_bytes, stream))     \
-                              : (bg ? launch_forward<NS_, false, true, FW_MODE_PREDICT>(a, (unsigned)chunks, lds_bytes, stream)     \
-                                    : launch_forward<NS_, false, false, FW_MODE_PREDICT>(a, (unsigned)chunks, lds_bytes, stream)))
-            rc = ns == 1 ? FW_PRED(1) : ns == 3 ? FW_PRED(3) : FW_PRED(5);
-#undef FW_PRED
-        }
-        if (rc != IWVI_OK) return rc;
-        hipLaunchKernelGGL(k_pred_lse_merge, dim3((unsigned)((pred->N + 255) / 256)), dim3(256), 0, stream,
-                           (const float2*)pred->ws, (long long)pred->N, (long long)pred->S, 16 * ns, pred->out_logp);
-        return check_launch("k_pred_lse_merge");
-    }
-    if (a.h.e.adj_w) {                                   // every point's K samples inside one chunk, two doubles of ws per chunk; the sums travel through ws
-        if ((16 * ns) % a.h.e.K != 0 || 2 * chunks > (T + 15) / 16) {
-            set_error("iwvi_dgp_forward: the fused adjoint heads need K (%d) to divide the chunk of %d samples", a.h.e.K, 16 * ns);
+    if (h.e.adj_w) {                                     // every point's K samples inside one chunk, two doubles of ws per chunk; the sums travel through ws
+        const int nsamp = 16 * p.v.ns;
+        if (nsamp % h.e.K != 0 || 2 * (long long)p.grid > (c.T + 15) / 16) {
+            set_error("iwvi_dgp_forward: the fused adjoint heads need K (%d) to divide the chunk of %d samples", h.e.K, nsamp);
             return IWVI_ERR_UNSUPPORTED;
         }
-        a.h.e.fast = 0;
+        h.e.fast = 0;
     }
-    bool big = false;                                    // a layer with M > 128: the variants that carry the generic / super-block solves
-    for (int i = 0; i < n_layers; ++i) if (a.L[i].type == IWVI_LAYER_GP && a.L[i].gp.nbk > 8) big = true;
-#define FW_LAUNCH(NS_) (s16_all ? (big ? launch_forward<NS_, true, true>(a, (unsigned)chunks, lds_bytes, stream)      \
-                                      : launch_forward<NS_, true, false>(a, (unsigned)chunks, lds_bytes, stream))     \
-                                : (big ? launch_forward<NS_, false, true>(a, (unsigned)chunks, lds_bytes, stream)     \
-                                      : launch_forward<NS_, false, false>(a, (unsigned)chunks, lds_bytes, stream)))
-    bool fp32_shp = false;                               // s16_all is off only because a layer asked for the fp32-MFMA stage 2
-    for (int i = 0; i < n_layers; ++i) if (layers[i].type == IWVI_LAYER_GP && (layers[i].flags & IWVI_LAYER_F32_STAGE2)) fp32_shp = true;
-    {   // the headline stack at the headline chunk size: the variants with its shapes and sources compiled in (k_dgp_forward: SHP / LEAN)
-        // EVERY assumption the SHP / LEAN code compiles in is a condition here (the kernel has no run-time guard of its own,
-        // and tests/test_gpu_lean_variant.py lists a shape per condition that must NOT take these variants):
-        //   nvalid = NSAMP, grid * 80 == T  <- T % 80 == 0 (whole chunks)        nbk = 8                  <- M == 128
-        //   nsteps = 3 / nx_nsteps = 3      <- D + 2 <= 12 of every GP layer      mean-function loop u < 3 <- D <= 10 (the same)
-        //   npb = 1 (one block of outputs)  <- P <= 16                            rbf, operands staged, encoders precomputed, device noise
-        bool shp = ns == 5 && (s16_all || fp32_shp) && !f64_any && !big && !a.h.noise_any_src && !a.h.lw_init && !a.h.x_per_sample && !g_dbg_exit && T % (16 * 5) == 0
-                   && chunks * (16 * 5) == T;
-        for (int i = 0; i < n_layers && shp; ++i) {
-            const FwLayer& L = a.L[i];
-            if (L.type == IWVI_LAYER_GP) {
-                const FwGp& G = L.gp;                              // M = 128 (8 blocks), D <= 10, P <= 16, operands staged in LDS
-                if (G.kern_type != IWVI_KERN_RBF || G.M != 128 || G.nbk != 8 || G.nsteps != 3 || L.D > 10 || G.P > 16 || G.ls_off < 0 || G.zt_off < 0) shp = false;
-                if (L.nx_gp && L.nx_nsteps != 3) shp = false;
-            }
-            else if (!L.lv.enc_out) shp = false;
+    return IWVI_OK;
+}
+
+static int choose_variant(const FwCall& c, FwPlan& p) {
+    const FwArgs& a = p.a;
+    FwVariant& v = p.v;
+    v.s16 = p.s16_all; v.f64 = p.f64_any; v.big = p.big || p.f64_any;   // (the F64 variants are built with BIG)
+    v.mode = c.pred ? c.pred->mode : 0;
+    if (c.pred) return IWVI_OK;
+    // the headline stack at the headline chunk size: the variants with its shapes and sources compiled in (k_dgp_forward: SHP / LEAN)
+    // EVERY assumption the SHP / LEAN code compiles in is a condition here (the kernel has no run-time guard of its own,
+    // and tests/test_gpu_lean_variant.py lists a shape per condition that must NOT take these variants):
+    //   nvalid = NSAMP, grid * 80 == T  <- T % 80 == 0 (whole chunks)        nbk = 8                  <- M == 128
+    //   nsteps = 3 / nx_nsteps = 3      <- D + 2 <= 12 of every GP layer      mean-function loop u < 3 <- D <= 10 (the same)
+    //   npb = 1 (one block of outputs)  <- P <= 16                            rbf, operands staged, encoders precomputed, device noise
+    // (s16_all || f32_req: s16_all is off only because a layer asked for the fp32-MFMA stage 2 -- the strict-fp32 route with the same shapes compiled in)
+    bool shp = v.ns == 5 && (p.s16_all || p.f32_req) && !p.f64_any && !p.big && !a.h.noise_any_src && !a.h.lw_init && !a.h.x_per_sample && !g_dbg_exit && c.T % (16 * 5) == 0
+               && (long long)p.grid * (16 * 5) == c.T;
+    for (int i = 0; i < a.h.n_layers && shp; ++i) {
+        const FwLayer& L = a.L[i];
+        if (L.type == IWVI_LAYER_GP) {
+            const FwGp& G = L.gp;                              // M = 128 (8 blocks), D <= 10, P <= 16, operands staged in LDS
+            if (G.kern_type != IWVI_KERN_RBF || G.M != 128 || G.nbk != 8 || G.nsteps != 3 || L.D > 10 || G.P > 16 || G.ls_off < 0 || G.zt_off < 0) shp = false;
+            if (L.nx_gp && L.nx_nsteps != 3) shp = false;
         }
-        // mode 1: the bound's own evaluation (no per-layer output, the packed arrival; its tail: one half-wave per data point, lane = sample,
-        // so a chunk must hold whole data points: K | 80 with K <= 16 samples per half-wave ... or K = 20 (4 points per chunk) -- see the tail)
-        bool lean = shp && a.h.e.fast && a.h.out_logw && a.h.e.K >= 5 && a.h.e.K <= 32 && (16 * 5) % a.h.e.K == 0;
-        for (int i = 0; i < n_layers && lean; ++i) if (a.H[i].flags & FWF_ANY_OUT) lean = false;
-        if (shp && !dbg_opt("IWVI_FW_NO_LEAN")) {
-            if (!s16_all) {                              // the strict-fp32 route (IWVI_LAYER_F32_STAGE2 on a layer) with the same shapes compiled in
-                if (lean) { g_last_variant = 5 | 1 << 10; return launch_forward<5, false, false, 1>(a, (unsigned)chunks, lds_bytes, stream); }
-                g_last_variant = 5 | 1 << 11;
-                return launch_forward<5, false, false, 2>(a, (unsigned)chunks, lds_bytes, stream);
-            }
-            if (lean) { g_last_variant = 5 | 1 << 8 | 1 << 10; return launch_forward<5, true, false, 1>(a, (unsigned)chunks, lds_bytes, stream); }
-            // mode 2: the same stack with outputs and the general tail (the forward of a value + gradient evaluation, predictions, read-backs)
-            g_last_variant = 5 | 1 << 8 | 1 << 11;
-            return launch_forward<5, true, false, 2>(a, (unsigned)chunks, lds_bytes, stream);
-        }
+        else if (!L.lv.enc_out) shp = false;
     }
-    if (f64_any) {
-        g_last_variant = ns | 1 << 9 | 1 << 12;
-        switch (ns) {
-            case 1: return launch_forward<1, false, true, 0, true>(a, (unsigned)chunks, lds_bytes, stream);
-            case 2: return launch_forward<2, false, true, 0, true>(a, (unsigned)chunks, lds_bytes, stream);
-            case 3: return launch_forward<3, false, true, 0, true>(a, (unsigned)chunks, lds_bytes, stream);
-            case 4: return launch_forward<4, false, true, 0, true>(a, (unsigned)chunks, lds_bytes, stream);
-            default: return launch_forward<5, false, true, 0, true>(a, (unsigned)chunks, lds_bytes, stream);
-        }
-    }
-    g_last_variant = ns | (s16_all ? 1 << 8 : 0) | (big ? 1 << 9 : 0);
-    switch (ns) {
-#ifndef IWVI_DEV_ONLY5   /* development builds: only the 80-sample variants (make DEV5=1) */
-        case 1: return FW_LAUNCH(1);
-        case 2: return FW_LAUNCH(2);
-        case 3: return FW_LAUNCH(3);
-        case 4: return FW_LAUNCH(4);
+    // mode 1: the bound's own evaluation (no per-layer output, the packed arrival; its tail: one half-wave per data point, lane = sample,
+    // so a chunk must hold whole data points: K | 80 with K <= 16 samples per half-wave ... or K = 20 (4 points per chunk) -- see the tail)
+    bool lean = shp && a.h.e.fast && a.h.out_logw && a.h.e.K >= 5 && a.h.e.K <= 32 && (16 * 5) % a.h.e.K == 0;
+    for (int i = 0; i < a.h.n_layers && lean; ++i) if (a.H[i].flags & FWF_ANY_OUT) lean = false;
+    // mode 2: the same stack with outputs and the general tail (the forward of a value + gradient evaluation, predictions, read-backs)
+    if (shp && !dbg_opt("IWVI_FW_NO_LEAN")) v.mode = lean ? 1 : 2;
+    return IWVI_OK;
+}
+
+static int fw_plan(const FwCall& c, FwPlan& p) {
+    int rc;
+    if ((rc = plan_check_call(c, p)) != IWVI_OK || (rc = plan_layers(c, p)) != IWVI_OK || (rc = plan_elbo(c, p)) != IWVI_OK ||
+        (rc = plan_xstr(p)) != IWVI_OK || (rc = plan_fit(c, p)) != IWVI_OK || (rc = plan_hot(p)) != IWVI_OK ||
+        (rc = plan_grid(c, p)) != IWVI_OK || (rc = plan_tail(c, p)) != IWVI_OK) return rc;
+    return choose_variant(c, p);
+}
+
+// the diagnostic word of iwvi_debug_last_forward_variant: ns | S16 << 8 | BIG << 9 | LEAN << 10 | SHP << 11 | F64 << 12 (the two predictive
+// tails have no bit of their own)
+static int variant_code(const FwVariant& v) {
+    return v.ns | (v.s16 ? 1 << 8 : 0) | (v.big ? 1 << 9 : 0) | (v.mode == 1 ? 1 << 10 : 0) | (v.mode == 2 ? 1 << 11 : 0) | (v.f64 ? 1 << 12 : 0);
+}
+
+// every k_dgp_forward instantiation the library holds
+struct FwRow { FwVariant v; int (*launch)(const FwArgs&, unsigned, size_t, hipStream_t); };
+#define FW_ROW(NS_, S16_, BIG_, MODE_, F64_) {{NS_, S16_, BIG_, F64_, MODE_}, launch_forward<NS_, S16_, BIG_, MODE_, F64_>}
+#define FW_ROWS(NS_, MODE_) FW_ROW(NS_, true, true, MODE_, false), FW_ROW(NS_, true, false, MODE_, false), \
+                            FW_ROW(NS_, false, true, MODE_, false), FW_ROW(NS_, false, false, MODE_, false)
+static const FwRow fw_variants[] = {
+    FW_ROW(1, false, true, FW_MODE_SAMPLE, true), FW_ROW(3, false, true, FW_MODE_SAMPLE, true), FW_ROW(5, false, true, FW_MODE_SAMPLE, true),
+    FW_ROWS(1, FW_MODE_SAMPLE), FW_ROWS(3, FW_MODE_SAMPLE), FW_ROWS(5, FW_MODE_SAMPLE),
+    FW_ROW(1, false, true, FW_MODE_PREDICT, true), FW_ROW(3, false, true, FW_MODE_PREDICT, true), FW_ROW(5, false, true, FW_MODE_PREDICT, true),
+    FW_ROWS(1, FW_MODE_PREDICT), FW_ROWS(3, FW_MODE_PREDICT), FW_ROWS(5, FW_MODE_PREDICT),
+    FW_ROW(5, false, false, 1, false), FW_ROW(5, false, false, 2, false), FW_ROW(5, true, false, 1, false), FW_ROW(5, true, false, 2, false),
+    FW_ROW(1, false, true, 0, true), FW_ROW(2, false, true, 0, true), FW_ROW(3, false, true, 0, true), FW_ROW(4, false, true, 0, true),
+    FW_ROW(5, false, true, 0, true),
+#ifndef IWVI_DEV_ONLY5   /* development builds: only the 80-sample variants (make DEV5=1); launch_variant runs these calls on the ns = 5 row */
+    FW_ROWS(1, 0), FW_ROWS(2, 0), FW_ROWS(3, 0), FW_ROWS(4, 0),
 #endif
-        default: return FW_LAUNCH(5);
-    }
-#undef FW_LAUNCH
+    FW_ROWS(5, 0),
+};
+#undef FW_ROWS
+#undef FW_ROW
+
+static int launch_variant(const FwPlan& p, hipStream_t stream) {
+    const FwVariant& v = p.v;
+    auto row = [&](int ns) -> const FwRow* {
+        for (const FwRow& r : fw_variants) if (r.v.ns == ns && r.v.s16 == v.s16 && r.v.big == v.big && r.v.f64 == v.f64 && r.v.mode == v.mode) return &r;
+        return nullptr;
+    };
+    const FwRow* r = row(v.ns);
+#ifdef IWVI_DEV_ONLY5
+    if (!r) r = row(5);
+#endif
+    if (!r) { set_error("iwvi_dgp_forward: no k_dgp_forward variant 0x%x (mode %d)", variant_code(v), v.mode); return IWVI_ERR_UNSUPPORTED; }
+    g_last_variant = variant_code(v);
+    return r->launch(p.a, p.grid, p.lds_bytes, stream);
+}
+
+static int dgp_forward_core(const FwCall& c, hipStream_t stream) {
+    if (c.T <= 0) return IWVI_OK;                       // empty batch: nothing to do
+    FwPlan p{};
+    int rc = fw_plan(c, p);
+    if (rc != IWVI_OK || (rc = launch_variant(p, stream)) != IWVI_OK || p.v.mode != FW_MODE_PREDICT) return rc;
+    const FwPredict& q = *c.pred;
+    hipLaunchKernelGGL(k_pred_lse_merge, dim3((unsigned)((q.N + 255) / 256)), dim3(256), 0, stream,
+                       (const float2*)q.ws, (long long)q.N, (long long)q.S, 16 * p.v.ns, q.out_logp);
+    return check_launch("k_pred_lse_merge");
 }
 
 int dgp_forward_impl(const iwvi_layer_desc* layers, int n_layers, const float* X, int Dx, const float* XY, int XYdim,
                           const float* Y, int Dy, int64_t T, int64_t row_div, int64_t row_mod, float lik_variance,
                           uint64_t seed, uint64_t* rng_state, float* out_logw, const iwvi_elbo_desc* elbo, hipStream_t stream) {
-    return dgp_forward_core(layers, n_layers, X, Dx, XY, XYdim, Y, Dy, T, row_div, row_mod, lik_variance, seed, rng_state, out_logw, elbo,
-                            stream, nullptr, nullptr);
+    return dgp_forward_core(FwCall{layers, n_layers, X, Dx, XY, XYdim, Y, Dy, T, row_div, row_mod, lik_variance, seed, rng_state, out_logw, elbo,
+                                   nullptr, nullptr}, stream);
+}
+
+// The two predictive entries' own checks (`who`: the entry's name), then their call on the core: T = N * S rows, S consecutive rows share
+// a data point.  c.lik_variance is 1 where the variance is a device scalar.  N == 0 leaves T == 0: the core returns at once.
+static int fw_predict_call(const char* who, FwCall& c) {
+    const FwPredict& q = *c.pred;
+    const bool sampling = q.mode == FW_MODE_SAMPLE;
+    const int64_t N = q.N, S = q.S;
+    if (N < 0 || S < 1) { set_error("%s: N=%lld, S=%lld (N >= 0, S >= 1)", who, (long long)N, (long long)S); return IWVI_ERR_ARG; }
+    if (N == 0) return IWVI_OK;
+    if (N > 0x7fffffffLL || S > 0x7fffffffLL || N * S > 0x7fffffffLL - 4096) { set_error("%s: N x S = %lld x %lld rows (< 2^31)", who, (long long)N, (long long)S); return IWVI_ERR_ARG; }
+    if (sampling ? !q.out_y : (!c.Y || !q.out_logp || !q.ws)) { set_error("%s: null %s", who, sampling ? "out_y" : "Y / out_logp / ws"); return IWVI_ERR_ARG; }
+    if (c.Dy <= 0 || c.Dy > IWVI_MAX_P) { set_error("%s: Dy=%d out of range (1..%d)", who, c.Dy, IWVI_MAX_P); return IWVI_ERR_ARG; }
+    if (!(c.lik_variance > 0.f)) { set_error("%s: the likelihood variance must be positive", who); return IWVI_ERR_ARG; }
+    if (sampling && !q.z_y && !c.rng_state) { set_error("%s: without z_y the tail draws its own noise but rng_state is NULL", who); return IWVI_ERR_ARG; }
+    for (int i = 0; i < c.n_layers && c.layers; ++i)
+        if (c.layers[i].type == IWVI_LAYER_LV && (c.layers[i].enc_W || c.layers[i].enc_out)) {
+            set_error("%s: latent-variable layer %d has an encoder (prediction runs them in prior mode)", who, i); return IWVI_ERR_ARG;
+        }
+    c.T = N * S; c.row_div = S; c.row_mod = N;
+    return IWVI_OK;
 }
 
 }  // namespace iwvi
@@ -3247,38 +3327,35 @@ extern "C" size_t iwvi_dgp_predict_density_ws_bytes(int64_t N, int64_t S) {
 extern "C" int iwvi_dgp_predict_density(const iwvi_layer_desc* layers, int n_layers, const float* X, int Dx, const float* Y, int Dy,
                                         int64_t N, int64_t S, float lik_variance, const float* lik_variance_dev, uint64_t seed,
                                         uint64_t* rng_state, float* out_logp, void* ws, void* stream) {
-    if (N < 0 || S < 1) { set_error("iwvi_dgp_predict_density: N=%lld, S=%lld (N >= 0, S >= 1)", (long long)N, (long long)S); return IWVI_ERR_ARG; }
-    if (N == 0) return IWVI_OK;
-    if (N > 0x7fffffffLL || S > 0x7fffffffLL || N * S > 0x7fffffffLL - 4096) { set_error("iwvi_dgp_predict_density: N x S = %lld x %lld rows (< 2^31)", (long long)N, (long long)S); return IWVI_ERR_ARG; }
-    if (!Y || !out_logp || !ws) { set_error("iwvi_dgp_predict_density: null Y / out_logp / ws"); return IWVI_ERR_ARG; }
-    if (Dy <= 0 || Dy > IWVI_MAX_P) { set_error("iwvi_dgp_predict_density: Dy=%d out of range (1..%d)", Dy, IWVI_MAX_P); return IWVI_ERR_ARG; }
-    if (!lik_variance_dev && !(lik_variance > 0.f)) { set_error("iwvi_dgp_predict_density: the likelihood variance must be positive"); return IWVI_ERR_ARG; }
-    for (int i = 0; i < n_layers && layers; ++i)
-        if (layers[i].type == IWVI_LAYER_LV && (layers[i].enc_W || layers[i].enc_out)) {
-            set_error("iwvi_dgp_predict_density: latent-variable layer %d has an encoder (prediction runs them in prior mode)", i); return IWVI_ERR_ARG;
-        }
-    const FwPredict p{N, S, out_logp, ws, nullptr, nullptr};
-    return dgp_forward_core(layers, n_layers, X, Dx, nullptr, 0, Y, Dy, N * S, S, N, lik_variance_dev ? 1.f : lik_variance, seed, rng_state,
-                            nullptr, nullptr, (hipStream_t)stream, &p, lik_variance_dev);
+    const FwPredict q{FW_MODE_PREDICT, N, S, out_logp, ws, nullptr, nullptr};
+    FwCall c{layers, n_layers, X, Dx, nullptr, 0, Y, Dy, 0, 0, 0, lik_variance_dev ? 1.f : lik_variance, seed, rng_state, nullptr, nullptr, &q, lik_variance_dev};
+    const int rc = fw_predict_call("iwvi_dgp_predict_density", c);
+    return rc != IWVI_OK ? rc : dgp_forward_core(c, (hipStream_t)stream);
 }
 
 extern "C" int iwvi_dgp_predict_samples(const iwvi_layer_desc* layers, int n_layers, const float* X, int Dx, int Dy, int64_t N, int64_t S,
                                         float lik_variance, const float* lik_variance_dev, const float* z_y, uint64_t seed,
                                         uint64_t* rng_state, float* out_y, void* stream) {
-    if (N < 0 || S < 1) { set_error("iwvi_dgp_predict_samples: N=%lld, S=%lld (N >= 0, S >= 1)", (long long)N, (long long)S); return IWVI_ERR_ARG; }
-    if (N == 0) return IWVI_OK;
-    if (N > 0x7fffffffLL || S > 0x7fffffffLL || N * S > 0x7fffffffLL - 4096) { set_error("iwvi_dgp_predict_samples: N x S = %lld x %lld rows (< 2^31)", (long long)N, (long long)S); return IWVI_ERR_ARG; }
-    if (!out_y) { set_error("iwvi_dgp_predict_samples: null out_y"); return IWVI_ERR_ARG; }
-    if (Dy <= 0 || Dy > IWVI_MAX_P) { set_error("iwvi_dgp_predict_samples: Dy=%d out of range (1..%d)", Dy, IWVI_MAX_P); return IWVI_ERR_ARG; }
-    if (!lik_variance_dev && !(lik_variance > 0.f)) { set_error("iwvi_dgp_predict_samples: the likelihood variance must be positive"); return IWVI_ERR_ARG; }
-    if (!z_y && !rng_state) { set_error("iwvi_dgp_predict_samples: without z_y the tail draws its own noise but rng_state is NULL"); return IWVI_ERR_ARG; }
-    for (int i = 0; i < n_layers && layers; ++i)
-        if (layers[i].type == IWVI_LAYER_LV && (layers[i].enc_W || layers[i].enc_out)) {
-            set_error("iwvi_dgp_predict_samples: latent-variable layer %d has an encoder (prediction runs them in prior mode)", i); return IWVI_ERR_ARG;
-        }
-    const FwPredict p{N, S, nullptr, nullptr, out_y, z_y};
-    return dgp_forward_core(layers, n_layers, X, Dx, nullptr, 0, nullptr, Dy, N * S, S, N, lik_variance_dev ? 1.f : lik_variance, seed, rng_state,
-                            nullptr, nullptr, (hipStream_t)stream, &p, lik_variance_dev);
+    const FwPredict q{FW_MODE_SAMPLE, N, S, nullptr, nullptr, out_y, z_y};
+    FwCall c{layers, n_layers, X, Dx, nullptr, 0, nullptr, Dy, 0, 0, 0, lik_variance_dev ? 1.f : lik_variance, seed, rng_state, nullptr, nullptr, &q, lik_variance_dev};
+    const int rc = fw_predict_call("iwvi_dgp_predict_samples", c);
+    return rc != IWVI_OK ? rc : dgp_forward_core(c, (hipStream_t)stream);
+}
+
+/* diagnostic (include/iwvi_hip.h): the plan of a forward call without the call -- no HIP function, no data pointer dereferenced */
+extern "C" int iwvi_debug_forward_plan(const iwvi_layer_desc* layers, int n_layers, const float* X, int Dx, const float* XY, int XYdim,
+                                       const float* Y, int Dy, int64_t T, int64_t row_div, int64_t row_mod, float lik_variance, uint64_t seed,
+                                       uint64_t* rng_state, float* out_logw, const iwvi_elbo_desc* elbo, void* stream, int tail, int64_t* out_host) {
+    if (!out_host || tail < IWVI_FW_TAIL_BOUND || tail > IWVI_FW_TAIL_SAMPLES) { set_error("iwvi_debug_forward_plan: null out_host or unknown tail %d", tail); return IWVI_ERR_ARG; }
+    const bool sampling = tail == IWVI_FW_TAIL_SAMPLES;
+    const FwPredict q{sampling ? FW_MODE_SAMPLE : FW_MODE_PREDICT, row_mod, row_div, out_logw, out_logw, out_logw, XY};
+    FwCall c{layers, n_layers, X, Dx, XY, XYdim, Y, Dy, T, row_div, row_mod, lik_variance, seed, rng_state, out_logw, elbo, nullptr, nullptr};
+    if (tail != IWVI_FW_TAIL_BOUND) c = FwCall{layers, n_layers, X, Dx, nullptr, 0, sampling ? nullptr : Y, Dy, 0, 0, 0, lik_variance, seed, rng_state, nullptr, nullptr, &q, nullptr};
+    FwPlan p{};
+    int rc = c.pred ? fw_predict_call(sampling ? "iwvi_dgp_predict_samples" : "iwvi_dgp_predict_density", c) : IWVI_OK;
+    if (rc == IWVI_OK && c.T > 0) rc = fw_plan(c, p);    // (an empty call: OK and zeros, as the entries return at once)
+    if (rc == IWVI_OK) { out_host[0] = variant_code(p.v); out_host[1] = p.grid; out_host[2] = (int64_t)p.lds_bytes; }
+    return rc;
 }
 
 /* diagnostic (not part of the drop-in surface): register a device buffer of 128 * max_workgroups 64-bit words;
@@ -3291,3 +3368,4 @@ extern "C" void iwvi_debug_set_stamps(void* buf, int64_t max_workgroups) {
     iwvi::g_stamp_buf = (unsigned long long*)buf;
     iwvi::g_stamp_wgs = buf ? max_workgroups : 0;
 }
+

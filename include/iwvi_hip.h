@@ -906,6 +906,19 @@ int iwvi_debug_set_option(const char* name, int value);
  * large-M (M > 128) build, bits 10-11 LEAN mode (0 general, 1 bound-only, 2 with per-layer outputs), bit 12 a layer ran the float64
  * stage-1 route.  0 before the first launch. */
 int iwvi_debug_last_forward_variant(void);
+/* The plan of a fused-forward call without the call: the arguments of iwvi_dgp_forward (stream is not read) go through every check and
+ * decision of the host driver, and on success out_host[0..2] receive the word iwvi_debug_last_forward_variant() would report after the
+ * launch, the grid (workgroups) and the dynamic LDS bytes.  A refusal returns the status and error text of the entry it stands for.
+ * No HIP function is called and no data pointer is dereferenced (only the descriptors and their encoder tables are read), so it runs on
+ * a host without a device; the pointers only need to be null or not as in the real call.  tail selects the entry: the bound
+ * (iwvi_dgp_forward), or one of the predictive entries with their own checks -- then N = row_mod, S = row_div, T is not read, the
+ * variance is lik_variance, out_logw stands for out_logp and ws (density) or out_y (samples) and XY for z_y (samples). */
+#define IWVI_FW_TAIL_BOUND 0
+#define IWVI_FW_TAIL_DENSITY 1
+#define IWVI_FW_TAIL_SAMPLES 2
+int iwvi_debug_forward_plan(const iwvi_layer_desc* layers, int n_layers, const float* X, int Dx, const float* XY, int XYdim,
+                            const float* Y, int Dy, int64_t T, int64_t row_div, int64_t row_mod, float lik_variance, uint64_t seed,
+                            uint64_t* rng_state, float* out_logw, const iwvi_elbo_desc* elbo, void* stream, int tail, int64_t* out_host);
 /* In-kernel time stamps of the fused forward / of the precompute launch (128 64-bit words per workgroup; NULL switches them off) and an
  * early exit of the fused forward after phase N -- timing scripts only (scripts/stamp_*.py, bench.py's gemm_phase_mfma_util). */
 /* ABI 18: the route of every GP layer adjoint (iwvi_gp_layer_backward) since the previous call of this function, in call order (the latest

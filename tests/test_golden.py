@@ -13,8 +13,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 from make_golden import CASES, arrays_to_spec, oracle_outputs   # noqa: E402
 
-# (grad_*: the gradient oracle's targets; bw_*: recorded answers of the adjoint's sizing entries, tests/test_bw_sizing_host.py)
-FIXTURES = sorted(p for p in glob.glob(os.path.join(HERE, "golden", "*.npz")) if not os.path.basename(p).startswith(("grad_", "bw_")))
+# (grad_*: the gradient oracle's targets; bw_* / fw_plan: recorded answers of the adjoint's sizing entries and of the forward's host plan,
+#  tests/test_bw_sizing_host.py / tests/test_fw_plan_host.py)
+FIXTURES = sorted(p for p in glob.glob(os.path.join(HERE, "golden", "*.npz")) if not os.path.basename(p).startswith(("grad_", "bw_", "fw_plan")))
 
 
 def load(path):

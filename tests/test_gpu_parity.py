@@ -447,7 +447,7 @@ def _golden_paths():
     import glob
     import os
     return sorted(p for p in glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "*.npz"))
-                  if not os.path.basename(p).startswith(("grad_", "bw_")))      # grad_*: backward-pass targets (row F1), bw_*: the adjoint's sizing answers -- not forward cases
+                  if not os.path.basename(p).startswith(("grad_", "bw_", "fw_plan")))      # grad_*: backward-pass targets (row F1), bw_* / fw_plan: recorded host answers -- not forward cases
 
 
 @pytest.mark.parametrize("path", _golden_paths(), ids=lambda p: p.split("/")[-1][:-4])
