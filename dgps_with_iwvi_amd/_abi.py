@@ -289,10 +289,13 @@ PROTOTYPES = {
                                         c_void_p, ctypes.POINTER(CvaeGrads), c_void_p, c_void_p]),
     "iwvi_cvae_predict_samples": (c_int, [ctypes.POINTER(CvaeDesc), c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, ctypes.c_uint64,
                                           c_void_p, c_void_p, c_void_p]),
+    "iwvi_kmeans_ws_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "iwvi_kmeans": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                            c_void_p, c_void_p]),
 }
 
 DEBUG_OPTIONS = ("IWVI_BW_FUSED", "IWVI_CHAIN_EXIT", "IWVI_FW_SLOW_TAIL", "IWVI_FW_MAX_NS", "IWVI_NATGRAD_UNFUSED", "IWVI_NG_ONE_WG", "IWVI_NG_STOP", "IWVI_DEBUG_STOP", "IWVI_PRE_STAMP_P",
-                 "IWVI_FW_NO_LEAN", "IWVI_PRE_SB_INLINE", "IWVI_BW_P5_F32")
+                 "IWVI_FW_NO_LEAN", "IWVI_PRE_SB_INLINE", "IWVI_BW_P5_F32", "IWVI_KM_MAX_WG")
 
 
 def set_debug_option(name, value):

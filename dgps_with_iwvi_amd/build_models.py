@@ -38,12 +38,19 @@ def parse_configuration(configuration):
     return out
 
 
-def build_layers(configuration, X, M, rng=None):
-    """The reference's layer stack (everything but the model object): list of layers, on the CPU."""
+def build_layers(configuration, X, M, rng=None, kmeans="host"):
+    """The reference's layer stack (everything but the model object): list of layers, on the CPU.  ``kmeans``: where the first layer's
+    inducing inputs are clustered when N > M -- ``"host"``: SciPy's ``kmeans2`` (the default); ``"device"``: ``kmeans.kmeans2`` on X
+    rounded to float32 (what the model holds anyway), the same draw from NumPy's global stream for the start, the same loop."""
+    if kmeans not in ("host", "device"):
+        raise ValueError("kmeans=%r: 'host' or 'device'" % (kmeans,))
     rng = np.random if rng is None else rng
     X = np.asarray(X, dtype=np.float64)
     N, D = X.shape
-    if N > M:
+    if N > M and kmeans == "device":
+        from .kmeans import kmeans2 as device_kmeans2
+        Z = device_kmeans2(X, M, minit="points")[0].cpu().numpy().astype(np.float64)
+    elif N > M:
         Z = kmeans2(X, M, minit="points")[0]
     else:
         Z = np.concatenate([X.copy(), rng.randn(M - N, D)], 0)
@@ -79,7 +86,7 @@ def build_model(ARGS, X, Y, apply_name=True, device=None):
         raise NotImplementedError("mode %r: the VI / IWAE models (with their NatGrad + Adam train_op) are built here; an SGHMC model "
                                   "(with its sampler + Adam train_op) by build_sghmc_model; the CVAE baseline (with its Adam train_op) "
                                   "by build_cvae_model" % (ARGS.mode,))
-    layers = build_layers(ARGS.configuration, X, ARGS.M)
+    layers = build_layers(ARGS.configuration, X, ARGS.M, kmeans=getattr(ARGS, "kmeans", "host"))
     lik = Gaussian(ARGS.likelihood_variance)
     name = "Model" if apply_name else None
     if ARGS.mode == "VI":
@@ -105,7 +112,7 @@ def build_sghmc_model(ARGS, X, Y, apply_name=True, device=None):
     '', 'G5' and 'G5_G5' this way)."""
     if any(kind == "L" for kind, _ in parse_configuration(ARGS.configuration)):
         raise NotImplementedError("SGHMC: configurations with a latent-variable layer are not covered (%r)" % (ARGS.configuration,))
-    layers = build_layers(ARGS.configuration, X, ARGS.M)
+    layers = build_layers(ARGS.configuration, X, ARGS.M, kmeans=getattr(ARGS, "kmeans", "host"))
     for layer in layers:
         layer.q_sqrt = None                                          # :253-257; q_mu belongs to the sampler
     model = DGP_VI(X, Y, layers, Gaussian(ARGS.likelihood_variance), minibatch_size=ARGS.minibatch_size,

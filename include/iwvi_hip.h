@@ -651,6 +651,30 @@ int iwvi_kde_density_grid(const float* samples, int64_t sample_stride, int64_t p
                           const float* levels, int64_t level_point_stride, int G, double bandwidth,
                           float* out_logdens, float* out_mean_std, float* out_bandwidth, void* stream);
 
+/* Lloyd's k-means with the semantics of scipy.cluster.vq.kmeans2's loop (additive extension of ABI 19; csrc/kmeans.hip): the first-layer
+ * inducing inputs of the reference's models (experiments/build_models.py:179-180, kmeans2(X, M, minit="points")).  `iters` times:
+ *   label_n = argmin_m sum_d (X[n, d] - C[m, d])^2    (dimension order; ties to the lowest m: the comparison is a strict <)
+ *   C[m]    = mean of { X[n] : label_n == m }         (a centroid without members keeps its row)
+ * X [N, D] and Z_init [M, D] row-major float32; everything formed from them is float64 (differences, squares, sums, means), and the
+ * running centroids C stay float64 in the workspace between iterations.  The distance is the sum above as written, never the expansion
+ * |x|^2 - 2 x.c + |c|^2.  1 + 2 iters launches on `stream`, nothing returns to the host in between.
+ *   out_Z [M, D] float32, required: the float32 rounding of out_Z64 and nothing else; it may be Z_init.
+ *   out_Z64 [M, D] or NULL: the centroids after the last update.
+ *   out_labels [N] or NULL: the labels of the LAST assignment -- against the centroids before the last update, as SciPy returns them.
+ *   out_counts [M] or NULL: the members at that assignment;  out_inertia [1] or NULL: the sum of the labelled points' smallest squared
+ *   distances at that assignment.
+ * A point with a non-finite coordinate gets label -1 and enters no sum, no count and no inertia (SciPy refuses such data; check it
+ * before the call where that is wanted).  No floating-point atomics: every sum is taken in an order fixed by (N, M, D), so two calls on
+ * the same inputs give the same bits.  M > N is allowed: the surplus centroids stay where Z_init put them.
+ * ws: iwvi_kmeans_ws_bytes(N, M, D) bytes of device memory, contents arbitrary; at most 512 partial [M, D] sums, whatever N is.  That
+ * function returns 0 for sizes iwvi_kmeans refuses.
+ * IWVI_ERR_ARG (iwvi_last_error names the entry point) before any HIP call for: a null X, Z_init, out_Z or ws; N outside 1 .. 2^31 - 1;
+ * D outside 1 .. IWVI_MAX_D; M outside 1 .. IWVI_MAX_M; iters < 1. */
+size_t iwvi_kmeans_ws_bytes(int64_t N, int M, int D);
+int iwvi_kmeans(const float* X, int64_t N, int D, const float* Z_init, int M, int iters,
+                float* out_Z, double* out_Z64, int32_t* out_labels, int32_t* out_counts, double* out_inertia,
+                void* ws, void* stream);
+
 /* ------------------------------------------------------------------------
  * Likelihoods other than the Gaussian (additive extension of ABI 19; csrc/likelihood_tail.hip).  The reference hands ANY GPflow-1.x
  * likelihood object to its models and calls variational_expectations (models.py:66,134) and predict_mean_and_var (:105) on it.  The

@@ -92,7 +92,10 @@ def main(argv=None):
     ap.add_argument("--levels", type=int, default=200)
     ap.add_argument("--out", default="demo_out")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--kmeans", choices=("host", "device"), default="host",
+                    help="where the inducing inputs are clustered: SciPy's kmeans2 on the host, or iwvi_kmeans on the device")
     a = ap.parse_args(argv)
+    ARGS.kmeans = a.kmeans
     os.makedirs(a.out, exist_ok=True)
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(a.seed)

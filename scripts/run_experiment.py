@@ -93,6 +93,8 @@ def main(argv=None):
     p.add_argument("--sghmc_spacing", type=int, default=5, help="--mode SGHMC: sample ops between two kept posterior samples")
     p.add_argument("--use_graph", type=int, default=1, help="replay the ops of a step from captured graphs")
     p.add_argument("--device_eval", action="store_true", help="evaluate on the device: fused y-samples + iwvi_sample_stats (evaluate(on_device=True))")
+    p.add_argument("--kmeans", choices=("host", "device"), default="host",
+                   help="where the first layer's inducing inputs are clustered: SciPy's kmeans2 on the host, or iwvi_kmeans on the device")
     ARGS = p.parse_args(argv)
     ARGS.fix_linear = bool(ARGS.fix_linear)
     rng = np.random.default_rng(ARGS.seed)
