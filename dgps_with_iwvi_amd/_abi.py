@@ -277,6 +277,8 @@ PROTOTYPES = {
     "iwvi_lik_predict_mean_and_var": (c_int, [ctypes.POINTER(LikDesc), c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "iwvi_lik_predict_mixture": (c_int, [ctypes.POINTER(LikDesc), c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_int64,
                                          c_void_p, c_void_p, c_void_p, c_void_p]),
+    "iwvi_lik_sample_y": (c_int, [ctypes.POINTER(LikDesc), c_void_p, c_void_p, c_int64, c_int, c_void_p,
+                                  ctypes.c_uint64, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "iwvi_unwhiten": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "iwvi_fill_normal": (c_int, [c_void_p, c_int64, ctypes.c_uint64, ctypes.c_uint64, c_void_p]),
     "iwvi_fill_normal_dev": (c_int, [c_void_p, c_int64, ctypes.c_uint64, c_void_p, c_void_p]),

@@ -344,6 +344,10 @@ inline int launch_elem_mode(const char* what, int mode, long long n, F&& launch)
     return check_launch(what);
 }
 
+// ---- csrc/likelihood_tail.hip: the descriptor checks every iwvi_lik_* entry point shares (csrc/likelihood_sample.hip calls them too) ----
+int take_lik(const iwvi_lik_desc* d, Lik& L, const char* what, bool need_df2 = false);
+int mc_check_classes(const Lik& L, int Dy, const char* what);
+
 // ---- csrc/likelihood_multiclass.hip (IWVI_LIK_MULTICLASS: lik.p0 = epsilon, lik.p1 = Dy = the number of classes, Y one column of labels) ----
 int mc_launch_elbo(const LikReduceArgs& g, hipStream_t stream);                   // k_mc_elbo<SEG>
 int mc_launch_elbo_bwd(const LikBwdArgs& a, hipStream_t stream);                  // k_mc_elbo_bwd (the caller launches k_lik_finish behind it)

@@ -261,12 +261,12 @@ __global__ __launch_bounds__(LIK_THREADS) void k_lik_mix(LikMixArgs g) {
 
 // descriptor -> kernel argument; what: the entry point's name for the error text; need_df2: predict_mean_and_var of the Student-t
 // IWVI_LIK_MULTICLASS: the moments have one column per class (Dy = param[1]) while Y has ONE column of labels
-static int mc_check_classes(const Lik& L, int Dy, const char* what) {
+int mc_check_classes(const Lik& L, int Dy, const char* what) {
     if (Dy != (int)L.p1) { set_error("%s: MultiClass with %d classes needs Dy = %d, got %d", what, (int)L.p1, (int)L.p1, Dy); return IWVI_ERR_ARG; }
     return IWVI_OK;
 }
 
-static int take_lik(const iwvi_lik_desc* d, Lik& L, const char* what, bool need_df2 = false) {
+int take_lik(const iwvi_lik_desc* d, Lik& L, const char* what, bool need_df2) {
     if (!d) { set_error("%s: null likelihood descriptor", what); return IWVI_ERR_ARG; }
     L.type = d->type; L.p0 = d->param[0]; L.p1 = d->param[1]; L.lgc = d->lgc; L.p0_dev = d->param0_dev;
     switch (d->type) {

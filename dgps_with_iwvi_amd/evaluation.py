@@ -411,3 +411,42 @@ def evaluate_mixture(model, X_test, Y_test, num_predict_samples=2000, predict_ba
     if return_predictions:
         res["mean"], res["var"] = pm["mean"].cpu().numpy(), pm["var"].cpu().numpy()
     return res
+
+
+def evaluate_draws(model, X_test, Y_test, num_predict_samples=2000, predict_batch_size=1000, interval=0.9):
+    """Posterior-predictive check of ONE target column, any likelihood, from the exact draws of ``model.predict_y_draws``: per batch of
+    ``predict_batch_size`` points one draw of ``num_predict_samples`` targets per point and one ``sample_stats`` launch (one sort) ->
+    ``test_coverage``, the share of targets inside the central ``interval`` of their draws (the empirical quantiles at (1 -+ interval) / 2,
+    both ends included: the draws of a count or a label are discrete); ``test_interval_width``, that interval's mean width;
+    ``test_rmse``, the draws' mean against Y; and for the continuous likelihoods (Gaussian, Student-t, Exponential, Gamma, Beta)
+    ``test_loglik``, the reference's KDE test log-likelihood (run_conditional_density_estimation.py:148-165) from the same launch.
+    One read-back at the end."""
+    from .likelihoods import Bernoulli, MultiClass, Ordinal, Poisson, target_dim
+    if not 0.0 < float(interval) < 1.0:
+        raise ValueError("interval must lie in (0, 1), got %r" % (interval,))
+    dev = model.X.device
+    X_test = torch.as_tensor(np.asarray(X_test, dtype=np.float32), device=dev) if not isinstance(X_test, torch.Tensor) else X_test.to(dev, settings.float_type)
+    Y_test = torch.as_tensor(np.asarray(Y_test, dtype=np.float32), device=dev) if not isinstance(Y_test, torch.Tensor) else Y_test.to(dev, settings.float_type)
+    N = X_test.shape[0]
+    if target_dim(model.likelihood, model._output_dim()) != 1:
+        raise ValueError("evaluate_draws is for one target column, the model has %s" % (model._output_dim(),))
+    if N == 0 or Y_test.numel() != N:
+        raise ValueError("X_test has %d rows, Y_test must be [%d, 1], got %s" % (N, N, tuple(Y_test.shape)))
+    Y_test = Y_test.reshape(N)
+    continuous = not isinstance(model.likelihood, (Bernoulli, MultiClass, Ordinal, Poisson))
+    probs = [0.5 * (1.0 - float(interval)), 0.5 * (1.0 + float(interval))]
+    parts = []
+    for lo in range(0, N, int(predict_batch_size)):
+        x, y = X_test[lo:lo + predict_batch_size], Y_test[lo:lo + predict_batch_size]
+        smp = model.predict_y_draws(x, num_predict_samples)[:, :, 0]                # [S, n], a point's draws contiguous
+        parts.append(sample_stats(smp, y, shapiro=False, quantiles=probs))
+    cat = {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+    q = cat["quantiles"].double()
+    inside = (Y_test.double() >= q[:, 0]) & (Y_test.double() <= q[:, 1])
+    stats = [inside.double().mean(), (q[:, 1] - q[:, 0]).mean(), cat["sqerr"].double().mean().sqrt()]
+    names = ["test_coverage", "test_interval_width", "test_rmse"]
+    if continuous:
+        stats.append(cat["logp"].double().mean())
+        names.append("test_loglik")
+    vals = torch.stack(stats).cpu().numpy()                                         # the one read-back
+    return {k: float(v) for k, v in zip(names, vals)}

@@ -54,7 +54,36 @@ def _moments(Fmu, Fvar, Y, likelihood=None):
     return Fmu, Fvar, Y, Fmu.numel() // max(Dy, 1), Dy
 
 
-class _QuadratureLikelihood:
+def sample_y_launch(desc, Fmu, Fvar, z_f=None, return_f=False, seed=None, serial=None):
+    """One ``iwvi_lik_sample_y`` launch on contiguous device moments [..., Dy] for the descriptor ``desc`` -> y [..., Dt] (Dt = 1 for the
+    MultiClass, else Dy), or (y, f) with ``return_f``."""
+    Fmu, Fvar, _, T, Dy = _moments(Fmu, Fvar, None)
+    if z_f is not None:
+        z_f = _abi.dev_tensor(torch.as_tensor(z_f, device=Fmu.device).expand_as(Fmu).contiguous(), "z_f")
+    Dt = 1 if desc.type == _abi.LIK_MULTICLASS else Dy
+    out_y = torch.empty(*Fmu.shape[:-1], Dt, dtype=Fmu.dtype, device=Fmu.device) if Fmu.dim() else torch.empty_like(Fmu)
+    out_f = torch.empty_like(Fmu) if return_f else None
+    if Fmu.numel() == 0:                                             # (an empty tensor has no address to hand over: nothing to launch)
+        return (out_y, out_f) if return_f else out_y
+    _abi.check(_abi.lib().iwvi_lik_sample_y(desc, _abi.ptr(Fmu), _abi.ptr(Fvar), T, Dy, _abi.ptr(z_f),
+                                            settings.seed if seed is None else int(seed),
+                                            settings.next_sample_serial() if serial is None else int(serial),
+                                            None, _abi.ptr(out_y), _abi.ptr(out_f), _abi.stream_ptr()))
+    return (out_y, out_f) if return_f else out_y
+
+
+class _SampleY:
+    """``sample_y`` of every likelihood: exact draws of a target, one ``iwvi_lik_sample_y`` launch (``csrc/likelihood_sample.hip``)."""
+
+    def sample_y(self, Fmu, Fvar, z_f=None, return_f=False, seed=None, serial=None):
+        """y ~ p(y | f), f = Fmu + sqrt(Fvar) z (``Fvar`` None: f = Fmu), elementwise on device moments [..., Dy] -> [..., Dy] (MultiClass:
+        [..., 1] labels).  ``z_f``: the standard normals of f, drawn when None; ``return_f``: also the f that was used.  The noise is the
+        sub-stream (``seed``, ``serial``) per element: ``settings.seed`` and the next serial of ``settings.next_sample_serial`` by default,
+        the same pair gives the same bits."""
+        return sample_y_launch(self.lik_desc(), Fmu, Fvar, z_f=z_f, return_f=return_f, seed=seed, serial=serial)
+
+
+class _QuadratureLikelihood(_SampleY):
     """The methods of a likelihood whose arithmetic lives in ``csrc/likelihood_tail.hip``."""
 
     def variational_expectations(self, Fmu, Fvar, Y):
@@ -88,7 +117,7 @@ class _QuadratureLikelihood:
         return m, v
 
 
-class Gaussian(DeviceScalarVariance):
+class Gaussian(_SampleY, DeviceScalarVariance):
     def __init__(self, variance=1.0, name=None):
         self.variance = float(variance)
         self.name = name
@@ -226,7 +255,7 @@ class RobustMax:
         self.epsilon = float(epsilon)
 
 
-class MultiClass:
+class MultiClass(_SampleY):
     """gpflow 1.x ``MultiClass(num_classes)`` with the ``RobustMax`` link (its default).  ``Y`` is ONE column of class labels 0 .. C-1; ``F``,
     ``Fmu`` and ``Fvar`` have C columns.  With p = prob_is_largest(Y; Fmu, Fvar) by the 20-point rule over the label's own latent
     (``csrc/likelihood_multiclass.hip``; clips and the 1e-4 cdf jitter as GPflow's) and eps_1 = epsilon / (C - 1):

@@ -100,7 +100,8 @@ class DGP_VI:
         return self
 
     def _words(self):
-        """[ticket, rng step, rng ticket] device words, zeroed once (never per call)."""
+        """[ticket, rng step, rng ticket, draw serial] device words, zeroed once (never per call).  Word 3 belongs to ``predict_y_draws``
+        (``iwvi_lik_sample_y``'s ``serial_dev``): the serial in its low half, the running launch's arrival count in its high half."""
         dev = self.X.device
         if self._dev_words is None or self._dev_words.device != dev:
             self._dev_words = torch.zeros(4, dtype=torch.int64, device=dev)
@@ -628,8 +629,9 @@ class DGP_VI:
         ``predict_y_samples(X, S, zs, z_y)``; what is not given is drawn in the kernel.  The result is a transposed view of the kernel's
         [N, S, Dy], in which a point's S samples are contiguous (what ``evaluation.sample_stats`` reads fastest)."""
         if not is_gaussian(self.likelihood):
-            raise NotImplementedError("predict_y_samples_fused adds Gaussian noise in the launch's tail; with %s use predict_mixture (the "
-                                      "predictive mixture's moments and log density over S draws) or predict_y_samples (layer by layer, "
+            raise NotImplementedError("predict_y_samples_fused adds Gaussian noise in the launch's tail; with %s use predict_y_draws (exact "
+                                      "draws of the targets from the likelihood), predict_mixture (the predictive mixture's moments and "
+                                      "log density over S draws) or predict_y_samples (layer by layer, the moment-matched m + z sqrt(v) of "
                                       "the likelihood's predict_mean_and_var)" % type(self.likelihood).__name__)
         X = _data(X)
         S = int(S)
@@ -659,6 +661,59 @@ class DGP_VI:
             self._fused_forward(nb * S, S, nb, (nb * S,), zs=zb, want_logw=False, use_encoder=False,
                                 X=X[lo:hi], predict=dict(S=S, out_y=out[lo:hi], z_y=zyb))
         return out.transpose(0, 1)
+
+    def predict_y_draws(self, X, S, zs=None, z_f=None, batch_size=None, return_f=False, serial=None):
+        """EXACT draws of the predictive targets [S, N, Dt] for any likelihood: y ~ p(y | f), f ~ N(m_s, v_s) over S draws through the inner
+        layers (drawn as in ``predict_f_multisample``; ``zs``: one [S, N, dim] array or None per layer) -- counts for a Poisson, labels for
+        a Bernoulli / Ordinal / MultiClass (Dt = 1 there, else Dt = Dy), heavy tails for a Student-t --, where ``predict_y_samples`` stays
+        the reference's moment-matched ``m + z sqrt(v)``.  Per batch of ``batch_size`` points: one precompute, the layer launch without a
+        tail (the final layer's moments, rows n S + s) and ONE ``iwvi_lik_sample_y`` launch on them.  ``z_f`` [S, N, Dy]: the standard
+        normals of f (drawn when None); ``return_f``: also the f that was used, [S, N, Dy].  Both results are transposed views of
+        [N, S, .] buffers, in which a point's S draws are contiguous (what ``evaluation.sample_stats`` reads fastest).
+        The draws' serial lives with the model's device words and every launch advances it: a captured call replays with fresh draws, and
+        every batch has a serial of its own -- so the bits depend on ``batch_size``, the distribution does not.  ``serial``: a host
+        serial instead (batch i takes ``serial + i``): the same call then gives the same bits."""
+        X = _data(X)
+        S = int(S)
+        if S < 1:
+            raise ValueError("S must be >= 1, got %d" % S)
+        if X.dim() != 2 or X.shape[1] != self._input_dim():
+            raise ValueError("X must be [N, %s], got %s" % (self._input_dim(), tuple(X.shape)))
+        Dy = self._output_dim()
+        if Dy is None:
+            raise ValueError("predict_y_draws needs a GP layer as the last layer")
+        N = X.shape[0]
+        zs = self._check_predict_noise("predict_y_draws", S, N, zs)
+        if z_f is not None and tuple(z_f.shape) != (S, N, Dy):
+            raise ValueError("z_f must be [S, N, %d] = %s, got %s" % (Dy, (S, N, Dy), tuple(z_f.shape)))
+        bs = max(1, self._PREDICT_ROWS // S) if batch_size is None else int(batch_size)
+        if bs < 1:
+            raise ValueError("batch_size must be >= 1")
+        desc = self.likelihood.lik_desc() if hasattr(self.likelihood, "lik_desc") else None
+        if desc is None:                                             # (an object that only quacks like the Gaussian: is_gaussian)
+            desc = _abi.LikDesc()
+            desc.type = _abi.LIK_GAUSSIAN
+            desc.param[0], desc.param0_dev = self.likelihood.desc_variance()
+        Dt = target_dim(self.likelihood, Dy)
+        dev = X.device
+        out = torch.empty(N, S, Dt, dtype=settings.float_type, device=dev)
+        out_f = torch.empty(N, S, Dy, dtype=settings.float_type, device=dev) if return_f else None
+        if N:
+            self.precompute()
+        last = len(self.layers) - 1
+        for i, lo in enumerate(range(0, N, bs)):
+            hi = min(N, lo + bs)
+            nb = hi - lo
+            zb = [None if z is None else _data(z)[:, lo:hi].transpose(0, 1).reshape(nb * S, -1) for z in zs]   # point-major rows n S + s
+            zfb = None if z_f is None else _abi.dev_tensor(_data(z_f)[:, lo:hi].transpose(0, 1).reshape(nb * S, Dy).contiguous(), "z_f")
+            _, outs, _ = self._fused_forward(nb * S, S, nb, (nb * S,), zs=zb, sampled_kl=False, want_layers=True, want_logw=False,
+                                             use_encoder=False, X=X[lo:hi], outputs_for={last})
+            _abi.check(_abi.lib().iwvi_lik_sample_y(
+                desc, _abi.ptr(outs[last]["mean"]), _abi.ptr(outs[last]["var"]), nb * S, Dy, _abi.ptr(zfb), settings.seed,
+                0 if serial is None else int(serial) + i,
+                ctypes.c_void_p(self._words().data_ptr() + 24) if serial is None else None,
+                _abi.ptr(out[lo:hi]), None if out_f is None else _abi.ptr(out_f[lo:hi]), _abi.stream_ptr()))
+        return (out.transpose(0, 1), out_f.transpose(0, 1)) if return_f else out.transpose(0, 1)
 
     def predict_y_samples(self, X, S, zs=None, z_y=None):
         X = _data(X)

@@ -12,6 +12,7 @@ float_type = torch.float32
 jitter_level = 1e-6          # gpflow.settings.numerics.jitter_level default
 seed = 0                     # Philox key of the on-device N(0,1) stream (iwvi_fill_normal)
 _offset = 0                  # Philox counter; advanced by every draw
+_sample_serial = 0           # serial of the likelihoods' sample_y stream (iwvi_lik_sample_y); advanced by every call that is not given one
 # Arithmetic of the R * M^2 contraction (stage 2 of the layer kernel) and of the adjoint chain's S_r products: split-f16 operands on
 # v_mfma_f32_16x16x32_f16 (default; 22 operand mantissa bits) or fp32 MFMAs.  Passed PER CALL in the descriptors
 # (iwvi_layer_desc.flags / iwvi_gp_bwd_desc.flags); the environment variables only set these defaults.
@@ -78,9 +79,17 @@ def next_noise_offset(n):
     return off
 
 
+def next_sample_serial():
+    """The next serial of the ``sample_y`` stream (``iwvi_lik_sample_y``: one sub-stream per element, keyed by (seed, serial))."""
+    global _sample_serial
+    s = _sample_serial
+    _sample_serial += 1
+    return s
+
+
 def set_seed(s):
-    global seed, _offset
-    seed, _offset = int(s), 0
+    global seed, _offset, _sample_serial
+    seed, _offset, _sample_serial = int(s), 0, 0
 
 
 @contextlib.contextmanager

@@ -814,6 +814,39 @@ int iwvi_lik_predict_mixture(const iwvi_lik_desc* lik, const float* fmean, const
                              int64_t N, int S, int Dy, int64_t stride_n, int64_t stride_s,
                              float* out_logp, float* out_mean, float* out_var, void* stream);
 
+/* Exact draws of a predictive target, y ~ p(y | f) with f ~ N(fmean, fvar), for every likelihood above (additive extension of ABI 19;
+ * csrc/likelihood_sample.hip).  fmean, fvar [T, Dy]: the final layer's moments, one row per (point, draw) in either layout -- the kernel is
+ * elementwise over rows.  fvar == NULL: f = fmean.  z_f: optional [T, Dy] standard normals for f (tests); otherwise they are drawn.
+ * out_f: optional [T, Dy], the f that was used (the exported noise: a test conditions on it).  out_y [T, Dt], Dt = Dy, except MULTICLASS:
+ * Dy = C and Dt = 1 (one label column).  f = fmean + sqrt(max(fvar, 0)) z; links and jitters as in the table above:
+ *   GAUSSIAN     y = f + sqrt(variance) e
+ *   BERNOULLI    y = 1 with probability ip(f) = Phi(f) (1 - 2e-3) + 1e-3, else 0
+ *   STUDENT_T    y = f + s n / sqrt(g / (nu / 2)),  n ~ N(0, 1), g ~ Gamma(nu / 2, 1); any nu > 0
+ *   MULTICLASS   the first arg-max of f_1 .. f_C with probability 1 - epsilon, otherwise one of the other C - 1 classes, uniformly
+ *   POISSON      y ~ Poisson(b exp(f)), exact: sequential inversion below a rate of 10, Hoermann's transformed rejection (PTRS) from 10 on,
+ *                round(rate + sqrt(rate) n) from 2^24 on (float32 no longer holds the integers); a rate of +inf gives +inf
+ *   EXPONENTIAL  y = -exp(f) log u, u in (0, 1]
+ *   GAMMA        y = exp(f) G, G ~ Gamma(a, 1) by Marsaglia-Tsang; a < 1: Gamma(a + 1) u^(1/a), formed in log space
+ *   BETA         alpha = ip(f) s, beta = s - alpha, y = G_alpha / (G_alpha + G_beta)
+ *   ORDINAL      bin j with probability P_j(f) / sum_k P_k(f) (the P_j sum to 0.998): inverse CDF over the n + 1 bins from one uniform
+ * A NaN moment gives a NaN y.  param0_dev is honoured as everywhere: trained variance, scale, shape and sigma are read on the device.
+ * EVERY LOOP IS CAPPED: a rejection sampler (Marsaglia-Tsang, PTRS) runs at most 32 rounds -- exhaustion probability below 0.14^32 = 5e-28
+ * at their acceptance rates -- and then returns the conditional mean (f; a exp(f); ip(f); the rate, rounded); the Poisson inversion takes at
+ * most 64 steps (P(Poisson(10) > 64) < 1e-29); the Ordinal walks its n edges, the MultiClass its C classes.
+ * Randomness: Philox4x32-10, one sub-stream per ELEMENT (draw consumption varies): counter = (element index low, high, round, serial low),
+ * key = (seed low, seed high ^ serial high); element = t Dy + d.  Round 0 gives z, a second normal and two uniforms; rounds 1 .. 32 (BETA:
+ * 33 .. 64 for G_beta) feed one rejection round each.  The same (seed, serial) gives the same bits.  serial_dev, if given, is ONE device
+ * word read instead of `serial`: its low 32 bits are the serial, its high 32 bits count the arrivals of the running launch (zero the word
+ * once).  Every workgroup reads the serial, the last one to finish clears the count and adds one to the serial (the ticket of
+ * iwvi_fill_normal_dev, kept in the word itself): replays of a captured graph draw fresh values; launches sharing a word must be
+ * stream-ordered.  The device serial is 32 bits wide: the key's hi32(serial) term is 0 with serial_dev, and the word must be re-zeroed
+ * before its 2^32nd launch (the increment would carry into the arrival count).
+ * ONE launch, no workspace, no host synchronisation: capturable in a hipGraph.  T = 0: IWVI_OK, nothing is launched.  IWVI_ERR_ARG (with
+ * iwvi_last_error) before any launch: a null or invalid descriptor (the checks of iwvi_lik_predict_mixture), T < 0, Dy outside
+ * 1..IWVI_MAX_P, MULTICLASS with Dy != C, a null out_y (or, with T > 0, a null fmean). */
+int iwvi_lik_sample_y(const iwvi_lik_desc* lik, const float* fmean, const float* fvar, int64_t T, int Dy, const float* z_f,
+                      uint64_t seed, uint64_t serial, uint64_t* serial_dev, float* out_y, float* out_f, void* stream);
+
 /* white=False (temp_workaround.py:63-65: "another backsubstitution in the unwhitened case").  The unwhitened
  * q(u) = N(f, q_sqrt q_sqrt^T) gives the same conditional as the whitened one with f_w = Lm^-1 f and
  * q_sqrt_w[r] = Lm^-1 tril(q_sqrt[r]) (lower triangular again), so the back-substitution is applied ONCE to the
