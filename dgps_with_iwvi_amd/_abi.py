@@ -121,6 +121,15 @@ class AdamTensor(ctypes.Structure):
                 ("n", c_int64), ("transform", ctypes.c_int32)]
 
 
+class MomentsTensor(ctypes.Structure):
+    """struct iwvi_moments_tensor (include/iwvi_hip.h)."""
+    _fields_ = [("x", c_void_p), ("mean", c_void_p), ("m2", c_void_p), ("n", c_int64)]
+
+
+MOMENTS_MAX_TENSORS = 48
+LV_GRAD_IWAE, LV_GRAD_DREG, LV_GRAD_STL = 0, 1, 2              # IWVI_LV_GRAD_*
+LV_GRAD = {"iwae": LV_GRAD_IWAE, "dreg": LV_GRAD_DREG, "stl": LV_GRAD_STL}
+
 SGHMC_MAX_TENSORS = 8
 
 
@@ -182,6 +191,14 @@ PROTOTYPES = {
                                           c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "iwvi_lv_layer_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                        c_int, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "iwvi_lv_layer_backward_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                          c_int, c_int64, c_int, c_int, c_int, c_double, c_void_p, c_void_p]),
+    "iwvi_lv_encoder_backward_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                            c_int, c_int64, c_int, c_int, c_int, c_double,
+                                            c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
+                                            ctypes.POINTER(ctypes.c_int32), c_int, c_int,
+                                            ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_void_p, c_void_p]),
+    "iwvi_moments_update": (c_int, [ctypes.POINTER(MomentsTensor), c_int, c_void_p, c_void_p]),
     "iwvi_encoder_backward_ws_bytes": (c_size_t, [c_int64, ctypes.POINTER(ctypes.c_int32), c_int]),
     "iwvi_encoder_backward_act": (c_int, [c_void_p, c_int64, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
                                           ctypes.POINTER(ctypes.c_int32), c_int, c_int, c_void_p,

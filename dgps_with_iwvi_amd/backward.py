@@ -301,23 +301,25 @@ def _encoder_adjoint_buffers(layer, XY, B, dev):
     return dW, db, _abi.ptr(XY), (Wp, bp, dims, n, layer.encoder.act), (_abi.ptr_array(dW), _abi.ptr_array(db), ws.data_ptr()), (keep, ws, XY)
 
 
-def lv_backward(layer, XY, enc_out, eps, dF_next, col0, w, B, K, sampled_kl=True, fused=True):
-    """``iwvi_lv_layer_backward`` + ``iwvi_encoder_backward`` -> (dW list, db list) of the layer's encoder.
-    ``enc_out`` [B, 2*latent_dim] = (means | raw) as the precompute launch leaves it (``layer._enc_out``)."""
+def lv_backward(layer, XY, enc_out, eps, dF_next, col0, w, B, K, sampled_kl=True, fused=True, estimator="iwae", w_unit=1.0):
+    """``iwvi_lv_layer_backward_ex`` + ``iwvi_encoder_backward`` -> (dW list, db list) of the layer's encoder.
+    ``enc_out`` [B, 2*latent_dim] = (means | raw) as the precompute launch leaves it (``layer._enc_out``).
+    ``estimator`` ("iwae" | "dreg" | "stl") and ``w_unit`` (num_data / B: ``w / w_unit`` is the normalised importance weight) reach the
+    kernel on all three routes: fused, two launches, and the custom activation, whose d(encoder output) the kernel forms."""
     dev = enc_out.device
     Lw = layer.latent_dim
     enc_out = _abi.dev_tensor(enc_out, "enc_out")
     # (means, raw, their row stride, ..., the adjoint of the layer above and the columns it has for this layer, the weights)
     latent = (ctypes.c_void_p(enc_out.data_ptr()), ctypes.c_void_p(enc_out.data_ptr() + 4 * Lw), 2 * Lw, 1,
               _abi.ptr(eps), _abi.ptr(dF_next), 0 if dF_next is None else dF_next.shape[1], col0,
-              _abi.ptr(w), Lw, B, K, 1 if sampled_kl else 0)
+              _abi.ptr(w), Lw, B, K, 1 if sampled_kl else 0, _abi.LV_GRAD[estimator], float(w_unit))
     if layer.encoder.custom_act is None and fused:
-        # one launch: the encoder's workgroups form the d(means | raw) of their own rows (iwvi_lv_encoder_backward)
+        # one launch: the encoder's workgroups form the d(means | raw) of their own rows (iwvi_lv_encoder_backward_ex)
         dW, db, xy, enc, out, _keep = _encoder_adjoint_buffers(layer, XY, B, dev)
-        _abi.check(_abi.lib().iwvi_lv_encoder_backward(*latent, xy, *enc, *out, _abi.stream_ptr()))
+        _abi.check(_abi.lib().iwvi_lv_encoder_backward_ex(*latent, xy, *enc, *out, _abi.stream_ptr()))
         return dW, db
     d_enc = torch.empty(B, 2 * Lw, dtype=settings.float_type, device=dev)
-    _abi.check(_abi.lib().iwvi_lv_layer_backward(*latent, _abi.ptr(d_enc), _abi.stream_ptr()))
+    _abi.check(_abi.lib().iwvi_lv_layer_backward_ex(*latent, _abi.ptr(d_enc), _abi.stream_ptr()))
     if layer.encoder.custom_act is not None:
         # a user-supplied activation: the encoder is torch ops (layers.Encoder.torch_raw), so are its weight gradients -- the
         # vector-Jacobian product of d(encoder output), which the kernel above formed
@@ -333,9 +335,14 @@ def lv_backward(layer, XY, enc_out, eps, dF_next, col0, w, B, K, sampled_kl=True
     return dW, db
 
 
-def _checked(model, zs, mode_vi, gauss, exchange, wrt, overlap, q_moved, prepare_route):
+def _checked(model, zs, mode_vi, gauss, exchange, wrt, overlap, q_moved, prepare_route, encoder_gradient="iwae"):
     """Everything the evaluation refuses before it queues work -> (zs: per layer None or [B, K, dim], final_q, inline)."""
     layers = model.layers
+    if encoder_gradient not in _abi.LV_GRAD:
+        raise ValueError("encoder_gradient is one of %s, not %r" % (" | ".join(_abi.LV_GRAD), encoder_gradient))
+    if mode_vi and encoder_gradient != "iwae":
+        raise ValueError("encoder_gradient=%r: the analytic-KL bound (mode_vi) has the 'iwae' estimator only -- 'dreg' and 'stl' belong to "
+                         "the sampled regulariser of the importance-weighted bound" % (encoder_gradient,))
     B, K = model.X.shape[0], model.num_samples
     zs = [None] * len(layers) if zs is None else list(zs)
     if len(zs) != len(layers):
@@ -511,7 +518,7 @@ def branch_placement(layers, overlap, branch_order):
     return -1, deferred[0]
 
 
-def _reverse_sweep(model, saved, prepared, XY, adj, mode_vi, kl_weight, overlap, branch_order, cur, grads):
+def _reverse_sweep(model, saved, prepared, XY, adj, mode_vi, kl_weight, overlap, branch_order, cur, grads, encoder_gradient="iwae"):
     """The layers' adjoints, top to bottom, into ``grads``: the GP layers' per-sample chains back to back on the caller's stream ``cur``; a
     layer's parameter branch ("_finish") is queued once the chain of the layer BELOW is, where ``branch_placement`` puts it."""
     layers = model.layers
@@ -542,7 +549,9 @@ def _reverse_sweep(model, saved, prepared, XY, adj, mode_vi, kl_weight, overlap,
             if i == on_cur:                                      # queued behind everything else on the caller's stream, below
                 finish_on_cur, pending = pending, None
         else:
-            dW, db = lv_backward(layer, XY, s.enc_out, s.eps, dF, s.D_in, adj["w"], B, K, not mode_vi)
+            # (w / w_unit = the normalised importance weight; K-sharded, w is this rank's share against the merged normaliser: still right)
+            dW, db = lv_backward(layer, XY, s.enc_out, s.eps, dF, s.D_in, adj["w"], B, K, not mode_vi,
+                                 estimator=encoder_gradient, w_unit=float(model.num_data) / float(B))
             for j, (a, b) in enumerate(zip(dW, db)):
                 grads["l%d.encW%d" % (i, j)], grads["l%d.encb%d" % (i, j)] = a, b
             dF = None if (dF is None or i == 0) else dF[:, :s.D_in].contiguous()
@@ -555,8 +564,12 @@ def _reverse_sweep(model, saved, prepared, XY, adj, mode_vi, kl_weight, overlap,
 
 
 def iw_elbo_and_gradients(model, zs=None, mode_vi=None, exchange=None, K_total=None, kl_weight=1.0, overlap=True, wrt="all", fuse_heads=True,
-                          prefactor=False, q_moved=None):
-    """``wrt="final_q"``: only the final layer's 'l<i>.q_mu' / 'l<i>.q_sqrt' (all that the natural-gradient op of
+                          prefactor=False, q_moved=None, encoder_gradient=None):
+    """``encoder_gradient`` ("iwae" | "dreg" | "stl"; default: ``model.encoder_gradient``): the estimator of the encoders' gradients
+    ('l<i>.encW<j>' / 'l<i>.encb<j>'; include/iwvi_hip.h: IWVI_LV_GRAD_*).  The bound and every other gradient do not depend on it;
+    ``wrt="final_q"`` forms no encoder gradient and ignores it; the analytic-KL bound (``mode_vi``) refuses anything but "iwae".
+
+    ``wrt="final_q"``: only the final layer's 'l<i>.q_mu' / 'l<i>.q_sqrt' (all that the natural-gradient op of
     build_models.py:288-295 uses): same forward and bound, and of the adjoints only the final layer's two sums over samples.
 
     ``mode_vi`` (default: the model is a DGP_VI, not a DGP_IWVI): the bound of models.py:49-86 instead -- analytic
@@ -592,7 +605,9 @@ def iw_elbo_and_gradients(model, zs=None, mode_vi=None, exchange=None, K_total=N
     mode_vi = (not isinstance(model, DGP_IWVI)) if mode_vi is None else bool(mode_vi)
     gauss = is_gaussian(model.likelihood)
     prepare_route, branch_order = settings.backward_routes()
-    zs, final_q, inline = _checked(model, zs, mode_vi, gauss, exchange, wrt, overlap, q_moved, prepare_route)
+    if encoder_gradient is None:
+        encoder_gradient = getattr(model, "encoder_gradient", "iwae")
+    zs, final_q, inline = _checked(model, zs, mode_vi, gauss, exchange, wrt, overlap, q_moved, prepare_route, encoder_gradient)
     X, Y = _abi.dev_tensor(model.X.contiguous(), "X"), _abi.dev_tensor(model.Y.contiguous(), "Y")
     XY = model._xy_minibatch() if any(isinstance(l, LatentVariableLayer) for l in model.layers) else None
     cur = torch.cuda.current_stream()
@@ -607,8 +622,101 @@ def iw_elbo_and_gradients(model, zs=None, mode_vi=None, exchange=None, K_total=N
         return elbo, _final_q_gradients(model, saved[-1], adj, kl_weight, prefactor, cur)
     if prep_stream != cur:
         cur.wait_stream(prep_stream)                             # dense factors and packed adjoint operands are ready
-    _reverse_sweep(model, saved, prepared, XY, adj, mode_vi, kl_weight, overlap, branch_order, cur, grads)
+    _reverse_sweep(model, saved, prepared, XY, adj, mode_vi, kl_weight, overlap, branch_order, cur, grads, encoder_gradient)
     return elbo, grads
+
+
+class _Moments:
+    """Device-resident Welford accumulators (``iwvi_moments_update``) for a fixed list of gradient names: float64 mean / m2 per tensor and
+    one int64 count per table of at most ``_abi.MOMENTS_MAX_TENSORS`` tensors."""
+
+    def __init__(self, shapes, dev):
+        self.names = list(shapes)
+        self.mean = {n: torch.zeros(shapes[n], dtype=torch.float64, device=dev) for n in self.names}
+        self.m2 = {n: torch.zeros(shapes[n], dtype=torch.float64, device=dev) for n in self.names}
+        cap = _abi.MOMENTS_MAX_TENSORS
+        self.tables = [self.names[i:i + cap] for i in range(0, len(self.names), cap)]
+        self.counts = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in self.tables]
+
+    def update(self, grads):
+        """One update from this evaluation's gradients -> the float32 tensors the launch reads (keep them alive until it has run)."""
+        keep = []
+        for names, count in zip(self.tables, self.counts):
+            arr = (_abi.MomentsTensor * len(names))()
+            for a, n in zip(arr, names):
+                g = _abi.dev_tensor(grads[n].reshape(-1).to(settings.float_type).contiguous(), "grad " + n)
+                if g.numel() != self.mean[n].numel():
+                    raise ValueError("gradient %s has %d entries, its accumulator %d" % (n, g.numel(), self.mean[n].numel()))
+                keep.append(g)
+                a.x, a.mean, a.m2, a.n = g.data_ptr(), self.mean[n].data_ptr(), self.m2[n].data_ptr(), g.numel()
+            _abi.check(_abi.lib().iwvi_moments_update(arr, len(names), count.data_ptr(), _abi.stream_ptr()))
+        return keep
+
+    def result(self):
+        out = {}
+        for names, count in zip(self.tables, self.counts):
+            for n in names:
+                out[n] = dict(mean=self.mean[n], var=self.m2[n] / (count.to(torch.float64) - 1.0), count=count[0])
+        return out
+
+
+def gradient_moments(model, repeats, names=None, zs_list=None, encoder_gradient=None, use_graph=False):
+    """Mean and variance of the gradient over ``repeats`` noise draws at the model's current parameters and minibatch -> {name:
+    dict(mean, var [float64 device tensors shaped like the gradient], count [int64 device scalar])}, ``var = m2 / (count - 1)`` (NaN at
+    one repeat).  Every repeat is one ``iw_elbo_and_gradients`` (fresh device noise, or ``zs_list[r]``) followed by one
+    ``iwvi_moments_update`` over all the tensors: nothing returns to the host in between.  ``names``: the gradients to follow (default:
+    all of them).  ``use_graph``: value + gradient + update captured once (after one eager repeat) and replayed -- device noise only."""
+    repeats = int(repeats)
+    if repeats < 1:
+        raise ValueError("repeats must be at least 1")
+    if zs_list is not None and len(zs_list) != repeats:
+        raise ValueError("zs_list needs one entry per repeat")
+    if use_graph and zs_list is not None:
+        raise ValueError("use_graph draws the noise on the device (a captured graph cannot take per-repeat host arguments)")
+    dev = model.X.device
+    state = {}
+
+    def one(zs):
+        _, g = iw_elbo_and_gradients(model, zs, encoder_gradient=encoder_gradient)
+        if "mom" not in state:
+            chosen = list(g) if names is None else list(names)
+            missing = [n for n in chosen if n not in g]
+            if missing:
+                raise KeyError("no gradient named %s (there are: %s)" % (missing, ", ".join(sorted(g))))
+            state["mom"] = _Moments({n: g[n].shape for n in chosen}, dev)
+        return g, state["mom"].update(g)
+
+    if not use_graph:
+        for r in range(repeats):
+            one(None if zs_list is None else zs_list[r])
+        return state["mom"].result()
+    # one eager repeat (the accumulators are allocated there, on the caller's stream; every once-per-process setup has run), then the
+    # capture on a stream of its own, as training.Trainer._replay
+    one(None)
+    if repeats > 1:
+        side = _side_stream(dev, 3)                              # (one capture stream per caller stream: the adjoint keeps side streams per stream)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
+                held = one(None)                                 # recorded, not executed
+            for _ in range(repeats - 1):
+                graph.replay()
+        torch.cuda.current_stream().wait_stream(side)
+        side.synchronize()                                       # the graph and its memory pool go away with this call: not before its last replay has run
+        del held
+    return state["mom"].result()
+
+
+def snr_summary(moments):
+    """Signal-to-noise figures of ``gradient_moments``' result -> {name: dict(norm_snr, median_snr)} (host floats):
+    ``norm_snr = ||mean||_2 / sqrt(sum var)`` and the median over the elements of ``|mean| / sqrt(var)``."""
+    out = {}
+    for name, m in moments.items():
+        mean, var = m["mean"].reshape(-1), m["var"].reshape(-1)
+        out[name] = dict(norm_snr=float((mean.norm() / var.sum().sqrt()).item()),
+                         median_snr=float((mean.abs() / var.sqrt()).median().item()))
+    return out
 
 
 def parameter_list(model):

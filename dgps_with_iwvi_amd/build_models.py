@@ -94,6 +94,7 @@ def build_model(ARGS, X, Y, apply_name=True, device=None):
     else:
         model = DGP_IWVI(X, Y, layers, lik, minibatch_size=ARGS.minibatch_size,
                          num_samples=ARGS.num_IW_samples, name=name)
+    model.encoder_gradient = getattr(ARGS, "encoder_gradient", "iwae")     # (a DGP_VI refuses anything but "iwae")
     model = model.to(device or settings.default_device())
     if model.X.is_cuda and settings.f64_stage1 == "auto" and getattr(ARGS, "autotune_f64", True):
         # the float64 stage-1 route per layer from the measured diag(Lm) ratio of the initial values (k-means inducing inputs can

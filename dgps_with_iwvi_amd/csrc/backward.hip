@@ -2174,6 +2174,7 @@ __global__ __launch_bounds__(256) void k_elbo_finish(ElboFinishArgs a) {
 struct LvBwdArgs {
     const float* mu; const float* sigma; int ld_enc, raw; const float* eps; const float* dFn; int ld, col0;
     const float* w; int Lw; long long B; int K, sampled; float* d_out;
+    int est; float inv_unit;                                   // IWVI_LV_GRAD_* (uniform over the launch), 1 / w_unit: w inv_unit = the normalised weight
 };
 // (point b, latent dim l): lanes over the K samples, partials combined by a fixed shuffle tree (deterministic) -> (d mu, d raw) in every lane
 __device__ __forceinline__ void lv_bwd_pair(const LvBwdArgs& a, long long b, int l, int lane, float& o_mu, float& o_raw) {
@@ -2186,7 +2187,13 @@ __device__ __forceinline__ void lv_bwd_pair(const LvBwdArgs& a, long long b, int
         const float e = a.eps[t * a.Lw + l], W = fmaf(e, sg, mu);
         const float dfw = a.dFn ? a.dFn[t * a.ld + a.col0 + l] : 0.f;
         const float dkl = a.w ? -a.w[t] : 0.f;                 // L_nk contains -kl (models.py:141-142)
-        if (a.sampled) { const float dW = dfw + dkl * W; dmu += dW; dsg += dW * e - dkl / sg; }
+        if (a.sampled && a.est != IWVI_LV_GRAD_IWAE) {
+            // encoder parameters held fixed inside log q: T = dfw + w (e / sigma - W), the pathwise cotangent alone; DReG weights it
+            // with the normalised importance weight once more (Tucker et al.: sum_k w~_k^2 dlog w_k/dz dz/dphi), STL leaves it as it is
+            float Tp = dfw + dkl * W - dkl * (e / sg);
+            if (a.est == IWVI_LV_GRAD_DREG) Tp *= -dkl * a.inv_unit;
+            dmu += Tp; dsg += Tp * e;
+        } else if (a.sampled) { const float dW = dfw + dkl * W; dmu += dW; dsg += dW * e - dkl / sg; }
         else { dmu += dfw + dkl * mu; dsg += dfw * e + dkl * (sg - 1.f / sg); }
     }
     for (int o = 32; o > 0; o >>= 1) { dmu += __shfl_xor(dmu, o, 64); dsg += __shfl_xor(dsg, o, 64); }
@@ -3009,13 +3016,30 @@ extern "C" int iwvi_iw_elbo_backward_dev(const float* fmean, const float* fvar, 
     return check_launch("k_elbo_bwd");
 }
 
+// the estimator arguments of the two _ex entries, refused before anything else is looked at (and before any HIP call)
+static int lv_estimator_ok(const char* fn, int estimator, double w_unit, int sampled_kl, const float* w) {
+    if (estimator < IWVI_LV_GRAD_IWAE || estimator > IWVI_LV_GRAD_STL) { set_error("%s: unknown estimator %d (IWVI_LV_GRAD_IWAE / _DREG / _STL)", fn, estimator); return IWVI_ERR_ARG; }
+    if (!(w_unit > 0.0) || !std::isfinite(w_unit)) { set_error("%s: w_unit must be finite and positive", fn); return IWVI_ERR_ARG; }
+    if (estimator != IWVI_LV_GRAD_IWAE && !sampled_kl) { set_error("%s: the DReG / STL estimators exist for the sampled regulariser only (sampled_kl = 1)", fn); return IWVI_ERR_ARG; }
+    if (estimator != IWVI_LV_GRAD_IWAE && !w) { set_error("%s: the DReG / STL estimators need the weights w", fn); return IWVI_ERR_ARG; }
+    return IWVI_OK;
+}
 extern "C" int iwvi_lv_layer_backward(const float* mu, const float* sigma, int ld_enc, int sigma_is_raw, const float* noise,
                                       const float* dF_next, int ld_next, int col0, const float* w,
                                       int latent_dim, int64_t B, int K, int sampled_kl, float* d_enc_out, void* stream_) {
+    return iwvi_lv_layer_backward_ex(mu, sigma, ld_enc, sigma_is_raw, noise, dF_next, ld_next, col0, w, latent_dim, B, K, sampled_kl,
+                                     IWVI_LV_GRAD_IWAE, 1.0, d_enc_out, stream_);
+}
+extern "C" int iwvi_lv_layer_backward_ex(const float* mu, const float* sigma, int ld_enc, int sigma_is_raw, const float* noise,
+                                         const float* dF_next, int ld_next, int col0, const float* w,
+                                         int latent_dim, int64_t B, int K, int sampled_kl, int estimator, double w_unit,
+                                         float* d_enc_out, void* stream_) {
+    int rc;
+    if ((rc = lv_estimator_ok("iwvi_lv_layer_backward", estimator, w_unit, sampled_kl, w)) != IWVI_OK) return rc;
     if (!mu || !sigma || !noise || !d_enc_out || latent_dim <= 0 || ld_enc < latent_dim || B <= 0 || K <= 0 || (dF_next && (ld_next < col0 + latent_dim || col0 < 0))) {
         set_error("iwvi_lv_layer_backward: bad argument"); return IWVI_ERR_ARG;
     }
-    LvBwdArgs a{mu, sigma, ld_enc, sigma_is_raw, noise, dF_next, ld_next, col0, w, latent_dim, B, K, sampled_kl, d_enc_out};
+    LvBwdArgs a{mu, sigma, ld_enc, sigma_is_raw, noise, dF_next, ld_next, col0, w, latent_dim, B, K, sampled_kl, d_enc_out, estimator, (float)(1.0 / w_unit)};
     hipLaunchKernelGGL(k_lv_bwd, dim3((unsigned)((B * latent_dim + 3) / 4)), dim3(256), 0, (hipStream_t)stream_, a);
     return check_launch("k_lv_bwd");
 }
@@ -3053,11 +3077,22 @@ extern "C" int iwvi_lv_encoder_backward(const float* mu, const float* sigma, int
                                         const float* XY, const float* const* enc_W, const float* const* enc_b,
                                         const int32_t* dims, int n_enc, int act,
                                         float* const* dW, float* const* db, void* ws_, void* stream_) {
+    return iwvi_lv_encoder_backward_ex(mu, sigma, ld_enc, sigma_is_raw, noise, dF_next, ld_next, col0, w, latent_dim, B, K, sampled_kl,
+                                       IWVI_LV_GRAD_IWAE, 1.0, XY, enc_W, enc_b, dims, n_enc, act, dW, db, ws_, stream_);
+}
+extern "C" int iwvi_lv_encoder_backward_ex(const float* mu, const float* sigma, int ld_enc, int sigma_is_raw, const float* noise,
+                                           const float* dF_next, int ld_next, int col0, const float* w,
+                                           int latent_dim, int64_t B, int K, int sampled_kl, int estimator, double w_unit,
+                                           const float* XY, const float* const* enc_W, const float* const* enc_b,
+                                           const int32_t* dims, int n_enc, int act,
+                                           float* const* dW, float* const* db, void* ws_, void* stream_) {
+    int rce;
+    if ((rce = lv_estimator_ok("iwvi_lv_encoder_backward", estimator, w_unit, sampled_kl, w)) != IWVI_OK) return rce;
     if (!mu || !sigma || !noise || latent_dim <= 0 || ld_enc < latent_dim || B <= 0 || K <= 0 || (dF_next && (ld_next < col0 + latent_dim || col0 < 0))) {
         set_error("iwvi_lv_encoder_backward: bad argument"); return IWVI_ERR_ARG;
     }
     if (!dims || n_enc <= 0 || n_enc > IWVI_MAX_ENC || dims[n_enc] != 2 * latent_dim) { set_error("iwvi_lv_encoder_backward: the encoder's output width must be 2 * latent_dim"); return IWVI_ERR_ARG; }
-    const LvBwdArgs lv{mu, sigma, ld_enc, sigma_is_raw, noise, dF_next, ld_next, col0, w, latent_dim, B, K, sampled_kl, nullptr};
+    const LvBwdArgs lv{mu, sigma, ld_enc, sigma_is_raw, noise, dF_next, ld_next, col0, w, latent_dim, B, K, sampled_kl, nullptr, estimator, (float)(1.0 / w_unit)};
     return enc_bwd_impl(XY, B, enc_W, enc_b, dims, n_enc, act, nullptr, &lv, dW, db, ws_, stream_);
 }
 static int enc_bwd_impl(const float* XY, int64_t rows, const float* const* enc_W, const float* const* enc_b,

@@ -69,6 +69,22 @@ class DGP_VI:
         self.keep_lv_noise = False
         self._dev_words = None
 
+    # -- the estimator of the encoder gradient (configuration, not state: no checkpoint carries it) ------------
+    # "iwae": the reparameterised gradient of the bound; "dreg" / "stl": the doubly reparameterised estimator and "sticking the landing"
+    # (include/iwvi_hip.h: IWVI_LV_GRAD_*), which exist for the sampled regulariser of DGP_IWVI only
+    ENCODER_GRADIENTS = ("iwae",)
+    _encoder_gradient = "iwae"
+
+    @property
+    def encoder_gradient(self):
+        return self._encoder_gradient
+
+    @encoder_gradient.setter
+    def encoder_gradient(self, name):
+        if name not in self.ENCODER_GRADIENTS:
+            raise ValueError("%s.encoder_gradient is one of %s, not %r" % (type(self).__name__, " | ".join(self.ENCODER_GRADIENTS), name))
+        self._encoder_gradient = name
+
     # -- data ---------------------------------------------------------------------------------
     def next_minibatch(self):
         """Advance to the next minibatch (shuffled epochs, X and Y aligned like gpflow.Minibatch)."""
@@ -725,6 +741,8 @@ class DGP_VI:
 
 
 class DGP_IWVI(DGP_VI):
+    ENCODER_GRADIENTS = ("iwae", "dreg", "stl")
+
     def _joint_over_samples(self):
         """True when some non-final GPLayer has a plain kernel and K > 1: the reference then samples that layer with the
         full [K, K] covariance over the importance samples (models.py:122-125 -> temp_workaround.py:149-155), which the

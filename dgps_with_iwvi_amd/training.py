@@ -114,6 +114,9 @@ class Trainer:
         are re-captured there anyway), so that a layer whose K_uu becomes ill-conditioned DURING training (lengthscales grow, inducing
         inputs cluster) leaves the float32 solve; captured graphs are dropped whenever a layer's route moves (``model.route_key()``).
 
+        The encoders' gradients follow ``model.encoder_gradient`` ("iwae" | "dreg" | "stl"); the estimator is an argument of the captured
+        launches, so the graphs are dropped when the setting changes between steps.
+
         ``one_factorisation`` (default on; single rank, N-layout): a step factorises every K_uu ONCE.  The natural-gradient op moves
         nothing but the final layer's q(u) (build_models.py:288-295), so the Adam op that follows it in ``step`` re-packs that layer's q(u)
         images (IWVI_GP_REUSE_FACTOR, ~5 us) instead of factorising every layer again, and the dense float64 factors its adjoints read
@@ -143,6 +146,7 @@ class Trainer:
         self.adam_t = 0
         self.use_graph, self.check_finite, self.check_every = bool(use_graph), bool(check_finite), max(1, int(check_every))
         self._graphs = {}                                      # op name -> (decay epoch, CUDAGraph, elbo tensor)
+        self._graphs_estimator = getattr(model, "encoder_gradient", "iwae")   # the estimator the captured graphs hold (a kernel argument)
         dev = model.X.device
         self._t_dev = torch.zeros(1, dtype=torch.int64, device=dev)     # Adam's step count, on the device
         ft = settings.float_type
@@ -337,6 +341,9 @@ class Trainer:
         """``model.train_op`` (build_models.py:297-300); returns the ELBO seen by the Adam op."""
         self.global_step += 1
         self._autotune_if_due()
+        est = getattr(self.model, "encoder_gradient", "iwae")
+        if est != self._graphs_estimator:                      # ``model.encoder_gradient`` moved between steps: the captured launches hold the old one
+            self._graphs, self._graphs_estimator = {}, est
         if self.use_graph:
             if zs_ng is not None or zs_adam is not None:
                 raise ValueError("use_graph draws the noise on the device (captured graphs cannot take per-step host arguments)")

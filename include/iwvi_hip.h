@@ -450,6 +450,37 @@ int iwvi_lv_encoder_backward(const float* mu, const float* sigma, int ld_enc, in
                              const int32_t* dims, int n_enc, int act,
                              float* const* dW, float* const* db, void* ws, void* stream);
 
+/* The estimator of the encoder gradient (additive at ABI 19).  With e = noise[t, l], W = mu + e sigma, dfw = dF_next[t, col0 + l] (0 when
+ * NULL) and w = w[t], the pathwise cotangent at the sample with the encoder parameters held fixed inside log q is
+ *     T = dfw + w (e / sigma - W)                     (+w e / sigma: the path through -log q;  -w W: the path through log p(W))
+ *   IWVI_LV_GRAD_IWAE  d mu += dfw - w W,       d sigma += (dfw - w W) e + w / sigma    (the reparameterised gradient of the bound)
+ *   IWVI_LV_GRAD_DREG  d mu += (w / w_unit) T,  d sigma += (w / w_unit) T e             (doubly reparameterised, Tucker et al. 2019)
+ *   IWVI_LV_GRAD_STL   d mu += T,               d sigma += T e                          ("sticking the landing", Roeder et al. 2017: biased for K > 1)
+ * then d raw = d sigma (1 - exp(-sigma)) as before.  w_unit = the weight a point's samples share (the `scale` of iwvi_iw_elbo_backward,
+ * num_data / B), so that w / w_unit is the normalised importance weight -- under K-sharding this rank's share of it, as w already is.
+ * The estimator is uniform over the launch.  IWVI_ERR_ARG before any device work: an estimator outside 0..2; DREG / STL with
+ * sampled_kl == 0 (the analytic regulariser has no such estimator) or with w == NULL; w_unit not finite or <= 0.
+ * iwvi_lv_layer_backward / iwvi_lv_encoder_backward are these with (IWVI_LV_GRAD_IWAE, 1.0). */
+enum { IWVI_LV_GRAD_IWAE = 0, IWVI_LV_GRAD_DREG = 1, IWVI_LV_GRAD_STL = 2 };
+int iwvi_lv_layer_backward_ex(const float* mu, const float* sigma, int ld_enc, int sigma_is_raw, const float* noise,
+                              const float* dF_next, int ld_next, int col0, const float* w,
+                              int latent_dim, int64_t B, int K, int sampled_kl, int estimator, double w_unit,
+                              float* d_enc_out, void* stream);
+int iwvi_lv_encoder_backward_ex(const float* mu, const float* sigma, int ld_enc, int sigma_is_raw, const float* noise,
+                                const float* dF_next, int ld_next, int col0, const float* w,
+                                int latent_dim, int64_t B, int K, int sampled_kl, int estimator, double w_unit,
+                                const float* XY, const float* const* enc_W, const float* const* enc_b,
+                                const int32_t* dims, int n_enc, int act,
+                                float* const* dW, float* const* db, void* ws, void* stream);
+
+/* Running moments of a set of float32 tensors (the gradient signal-to-noise monitor): ONE Welford update of every tensor of the table,
+ * in float64, in one launch:  c = *count_dev + 1;  d = x - mean;  mean += d / c;  m2 += d (x - mean);  then *count_dev = c (a one-thread
+ * launch behind it, as iwvi_adam_step_dev advances its step count: a captured graph stays valid from replay to replay).
+ * mean / m2 [n] start at zero with *count_dev = 0; the unbiased variance is m2 / (count - 1).  At most 48 tensors per call (the table is
+ * passed like iwvi_adam_step's); n == 0 entries are skipped.  IWVI_ERR_ARG: a null pointer, n_tensors <= 0 or beyond 48, n < 0. */
+typedef struct iwvi_moments_tensor { const float* x; double* mean; double* m2; int64_t n; } iwvi_moments_tensor;
+int iwvi_moments_update(const iwvi_moments_tensor* tensors_host, int n_tensors, int64_t* count_dev, void* stream);
+
 /* Test log-likelihood of experiments/run_conditional_density_estimation.py:148-169, batched over the test points:
  * samples: S predictive draws per point (element (s, n) at samples[s*sample_stride + n*point_stride]); y [N].
  * Gaussian KDE with Silverman's bandwidth 1.06 std S^(-1/5) (:158-162) -> out_logp [N]; squared error of the

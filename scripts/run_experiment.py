@@ -95,6 +95,8 @@ def main(argv=None):
     p.add_argument("--device_eval", action="store_true", help="evaluate on the device: fused y-samples + iwvi_sample_stats (evaluate(on_device=True))")
     p.add_argument("--kmeans", choices=("host", "device"), default="host",
                    help="where the first layer's inducing inputs are clustered: SciPy's kmeans2 on the host, or iwvi_kmeans on the device")
+    p.add_argument("--encoder_gradient", choices=("iwae", "dreg", "stl"), default="iwae",
+                   help="--mode IWAE: the estimator of the encoders' gradients (reparameterised, doubly reparameterised, sticking the landing)")
     ARGS = p.parse_args(argv)
     ARGS.fix_linear = bool(ARGS.fix_linear)
     rng = np.random.default_rng(ARGS.seed)

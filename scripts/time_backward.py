@@ -1,7 +1,8 @@
 """Wall time of one IW-ELBO value + gradient evaluation (backward.iw_elbo_and_gradients) and of one training step
 (training.Trainer.step = NatGrad op + Adam op, two gradient evaluations) at a BASELINE.json configuration.
-Usage: python scripts/time_backward.py [--config 2] [--iters 20]"""
+Usage: python scripts/time_backward.py [--config 2] [--iters 20] [--encoder_gradient iwae|dreg|stl] [--json out.json]"""
 import argparse
+import json
 import os
 import sys
 import time
@@ -21,10 +22,14 @@ def main():
     ap.add_argument("--config", type=int, default=2)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--only-gradient", action="store_true", help="time only the value+gradient evaluation (for kernel profiles)")
+    ap.add_argument("--encoder_gradient", choices=("iwae", "dreg", "stl"), default="iwae",
+                    help="the estimator of the encoders' gradients (configs with a latent-variable layer)")
+    ap.add_argument("--json", default=None, help="also write the figures to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     spec = synthetic.make_spec(**CONFIGS[a.config], seed=0)
     model = synthetic.build_model(spec, dev)
+    model.encoder_gradient = a.encoder_gradient
 
     def timed(fn, n):
         fn(); fn()
@@ -70,6 +75,10 @@ def main():
         print("graph-mode trainer failed: %s: %s" % (type(e).__name__, e))
     print("config %d: forward (fused, eager) %.3f ms | value+gradient %.3f ms (%.2e samples/s) | training step %.3f ms eager, %.3f ms as hipGraph replays (one per step: the data is not minibatched)"
           % (a.config, fwd, grad, T / grad * 1e3, step, step_g))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(dict(config=a.config, iters=a.iters, encoder_gradient=a.encoder_gradient, forward_ms=fwd, value_gradient_ms=grad,
+                           value_gradient_graph_ms=graph_ms, step_eager_ms=step, step_graph_ms=step_g), f, indent=1)
 
 
 if __name__ == "__main__":
