@@ -27,12 +27,12 @@ from . import settings  # noqa: F401
 from . import features, kernels, likelihoods, mean_functions  # noqa: F401
 from . import layers, models, temp_workaround  # noqa: F401
 from .layers import Encoder, GPLayer, LatentVariableLayer, RegularizerType  # noqa: F401
-from .models import DGP_IWVI, DGP_VI  # noqa: F401
+from .models import Bound, DGP_IWVI, DGP_VI  # noqa: F401
 from .temp_workaround import (SharedMixedMok, gauss_kl,  # noqa: F401
                               independent_multisample_sample_conditional,
                               multisample_sample_conditional)
 
 __all__ = ["settings", "features", "kernels", "likelihoods", "mean_functions", "layers", "models",
            "temp_workaround", "Encoder", "GPLayer", "LatentVariableLayer", "RegularizerType",
-           "DGP_IWVI", "DGP_VI", "SharedMixedMok", "gauss_kl",
+           "Bound", "DGP_IWVI", "DGP_VI", "SharedMixedMok", "gauss_kl",
            "independent_multisample_sample_conditional", "multisample_sample_conditional"]

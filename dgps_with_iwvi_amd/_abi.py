@@ -126,6 +126,11 @@ class MomentsTensor(ctypes.Structure):
     _fields_ = [("x", c_void_p), ("mean", c_void_p), ("m2", c_void_p), ("n", c_int64)]
 
 
+class BoundDesc(ctypes.Structure):
+    """struct iwvi_bound_desc (include/iwvi_hip.h): the bound family's triple (groups, tau = 1 - alpha, beta)."""
+    _fields_ = [("groups", ctypes.c_int32), ("tau", c_float), ("beta", c_float)]
+
+
 MOMENTS_MAX_TENSORS = 48
 LV_GRAD_IWAE, LV_GRAD_DREG, LV_GRAD_STL = 0, 1, 2              # IWVI_LV_GRAD_*
 LV_GRAD = {"iwae": LV_GRAD_IWAE, "dreg": LV_GRAD_DREG, "stl": LV_GRAD_STL}
@@ -251,6 +256,12 @@ PROTOTYPES = {
     "iwvi_logw_reduce": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, ctypes.POINTER(c_void_p),
                                  ctypes.POINTER(ctypes.c_int32), c_int, c_double, c_int, c_int,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "iwvi_bound_logw_reduce": (c_int, [ctypes.POINTER(BoundDesc), c_void_p, c_int64, c_int, c_int64, c_int64, ctypes.POINTER(c_void_p),
+                                       ctypes.POINTER(ctypes.c_int32), c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "iwvi_bound_elbo_backward": (c_int, [ctypes.POINTER(BoundDesc), c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(c_void_p),
+                                         ctypes.POINTER(ctypes.c_int32), c_int, c_int64, c_int, c_float, c_void_p, c_double,
+                                         c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_int32), c_int,
+                                         c_void_p, c_void_p, c_void_p]),
     "iwvi_iw_elbo_reduce": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int64, c_int, c_int,
                                     c_int64, c_int64,
                                     ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_int32), c_int,

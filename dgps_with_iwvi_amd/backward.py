@@ -335,9 +335,25 @@ def lv_backward(layer, XY, enc_out, eps, dF_next, col0, w, B, K, sampled_kl=True
     return dW, db
 
 
-def _checked(model, zs, mode_vi, gauss, exchange, wrt, overlap, q_moved, prepare_route, encoder_gradient="iwae"):
-    """Everything the evaluation refuses before it queues work -> (zs: per layer None or [B, K, dim], final_q, inline)."""
+def _checked(model, zs, mode_vi, gauss, exchange, wrt, overlap, q_moved, prepare_route, encoder_gradient="iwae", bound=None, K_total=None):
+    """Everything the evaluation refuses before it queues work -> (zs: per layer None or [B, K, dim], final_q, inline).
+    ``bound``: the model's ``Bound`` when it is not the default (else None): the family's heads exist for the importance-weighted bound of
+    one rank, the Gaussian likelihood and the 'iwae' estimator."""
     layers = model.layers
+    if bound is not None:
+        bound.check_samples(model.num_samples)
+        if mode_vi:
+            raise ValueError("bound %s: the bound family belongs to the importance-weighted bound; the analytic-KL bound (mode_vi, a DGP_VI) "
+                             "has the default only" % (bound,))
+        if encoder_gradient != "iwae":
+            raise ValueError("bound %s with encoder_gradient=%r: 'dreg' and 'stl' are derived for the importance-weighted bound 'iwae' only"
+                             % (bound, encoder_gradient))
+        if exchange is not None or (K_total is not None and int(K_total) != model.num_samples):
+            raise NotImplementedError("bound %s: K-sharded evaluation exchanges the importance-weighted bound's (max, sum exp) pairs; "
+                                      "sharded training has the default bound only" % (bound,))
+        if not gauss:
+            raise NotImplementedError("bound %s: the bound family has the closed-form Gaussian policy only (csrc/bound_family.hip); a %s "
+                                      "model has the default bound 'iwae'" % (bound, type(model.likelihood).__name__))
     if encoder_gradient not in _abi.LV_GRAD:
         raise ValueError("encoder_gradient is one of %s, not %r" % (" | ".join(_abi.LV_GRAD), encoder_gradient))
     if mode_vi and encoder_gradient != "iwae":
@@ -446,9 +462,10 @@ def _saving_forward(model, X, zs, mode_vi, try_fused, final_q, adj):
     return saved, fused_heads
 
 
-def _heads(model, saved, Y, mode_vi, gauss, fused_heads, exchange, K_total, cur, prep_stream, adj):
+def _heads(model, saved, Y, mode_vi, gauss, fused_heads, exchange, K_total, cur, prep_stream, adj, bound=None):
     """The bound and the heads of its adjoint -> (elbo, grads with the likelihood parameter's gradient).  ``adj`` (w [T], d_mean, d_var [T, Dy],
-    sums [3]) was filled by the layer launch (``fused_heads``) or is here; sharded, against the job's logsumexp from ``exchange``."""
+    sums [3]) was filled by the layer launch (``fused_heads``) or is here; sharded, against the job's logsumexp from ``exchange``.
+    ``bound`` (a non-default ``Bound``): ``iwvi_bound_elbo_backward`` -- w = scale d bound_n / d L_nk seeds every adjoint below."""
     B, K, dev = model.X.shape[0], model.num_samples, model.X.device
     fin = saved[-1]
     kls = [s.kl for s in saved if isinstance(s, LvSaved)]        # (only the unfused heads read them)
@@ -467,7 +484,13 @@ def _heads(model, saved, Y, mode_vi, gauss, fused_heads, exchange, K_total, cur,
         if sharding._RECORDER is not None and prep_stream != cur:
             cur.wait_stream(prep_stream)                         # a segmented capture cuts the graph at the exchange: no forked work may be left open across the cut
         lse_g = _abi.dev_tensor(exchange(ms).to(settings.float_type).contiguous(), "lse_global")
-    if not (gauss and fused_heads):
+    if bound is not None:
+        _abi.check(_abi.lib().iwvi_bound_elbo_backward(
+            bound.desc(), _abi.ptr(fin.mean), _abi.ptr(fin.var), _abi.ptr(Y), adj["d_mean"].shape[1], klp, kld, len(kls), B, K,
+            *model.likelihood.desc_variance(), float(model.num_data) / float(B), _abi.ptr(adj["w"]), _abi.ptr(adj["d_mean"]),
+            _abi.ptr(adj["d_var"]), glob_p, glob_n, len(glob), ctypes.c_void_p(adj["sums"].data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+            _abi.stream_ptr()))
+    elif not (gauss and fused_heads):
         # (the two entries differ in one place: a likelihood descriptor in front, or the Gaussian's variance behind the KLs)
         moments = (_abi.ptr(fin.mean), _abi.ptr(fin.var), _abi.ptr(Y), adj["d_mean"].shape[1], klp, kld, len(kls), B, K)
         tail = (float(model.num_data) / float(B), 1 if mode_vi else 0, _abi.ptr(adj["w"]), _abi.ptr(adj["d_mean"]), _abi.ptr(adj["d_var"]),
@@ -593,6 +616,11 @@ def iw_elbo_and_gradients(model, zs=None, mode_vi=None, exchange=None, K_total=N
     oracle/grad_oracle.py: 'l<i>.Z', 'l<i>.ls', 'l<i>.var', 'l<i>.q_mu', 'l<i>.q_sqrt', 'l<i>.W', 'l<i>.mfA' (layers with
     a mixing matrix / linear mean function), 'l<i>.encW<j>', 'l<i>.encb<j>', 'lik_var'.  ``zs``: one noise tensor per layer ([B, K, dim]) or None -> drawn.
 
+    ``model.bound`` other than ``Bound.iwae()`` (MIWAE, CIWAE, VR-alpha: models.Bound): the value is that bound and the weights that seed
+    every adjoint are its d bound_n / d L_nk; the heads come from ``iwvi_bound_elbo_backward`` on the final layer's moments (``fuse_heads``
+    is off: two launches more than the default, ``_saving_forward``), everything below them is unchanged; ``wrt="final_q"`` follows the
+    bound too.  Gaussian likelihood, one rank, ``encoder_gradient="iwae"``: anything else is refused before work is queued.
+
     A likelihood other than the Gaussian (``likelihoods.Bernoulli`` / ``StudentT`` / ``MultiClass`` / ``Poisson`` / ``Exponential`` / ``Gamma`` / ``Beta`` / ``Ordinal``): the heads never come out of the layer launch
     (``fuse_heads`` is off) but from ``iwvi_lik_elbo_backward`` on the final layer's moments; the layer adjoints are the same.  The
     likelihood's gradient is named by its ``grad_name`` ('lik_scale' for the Student-t and the Beta, 'lik_shape' for the Gamma, 'lik_sigma' for the Ordinal; the others have none).  With
@@ -607,7 +635,9 @@ def iw_elbo_and_gradients(model, zs=None, mode_vi=None, exchange=None, K_total=N
     prepare_route, branch_order = settings.backward_routes()
     if encoder_gradient is None:
         encoder_gradient = getattr(model, "encoder_gradient", "iwae")
-    zs, final_q, inline = _checked(model, zs, mode_vi, gauss, exchange, wrt, overlap, q_moved, prepare_route, encoder_gradient)
+    bound = getattr(model, "bound", None)
+    bound = None if (bound is None or bound.is_default) else bound     # (the default: every route below is the one it was)
+    zs, final_q, inline = _checked(model, zs, mode_vi, gauss, exchange, wrt, overlap, q_moved, prepare_route, encoder_gradient, bound, K_total)
     X, Y = _abi.dev_tensor(model.X.contiguous(), "X"), _abi.dev_tensor(model.Y.contiguous(), "Y")
     XY = model._xy_minibatch() if any(isinstance(l, LatentVariableLayer) for l in model.layers) else None
     cur = torch.cuda.current_stream()
@@ -615,9 +645,9 @@ def iw_elbo_and_gradients(model, zs=None, mode_vi=None, exchange=None, K_total=N
     Dy = output_dim(model.likelihood, Y.shape[1])                # (MultiClass: one column of labels against C outputs and heads)
     adj = dict(w=torch.empty(T, dtype=ft, device=dev), d_mean=torch.empty(T, Dy, dtype=ft, device=dev),
                d_var=torch.empty(T, Dy, dtype=ft, device=dev), sums=torch.empty(3, dtype=torch.float64, device=dev))
-    try_fused = fuse_heads and gauss and (not mode_vi) and exchange is None and (K_total is None or int(K_total) == K)
+    try_fused = fuse_heads and gauss and (not mode_vi) and exchange is None and (K_total is None or int(K_total) == K) and bound is None
     saved, fused_heads = _saving_forward(model, X, zs, mode_vi, try_fused, final_q, adj)
-    elbo, grads = _heads(model, saved, Y, mode_vi, gauss, fused_heads, exchange, K_total, cur, prep_stream, adj)
+    elbo, grads = _heads(model, saved, Y, mode_vi, gauss, fused_heads, exchange, K_total, cur, prep_stream, adj, bound)
     if final_q:
         return elbo, _final_q_gradients(model, saved[-1], adj, kl_weight, prefactor, cur)
     if prep_stream != cur:

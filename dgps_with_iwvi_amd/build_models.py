@@ -95,6 +95,10 @@ def build_model(ARGS, X, Y, apply_name=True, device=None):
         model = DGP_IWVI(X, Y, layers, lik, minibatch_size=ARGS.minibatch_size,
                          num_samples=ARGS.num_IW_samples, name=name)
     model.encoder_gradient = getattr(ARGS, "encoder_gradient", "iwae")     # (a DGP_VI refuses anything but "iwae")
+    # ARGS.bound: a string for models.Bound.parse ("iwae" | "miwae:4" | "ciwae:0.5" | "vr:0.3"); absent means "iwae" (a DGP_VI refuses the rest,
+    # and a DGP_IWVI checks that the groups divide num_IW_samples here, before anything is trained)
+    model.bound = getattr(ARGS, "bound", None) or "iwae"
+    model.bound.check_samples(model.num_samples)
     model = model.to(device or settings.default_device())
     if model.X.is_cuda and settings.f64_stage1 == "auto" and getattr(ARGS, "autotune_f64", True):
         # the float64 stage-1 route per layer from the measured diag(Lm) ratio of the initial values (k-means inducing inputs can

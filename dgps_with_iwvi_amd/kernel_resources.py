@@ -41,7 +41,9 @@ NO_SCRATCH = ("k_dgp_forward", "k_bw_chain", "k_sample_stats", "k_lik_elbo", "k_
               # csrc/cvae.hip: a map's weights travel in registers (32 / 64 per lane) between LDS stagings; they must stay there
               "k_cvae_rows", "k_cvae_wgrad", "k_cvae_finish", "k_cvae_sample",
               # csrc/kmeans.hip: a lane's one or two points travel in registers as float64 (up to 64 doubles per lane at D = 32)
-              "k_km_init", "k_km_step", "k_km_update")
+              "k_km_init", "k_km_step", "k_km_update",
+              # csrc/bound_family.hip: the MIWAE / CIWAE / VR-alpha reduction and heads -- segmented scans over a chunk's lanes, float64 sums
+              "k_bound_logw", "k_bound_bwd", "k_bound_finish")
 # ... except these (demangled-name substring -> bytes of scratch it is known to use; lower it when a kernel improves)
 ALLOWED_SCRATCH = {
     # round 6 (profiles/r06_kernel_resources.txt): every BIG variant (some layer with M > 128: configs[3] / [4]) and every float64-route
@@ -71,13 +73,16 @@ MAX_SPILLS = {
 # The bounded-target kernels (k_bo_*) likewise: k_bo_elbo 52-68, k_bo_elbo_bwd 68-117, k_bo_elem 34-50, k_bo_mix 68-88 (Ordinal - Beta).
 # The sampling kernel (k_lik_sample<type>, iwvi_lik_sample_y) is at the family's 128: 16-32 VGPRs for every type but the Poisson, whose
 # float64 acceptance test takes 69 (165 with the library's float64 lgamma in it, which is why log k! is a table and a Stirling series there).
+# The bound-family kernels (csrc/bound_family.hip), compiled counts rounded up to a multiple of 8: k_bound_logw 74-94, k_bound_bwd 122,
+# k_bound_finish 12.
 MAX_VGPRS = {"k_lik_elbo": 128, "k_lik_elbo_bwd": 128, "k_lik_elem": 128, "k_lik_finish": 32,
              "k_mc_elbo": 128, "k_mc_elbo_bwd": 128, "k_mc_elem": 128,
              "k_xl_elbo": 96, "k_xl_elbo_bwd": 72, "k_xl_elem": 64,
              "k_lik_mix": 128, "k_mc_mix": 128, "k_xl_mix": 96,
              "k_bo_elbo": 72, "k_bo_elbo_bwd": 120, "k_bo_elem": 56, "k_bo_mix": 88,
              "k_lik_sample": 128,
-             "k_sghmc_step": 64}
+             "k_sghmc_step": 64,
+             "k_bound_logw": 96, "k_bound_bwd": 128, "k_bound_finish": 16}
 
 
 def csrc_hash():

@@ -43,6 +43,111 @@ def _data(x):
     return t.to(dtype=settings.float_type, device=settings.default_device()).contiguous()
 
 
+class Bound:
+    """A member of the bound family between the K-sample ELBO and the importance-weighted bound (include/iwvi_hip.h: iwvi_bound_desc;
+    Rainforth et al. 2018, Li & Turner 2016).  Per data point, with the K samples in ``groups`` contiguous groups of K / groups:
+
+        bound_n = beta mean_k L_nk + (1 - beta) mean_g (1 / (1 - alpha)) [logsumexp_{k in g}((1 - alpha) L_nk) - log(K / groups)]
+
+    ``Bound.iwae()`` = (1, 0, 0) is the importance-weighted bound; ``miwae(groups)`` averages the groups' bounds, ``ciwae(beta)`` mixes the
+    ELBO in, ``vr(alpha)`` tempers the log-sum-exp.  ``parse`` reads "iwae" | "miwae:4" | "ciwae:0.5" | "vr:0.3", a "+"-joined combination
+    of them, and the ``repr`` of a Bound."""
+    __slots__ = ("groups", "alpha", "beta")
+
+    def __init__(self, groups=1, alpha=0.0, beta=0.0):
+        if isinstance(groups, bool) or int(groups) != groups or int(groups) < 1:
+            raise ValueError("Bound: groups must be an integer >= 1 (and divide num_samples), got %r" % (groups,))
+        alpha, beta = float(alpha), float(beta)
+        if not 0.0 <= alpha < 1.0 or not np.float32(1.0 - alpha) > 0:
+            raise ValueError("Bound: alpha must lie in [0, 1) (tau = 1 - alpha in (0, 1]), got %r" % (alpha,))
+        if not 0.0 <= beta <= 1.0:
+            raise ValueError("Bound: beta must lie in [0, 1], got %r" % (beta,))
+        object.__setattr__(self, "groups", int(groups))
+        object.__setattr__(self, "alpha", alpha)
+        object.__setattr__(self, "beta", beta)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a Bound is immutable: assign a new one to model.bound")
+
+    @classmethod
+    def iwae(cls):
+        return cls()
+
+    @classmethod
+    def miwae(cls, groups):
+        return cls(groups=groups)
+
+    @classmethod
+    def ciwae(cls, beta):
+        return cls(beta=beta)
+
+    @classmethod
+    def vr(cls, alpha):
+        return cls(alpha=alpha)
+
+    @classmethod
+    def parse(cls, text):
+        if isinstance(text, cls):
+            return text
+        if not isinstance(text, str):
+            raise ValueError("Bound.parse reads a string such as 'iwae', 'miwae:4', 'ciwae:0.5' or 'vr:0.3', got %r" % (text,))
+        s = text.strip()
+        if s.startswith("Bound.parse(") and s.endswith(")"):
+            s = s[len("Bound.parse("):-1].strip().strip("'\"")
+        kw = {}
+        for part in s.split("+"):
+            name, _, arg = part.strip().partition(":")
+            try:
+                if name == "iwae" and not arg:
+                    continue
+                key, val = {"miwae": ("groups", int), "ciwae": ("beta", float), "vr": ("alpha", float)}[name]
+                if key in kw:
+                    raise KeyError(name)
+                kw[key] = val(arg)
+            except (KeyError, ValueError):
+                raise ValueError("Bound.parse: %r is not 'iwae', 'miwae:<groups>', 'ciwae:<beta>' or 'vr:<alpha>' (or several joined by '+')"
+                                 % (text,)) from None
+        return cls(**kw)
+
+    @property
+    def tau(self):
+        return 1.0 - self.alpha
+
+    @property
+    def is_default(self):
+        return self.groups == 1 and self.alpha == 0.0 and self.beta == 0.0
+
+    def _key(self):
+        return (self.groups, self.alpha, self.beta)
+
+    def __eq__(self, other):
+        return isinstance(other, Bound) and self._key() == other._key()
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __str__(self):
+        parts = (["miwae:%d" % self.groups] if self.groups != 1 else []) + (["ciwae:%r" % self.beta] if self.beta else []) + \
+                (["vr:%r" % self.alpha] if self.alpha else [])
+        return "+".join(parts) or "iwae"
+
+    def __repr__(self):
+        return "Bound.parse(%r)" % str(self)
+
+    def check_samples(self, K):
+        """The point of use: the groups divide the model's K."""
+        if K % self.groups:
+            raise ValueError("bound %s: groups=%d does not divide num_samples=%d" % (self, self.groups, K))
+
+    def desc(self):
+        d = _abi.BoundDesc()
+        d.groups, d.tau, d.beta = self.groups, self.tau, self.beta
+        return d
+
+
 class DGP_VI:
     def __init__(self, X, Y, layers, likelihood, num_samples=1, minibatch_size=None, name=None):
         self.likelihood = likelihood
@@ -84,6 +189,22 @@ class DGP_VI:
         if name not in self.ENCODER_GRADIENTS:
             raise ValueError("%s.encoder_gradient is one of %s, not %r" % (type(self).__name__, " | ".join(self.ENCODER_GRADIENTS), name))
         self._encoder_gradient = name
+
+    # -- the bound (configuration, as the estimator above): DGP_IWVI alone has the family; the analytic-KL bound of this class is its own --
+    BOUND_FAMILY = False
+    _bound = Bound()
+
+    @property
+    def bound(self):
+        return self._bound
+
+    @bound.setter
+    def bound(self, value):
+        value = Bound.parse(value)
+        if not value.is_default and not self.BOUND_FAMILY:
+            raise ValueError("%s.bound: the bound family (%s) belongs to the importance-weighted DGP_IWVI; the analytic-KL bound of "
+                             "DGP_VI has the default only" % (type(self).__name__, value))
+        self._bound = value
 
     # -- data ---------------------------------------------------------------------------------
     def next_minibatch(self):
@@ -742,6 +863,11 @@ class DGP_VI:
 
 class DGP_IWVI(DGP_VI):
     ENCODER_GRADIENTS = ("iwae", "dreg", "stl")
+    # ``bound`` (a ``Bound`` or a string for ``Bound.parse``; default ``Bound.iwae()``): with the default every route is the one it was -- the
+    # fused tail, the fused heads, K-sharding --; any other member goes precompute, layer launch with its log-weights, ``iwvi_bound_logw_reduce``
+    # (``_build_likelihood`` / ``compute_log_likelihood`` / ``E_log_p_Y``, which then returns bound_n), and ``iwvi_bound_elbo_backward`` for the
+    # heads of the adjoint (backward.py).  Gaussian likelihood, one rank, the 'iwae' encoder-gradient estimator.
+    BOUND_FAMILY = True
 
     def _joint_over_samples(self):
         """True when some non-final GPLayer has a plain kernel and K > 1: the reference then samples that layer with the
@@ -788,9 +914,53 @@ class DGP_IWVI(DGP_VI):
         self.precompute(with_encoders=True)
         return self._fused_forward(B * K, K, B, (B, K), zs=zs, sampled_kl=True)[0]
 
+    def _check_bound(self, what=None):
+        """What a non-default ``bound`` refuses at the model, before anything is queued (each message names the limit)."""
+        bound = self.bound
+        bound.check_samples(self.num_samples)
+        if what is not None:
+            raise NotImplementedError("bound %s: %s" % (bound, what))
+        if not is_gaussian(self.likelihood):
+            raise NotImplementedError("bound %s: the bound family has the closed-form Gaussian policy only (csrc/bound_family.hip); a %s "
+                                      "model has the default bound 'iwae'" % (bound, type(self.likelihood).__name__))
+        if self._literal():
+            raise NotImplementedError("bound %s: the literal full_cov_over_samples path (and an inner plain-kernel GPLayer, which takes "
+                                      "it) reduces with the importance-weighted bound only" % (bound,))
+
+    def _reduce_bound(self, logw, bound, elbo_out=None, want_logp=True, want_ess=False):
+        """``iwvi_bound_logw_reduce`` on the layer launch's log-weights [B * K] -> (bound or None, bound_n [B] or None, ess [B] or None)."""
+        B, K, dev = self.X.shape[0], self.num_samples, logw.device
+        glob = [_abi.dev_tensor(g.reshape(-1), "global kl", torch.float64) for g in self._global_kls()]
+        glob_n = (ctypes.c_int32 * max(len(glob), 1))(*[g.numel() for g in glob])
+        logp = torch.empty(B, dtype=settings.float_type, device=dev) if want_logp else None
+        ess = torch.empty(B, dtype=settings.float_type, device=dev) if want_ess else None
+        elbo = None
+        if want_logp:
+            elbo = torch.empty(1, dtype=torch.float64, device=dev) if elbo_out is None else _abi.dev_tensor(elbo_out.view(-1), "elbo_out", torch.float64)
+        _abi.check(_abi.lib().iwvi_bound_logw_reduce(
+            bound.desc(), _abi.ptr(logw), B, K, K, 1, _abi.ptr_array(glob), glob_n, len(glob), float(self.num_data) / float(B),
+            _abi.ptr(logp), _abi.ptr(ess), _abi.ptr(elbo), _abi.ptr(self._words()), _abi.stream_ptr()))
+        return (None if elbo is None else elbo[0]), logp, ess
+
+    def importance_ess(self, zs=None):
+        """Kish's effective sample size of every point's K importance weights [B], in [1, K]: (sum_k w_k)^2 / sum_k w_k^2 with
+        w_k = exp(L_nk).  Over all K samples, whatever ``bound`` is (the default included).  Two launches and the reduction."""
+        logw = self._logw(zs)
+        if logw is None:
+            raise NotImplementedError("importance_ess reads the layer launch's log-weights; the literal full_cov_over_samples path has none")
+        return self._reduce_bound(logw, Bound(), want_logp=False, want_ess=True)[2]
+
     def _elbo_parts(self, zs=None, want_ms=False, K_total=None, ms_out=None, elbo_out=None):
         B, K = self.X.shape[0], self.num_samples
-        if self._literal():                                          # literal reference path, layer by layer
+        if not self.bound.is_default:
+            # precompute, the layer launch with its log-weights, iwvi_bound_logw_reduce: the fused tail holds the log-sum-exp over all K
+            self._check_bound()
+            if want_ms or ms_out is not None or K_total is not None:
+                self._check_bound("lse_partials / K_total exchange the importance-weighted bound's (max, sum exp) pairs: K-sharding has the "
+                                  "default bound only")
+            el, logp, _ = self._reduce_bound(self._logw(zs), self.bound, elbo_out=elbo_out)
+            return el, logp, None
+        if self._literal():                                         # literal reference path, layer by layer
             fmean, fvar, local_kls, global_kls, _, _, _ = self._forward_iw(zs, _last_sample=False)
             return self._reduce(fmean, fvar, self.Y, local_kls, global_kls, B, K, stride_b=K, stride_k=1,
                                 mode_vi=False, want_ms=want_ms, K_total=K_total,

@@ -114,6 +114,9 @@ class Trainer:
         are re-captured there anyway), so that a layer whose K_uu becomes ill-conditioned DURING training (lengthscales grow, inducing
         inputs cluster) leaves the float32 solve; captured graphs are dropped whenever a layer's route moves (``model.route_key()``).
 
+        ``model.bound`` (models.Bound: MIWAE, CIWAE, VR-alpha) is followed by both ops; it is a kernel argument too, so the graphs are dropped
+        when it changes between steps.  Sharded training has the default bound only.
+
         The encoders' gradients follow ``model.encoder_gradient`` ("iwae" | "dreg" | "stl"); the estimator is an argument of the captured
         launches, so the graphs are dropped when the setting changes between steps.
 
@@ -147,6 +150,7 @@ class Trainer:
         self.use_graph, self.check_finite, self.check_every = bool(use_graph), bool(check_finite), max(1, int(check_every))
         self._graphs = {}                                      # op name -> (decay epoch, CUDAGraph, elbo tensor)
         self._graphs_estimator = getattr(model, "encoder_gradient", "iwae")   # the estimator the captured graphs hold (a kernel argument)
+        self._graphs_bound = getattr(model, "bound", None)     # likewise the bound: the triple is an argument of the captured heads launch
         dev = model.X.device
         self._t_dev = torch.zeros(1, dtype=torch.int64, device=dev)     # Adam's step count, on the device
         ft = settings.float_type
@@ -234,8 +238,16 @@ class Trainer:
                                                     self._t_dev.data_ptr(), 1, _abi.stream_ptr()))
         return keep
 
+    def _refuse_sharded_bound(self):
+        """A non-default ``model.bound`` trains on one rank: refused before the minibatch advances or anything is queued."""
+        bound = getattr(self.model, "bound", None)
+        if bound is not None and not bound.is_default and (self.world > 1 or self.shard == "k" or self.group is not None):
+            raise NotImplementedError("bound %s: K- or N-sharded training has the default bound 'iwae' only (the exchange and the merged "
+                                      "gradients are those of the importance-weighted bound)" % (bound,))
+
     def _gradients(self, zs, advance=True, wrt="all", **one_factor):
         from .sharding import allreduce_gradients, k_shard_gradients
+        self._refuse_sharded_bound()
         if advance:
             self.model.next_minibatch()                          # gpflow.Minibatch: a new batch per session.run (models.py:21-26)
         if self.shard == "k":
@@ -344,6 +356,10 @@ class Trainer:
         est = getattr(self.model, "encoder_gradient", "iwae")
         if est != self._graphs_estimator:                      # ``model.encoder_gradient`` moved between steps: the captured launches hold the old one
             self._graphs, self._graphs_estimator = {}, est
+        bound = getattr(self.model, "bound", None)
+        if bound != self._graphs_bound:                        # ``model.bound`` moved: other launches (fused heads or not), another triple
+            self._graphs, self._graphs_bound = {}, bound
+        self._refuse_sharded_bound()
         if self.use_graph:
             if zs_ng is not None or zs_adam is not None:
                 raise ValueError("use_graph draws the noise on the device (captured graphs cannot take per-step host arguments)")

@@ -531,6 +531,36 @@ int iwvi_logw_reduce(const float* logw, int64_t B, int K, int64_t stride_b, int6
                      float* out_lse_ms, float* out_logp, double* out_elbo, uint64_t* ticket, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The bound family between the K-sample ELBO and the importance-weighted bound (csrc/bound_family.hip): MIWAE, CIWAE and the tempered
+ * (VR-alpha / Renyi) bound as one triple.  groups G >= 1 divides K, K_g = K / G, group g holds the contiguous samples g K_g .. (g+1) K_g - 1
+ * of the IW tiling; 0 < tau <= 1 (tau = 1 - alpha); 0 <= beta <= 1.  Per data point n:
+ *   bound_n = beta (1/K) sum_k L_nk + (1 - beta) (1/G) sum_g (1/tau) [ logsumexp_{k in g}(tau L_nk) - log K_g ]
+ *   w_nk    = d bound_n / d L_nk = beta / K + (1 - beta) / G softmax_{k' in group(k)}(tau L_nk')_k            (sum_k w_nk = 1)
+ * (1, 1, 0) is the importance-weighted bound, beta = 1 the mean over the samples (iwvi_logw_reduce with mode_vi).  Both entries return
+ * IWVI_ERR_ARG before any device work for a NULL descriptor, groups < 1 or K % groups != 0, tau outside (0, 1] or NaN, beta outside [0, 1]
+ * or NaN, and for what iwvi_logw_reduce / iwvi_iw_elbo_backward_dev refuse.  No float atomics: two calls give the same bits.
+ * ---------------------------------------------------------------------- */
+typedef struct iwvi_bound_desc { int32_t groups; float tau; float beta; } iwvi_bound_desc;
+
+/* On precomputed log-weights (row of (point b, sample k) = b*stride_b + k*stride_k), one launch.  Outputs, each may be NULL: out_logp [B] =
+ * bound_n; out_ess [B] = Kish's effective sample size (sum_k e^(L - m))^2 / sum_k e^(2 (L - m)) of the point's importance weights over ALL K
+ * samples, in [1, K], whatever the triple; out_elbo [1] = scale * sum_n bound_n - the sum of the kl_global arrays, which needs out_logp (the
+ * workgroups publish through it) and a zero-initialised ticket word, re-zeroed by the last workgroup (as iwvi_iw_elbo_reduce). */
+int iwvi_bound_logw_reduce(const iwvi_bound_desc* bound, const float* logw, int64_t B, int K, int64_t stride_b, int64_t stride_k,
+                           const double* const* kl_global_host, const int32_t* kl_global_counts_host, int n_glob, double scale,
+                           float* out_logp, float* out_ess, double* out_elbo, uint64_t* ticket, void* stream);
+
+/* The heads of the adjoint under the triple, Gaussian likelihood, IW tiling (t = b*K + k): the arguments of iwvi_iw_elbo_backward_dev
+ * without mode_vi, lse_global and K_total.  out_w [T] = scale * w_nk, d_mean / d_var [T, Dy] (any of the three may be NULL), out_sums[0] =
+ * sum_n bound_n, out_sums[1] = d bound / d lik_variance, out_sums[2] = the bound; ws: 2*B doubles. */
+int iwvi_bound_elbo_backward(const iwvi_bound_desc* bound, const float* fmean, const float* fvar, const float* Y, int Dy,
+                             const float* const* kl_local, const int32_t* kl_dims, int n_local,
+                             int64_t B, int K, float lik_variance, const float* lik_variance_dev, double scale,
+                             float* out_w, float* d_mean, float* d_var,
+                             const double* const* kl_global, const int32_t* kl_global_counts, int n_glob,
+                             double* out_sums, double* ws, void* stream);
+
+/* ------------------------------------------------------------------------
  * LatentVariableLayer forward alone (layers.py:72-105) with its Encoder MLP (:137-152).
  *   F   [T, D];  XY [T, XYdim] or NULL (prior mode, :73-81);  noise [T, Lw] or NULL (z = 0)
  *   enc_W[i] [dims[i], dims[i+1]], enc_b[i] [dims[i+1]], dims_host[n_enc+1],

@@ -5,7 +5,12 @@ parameters and after a fixed number of ``Trainer`` steps under each estimator.  
 ``norm_snr = ||mean|| / sqrt(sum var)``, and the same over all encoder tensors together ("encoder").
 
 A recorded measurement, not a threshold: whatever it shows is what README.md reports.
-Usage: python scripts/encoder_gradient_snr.py [--repeats 4096] [--steps 3000] [--out profiles/encoder_grad_snr.json] [--commit HASH]"""
+``--bound B1 B2 ...`` (models.Bound.parse: iwae | miwae:<groups> | ciwae:<beta> | vr:<alpha>) measures the bound family instead
+(profiles/bound_family_snr.json): the 'iwae' estimator throughout, each bound trained for ``--steps`` and measured at the state it trained,
+and each measured at the state 'iwae' trained; a bound whose groups do not divide K is skipped for that K and said so.
+
+Usage: python scripts/encoder_gradient_snr.py [--repeats 4096] [--steps 3000] [--out profiles/encoder_grad_snr.json] [--commit HASH]
+       python scripts/encoder_gradient_snr.py --bound iwae miwae:4 miwae:5 ciwae:0.5 vr:0.5 --Ks 20 50 --out profiles/bound_family_snr.json"""
 import argparse
 import json
 import os
@@ -32,10 +37,10 @@ def _commit():
         return "unknown (no git history here)"
 
 
-def measure(model, repeats, use_graph):
-    """{estimator: {tensor or "encoder": norm_snr, ...}} at the model's current parameters."""
+def measure(model, repeats, use_graph, estimators=ESTIMATORS):
+    """{estimator: {tensor or "encoder": norm_snr, ...}} at the model's current parameters (under the model's bound)."""
     out = {}
-    for est in ESTIMATORS:
+    for est in estimators:
         mom = backward.gradient_moments(model, repeats, encoder_gradient=est, use_graph=use_graph)
         enc = {n: m for n, m in mom.items() if ".enc" in n}
         snr = backward.snr_summary(enc)
@@ -48,6 +53,47 @@ def measure(model, repeats, use_graph):
     return out
 
 
+def _train(model, steps, use_graph):
+    """``steps`` Trainer steps -> the last step's bound (raises FloatingPointError when the run leaves the finite numbers)."""
+    tr = Trainer(model, use_graph=use_graph)
+    elbo = None
+    for _ in range(steps):
+        elbo = tr.step()
+    torch.cuda.synchronize()
+    return float(elbo)
+
+
+def bound_rows(spec, K, bounds, a, dev, use_graph):
+    """The bound family at one K -> {"trained_<bound>": {"at_own_state": ..., "bound_at_last_step": ...}, "at_iwae_state": {bound: ...}}."""
+    from dgps_with_iwvi_amd.models import Bound
+    rows, usable = {}, []
+    for text in bounds:
+        if K % Bound.parse(text).groups:
+            rows["trained_" + text] = dict(skipped="groups do not divide K = %d" % K)
+        else:
+            usable.append(text)
+    iwae_state = None
+    for text in usable:
+        settings.set_seed(a.noise_seed)
+        model = synthetic.build_model(spec, dev)
+        model.bound = text
+        try:
+            last = _train(model, a.steps, use_graph)
+        except FloatingPointError as e:
+            rows["trained_" + text] = dict(diverged=str(e))
+            continue
+        rows["trained_" + text] = dict(at_own_state=measure(model, a.repeats, use_graph, ("iwae",))["iwae"], bound_at_last_step=last)
+        if Bound.parse(text).is_default:
+            iwae_state = model
+    if iwae_state is not None:                                   # every bound's gradient at the parameters 'iwae' trained
+        rows["at_iwae_state"] = {}
+        for text in usable:
+            iwae_state.bound = text
+            rows["at_iwae_state"][text] = measure(iwae_state, a.repeats, use_graph, ("iwae",))["iwae"]
+        iwae_state.bound = "iwae"
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=4096)
@@ -58,6 +104,7 @@ def main():
     ap.add_argument("--eager", action="store_true", help="no graph replay (gradient_moments and the Trainer run eagerly)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "encoder_grad_snr.json"))
     ap.add_argument("--commit", default=None)
+    ap.add_argument("--bound", nargs="+", default=None, help="measure these bounds (the 'iwae' estimator) instead of the three estimators")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("encoder_gradient_snr.py measures on the device: no ROCm device here")
@@ -70,8 +117,24 @@ def main():
                commit=a.commit or _commit(), box=socket.gethostname(), device=torch.cuda.get_device_name(0), torch=torch.__version__,
                results={})
     t0 = time.time()
+    if a.bound:
+        res["what"] = ("norm_snr = ||mean|| / sqrt(sum var) of the encoder's gradient ('iwae' estimator) over `repeats` noise draws, per bound of "
+                       "the family: at the state that bound trained for `steps` Trainer steps (with the last step's value of THAT bound: "
+                       "different bounds, not comparable as numbers) and at the state 'iwae' trained; ONE seed")
+        res["bounds"] = list(a.bound)
     for K in a.Ks:
         spec = synthetic.make_spec(K=K, seed=a.seed, **SHAPE)
+        if a.bound:
+            rows = bound_rows(spec, K, a.bound, a, dev, use_graph)
+            res["results"]["K=%d" % K] = rows
+            for state, row in rows.items():
+                if state == "at_iwae_state":
+                    print("K=%-3d at the iwae-trained state: " % K + "  ".join("%s %.4g" % (b, r["encoder"]) for b, r in row.items()), flush=True)
+                elif "at_own_state" in row:
+                    print("K=%-3d %-20s snr %.4g  (its bound %.2f)" % (K, state, row["at_own_state"]["encoder"], row["bound_at_last_step"]), flush=True)
+                else:
+                    print("K=%-3d %-20s %s" % (K, state, row), flush=True)
+            continue
         rows = {}
         settings.set_seed(a.noise_seed)
         rows["init"] = measure(synthetic.build_model(spec, dev), a.repeats, use_graph)

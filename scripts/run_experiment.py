@@ -97,6 +97,9 @@ def main(argv=None):
                    help="where the first layer's inducing inputs are clustered: SciPy's kmeans2 on the host, or iwvi_kmeans on the device")
     p.add_argument("--encoder_gradient", choices=("iwae", "dreg", "stl"), default="iwae",
                    help="--mode IWAE: the estimator of the encoders' gradients (reparameterised, doubly reparameterised, sticking the landing)")
+    p.add_argument("--bound", default="iwae",
+                   help="--mode IWAE: the bound that is trained (models.Bound.parse): iwae | miwae:<groups> | ciwae:<beta> | vr:<alpha>; "
+                        "the groups divide --num_IW_samples; anything but iwae goes with --encoder_gradient iwae")
     ARGS = p.parse_args(argv)
     ARGS.fix_linear = bool(ARGS.fix_linear)
     rng = np.random.default_rng(ARGS.seed)

@@ -1,6 +1,6 @@
 """Wall time of one IW-ELBO value + gradient evaluation (backward.iw_elbo_and_gradients) and of one training step
 (training.Trainer.step = NatGrad op + Adam op, two gradient evaluations) at a BASELINE.json configuration.
-Usage: python scripts/time_backward.py [--config 2] [--iters 20] [--encoder_gradient iwae|dreg|stl] [--json out.json]"""
+Usage: python scripts/time_backward.py [--config 2] [--iters 20] [--encoder_gradient iwae|dreg|stl] [--bound iwae|miwae:4|ciwae:0.5|vr:0.3] [--json out.json]"""
 import argparse
 import json
 import os
@@ -24,12 +24,16 @@ def main():
     ap.add_argument("--only-gradient", action="store_true", help="time only the value+gradient evaluation (for kernel profiles)")
     ap.add_argument("--encoder_gradient", choices=("iwae", "dreg", "stl"), default="iwae",
                     help="the estimator of the encoders' gradients (configs with a latent-variable layer)")
+    ap.add_argument("--bound", default="iwae", help="the bound (models.Bound.parse): iwae | miwae:<groups> | ciwae:<beta> | vr:<alpha>; anything but "
+                                                    "iwae gives up the fused heads (two launches more per evaluation)")
     ap.add_argument("--json", default=None, help="also write the figures to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     spec = synthetic.make_spec(**CONFIGS[a.config], seed=0)
     model = synthetic.build_model(spec, dev)
     model.encoder_gradient = a.encoder_gradient
+    if a.bound != "iwae":                                     # (the default is never set: the script then also runs on a tree without the family)
+        model.bound = a.bound
 
     def timed(fn, n):
         fn(); fn()
@@ -77,7 +81,7 @@ def main():
           % (a.config, fwd, grad, T / grad * 1e3, step, step_g))
     if a.json:
         with open(a.json, "w") as f:
-            json.dump(dict(config=a.config, iters=a.iters, encoder_gradient=a.encoder_gradient, forward_ms=fwd, value_gradient_ms=grad,
+            json.dump(dict(config=a.config, iters=a.iters, encoder_gradient=a.encoder_gradient, bound=a.bound, forward_ms=fwd, value_gradient_ms=grad,
                            value_gradient_graph_ms=graph_ms, step_eager_ms=step, step_graph_ms=step_g), f, indent=1)
 
 
