@@ -38,6 +38,7 @@ ERR_ARG, ERR_LAUNCH, ERR_UNSUPPORTED = -1, -2, -3      # enum iwvi_status (inclu
 LIK_GAUSSIAN, LIK_BERNOULLI_PROBIT, LIK_STUDENT_T, LIK_MULTICLASS = 0, 1, 2, 3   # iwvi_lik_desc.type
 LIK_POISSON, LIK_EXPONENTIAL, LIK_GAMMA = 4, 5, 6                                # (exp link: csrc/likelihood_explink.hip)
 LIK_BETA, LIK_ORDINAL = 8, 9                                                     # (probit link: csrc/likelihood_bounded.hip; 7 is unassigned)
+LIK_HETERO_GAUSSIAN = 11                                                         # (csrc/likelihood_hetero.hip; 10 is unassigned)
 BW_ROUTE_CHAIN, BW_ROUTE_MID, BW_ROUTE_GEMM = 1, 2, 3   # iwvi_debug_last_backward_routes
 FW_TAIL_BOUND, FW_TAIL_DENSITY, FW_TAIL_SAMPLES = 0, 1, 2   # iwvi_debug_forward_plan
 

@@ -624,7 +624,8 @@ def iw_elbo_and_gradients(model, zs=None, mode_vi=None, exchange=None, K_total=N
     A likelihood other than the Gaussian (``likelihoods.Bernoulli`` / ``StudentT`` / ``MultiClass`` / ``Poisson`` / ``Exponential`` / ``Gamma`` / ``Beta`` / ``Ordinal``): the heads never come out of the layer launch
     (``fuse_heads`` is off) but from ``iwvi_lik_elbo_backward`` on the final layer's moments; the layer adjoints are the same.  The
     likelihood's gradient is named by its ``grad_name`` ('lik_scale' for the Student-t and the Beta, 'lik_shape' for the Gamma, 'lik_sigma' for the Ordinal; the others have none).  With
-    ``MultiClass`` Y is one column of labels and the heads are [T, C]."""
+    ``MultiClass`` Y is one column of labels and the heads are [T, C]; with ``HeteroskedasticGaussian`` Y has Dt columns and the heads are
+    [T, 2 Dt] (the means' columns, then the log noise variances')."""
     from .likelihoods import is_gaussian, output_dim
     from .models import DGP_IWVI
     dev, ft = model.X.device, settings.float_type

@@ -215,7 +215,7 @@ def attach_train_op(model, ARGS):
 def _likelihood_kind(lik):
     """The checkpoint type of a likelihood: the name of the class of likelihoods.py it is or derives from (subclasses count)."""
     from . import likelihoods
-    for kind in ("Beta", "Ordinal", "Poisson", "Exponential", "Gamma", "MultiClass", "StudentT", "Bernoulli"):
+    for kind in ("HeteroskedasticGaussian", "Beta", "Ordinal", "Poisson", "Exponential", "Gamma", "MultiClass", "StudentT", "Bernoulli"):
         if isinstance(lik, getattr(likelihoods, kind)):
             return kind
     return "Gaussian"
@@ -228,7 +228,7 @@ def likelihood_state(lik):
     if kind == "Gaussian":
         return {"likelihood.variance": np.float64(lik.variance)}
     params = {"MultiClass": lambda: [lik.num_classes, lik.epsilon], "StudentT": lambda: [lik.scale, lik.df], "Bernoulli": lambda: [],
-              "Poisson": lambda: [lik.binsize], "Exponential": lambda: [], "Gamma": lambda: [lik.shape],
+              "HeteroskedasticGaussian": lambda: [], "Poisson": lambda: [lik.binsize], "Exponential": lambda: [], "Gamma": lambda: [lik.shape],
               "Beta": lambda: [lik.scale], "Ordinal": lambda: [lik.sigma] + lik.bin_edges.tolist()}[kind]()
     return {"likelihood.type": np.str_(kind), "likelihood.params": np.array(params, dtype=np.float64)}
 

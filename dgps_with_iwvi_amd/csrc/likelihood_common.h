@@ -1,4 +1,5 @@
-// What csrc/likelihood_tail.hip, csrc/likelihood_multiclass.hip, csrc/likelihood_explink.hip and csrc/likelihood_bounded.hip share: the
+// What csrc/likelihood_tail.hip, csrc/likelihood_multiclass.hip, csrc/likelihood_explink.hip, csrc/likelihood_bounded.hip and
+// csrc/likelihood_hetero.hip (IWVI_LIK_HETERO_GAUSSIAN: HgOps, its launchers at the end of this file) share: the
 // Gauss-Hermite tables, the quadrature's variance floor, the probit link's jitter and the float64 digamma of a launch-wide parameter, the
 // kernel-argument structs of the iwvi_lik_* entry points and the segment reductions (moved here verbatim from likelihood_tail.hip), the
 // point loop of iwvi_lik_predict_mixture for the types whose outputs are independent (mix_points), the bound's reduction and the heads of its
@@ -355,6 +356,17 @@ int mc_launch_elbo_bwd(const LikBwdArgs& a, hipStream_t stream);                
 int mc_launch_elem(const char* what, int mode, const Lik& L, const float* Fmu, const float* Fvar, const float* Y, long long T, int C,
                    long long row_div, long long row_mod, float* out, float* out2, hipStream_t stream);
 int mc_launch_mix(const LikMixArgs& g, hipStream_t stream);                       // k_mc_mix<SEG>
+
+// ---- csrc/likelihood_hetero.hip (IWVI_LIK_HETERO_GAUSSIAN: no parameter; Dy = 2 Dt moments per row -- Dt means, then Dt log noise variances --,
+//      Y and every elementwise / mixture output Dt columns).  Every exponent is clipped to [-60, 60] before exp, and the heads are the gradient
+//      of the value AS COMPUTED: zero through an active clip, MultiClass's rule ----
+int hg_check_dim(int Dy, const char* what);                                       // Dy even, in 2..IWVI_MAX_P (the limit in the text)
+int hg_launch_elbo(const LikReduceArgs& g, hipStream_t stream);                   // k_hg_elbo<SEG>
+int hg_launch_elbo_bwd(const LikBwdArgs& a, hipStream_t stream);                  // k_hg_elbo_bwd (the caller launches k_lik_finish behind it)
+// mode 0: variational_expectations, 1: predict_density (Fvar == NULL: logp), 2: predict_mean_and_var (out, out2) -- all [T, Dy / 2]
+int hg_launch_elem(const char* what, int mode, const float* Fmu, const float* Fvar, const float* Y, long long T, int Dy,
+                   long long row_div, long long row_mod, float* out, float* out2, hipStream_t stream);
+int hg_launch_mix(const LikMixArgs& g, hipStream_t stream);                       // k_hg_mix<SEG>
 
 // ---- csrc/likelihood_explink.hip (IWVI_LIK_POISSON: lik.p0 = binsize; _EXPONENTIAL: no parameter; _GAMMA: lik.p0 / *lik.p0_dev = shape) ----
 inline bool xl_type(int type) { return type >= IWVI_LIK_POISSON && type <= IWVI_LIK_GAMMA; }

@@ -1,6 +1,6 @@
 // iwvi_lik_sample_y: exact draws y ~ p(y | f), f ~ N(fmean, fvar), for every likelihood of include/iwvi_hip.h -- the producer of the
 // sample sets that iwvi_sample_stats and iwvi_kde_density_grid consume.  ONE launch, elementwise over the [T, Dy] moments (MULTICLASS: one
-// lane per row of C classes), no workspace, no host synchronisation.  Definitions, loop caps and the stream: include/iwvi_hip.h, DESIGN.md section 6.
+// lane per row of C classes; HETERO_GAUSSIAN: one lane per (row, target column) of a row of 2 Dt moments), no workspace, no host synchronisation.  Definitions, loop caps and the stream: include/iwvi_hip.h, DESIGN.md section 6.
 //
 // Every loop has a fixed iteration cap (SMP_ROUNDS rounds per rejection sampler, SMP_INV_CAP steps of the Poisson inversion, n edges of the
 // Ordinal, C classes): a lane whose rounds run out takes the conditional mean, so a wave never spins whatever the moments hold.
@@ -195,17 +195,41 @@ __device__ __forceinline__ void smp_row_multiclass(const LikSampleArgs& g, long 
     g.out_y[t] = nan ? NAN : (float)y;
 }
 
+// HETERO_GAUSSIAN: one lane per (row t, target column d), e = t Dt + d its element and sub-stream.  Round 0: words (0, 1) -> z_1 (the mean's
+// normal) and eps (the target's noise), words (2, 3) -> z_2 (the log noise variance's normal).  f and g are columns d and Dt + d of the row.
+__device__ __forceinline__ void smp_row_hetero(const LikSampleArgs& g, long long e, unsigned long long serial) {
+    const int Dt = g.Dy / 2;
+    const long long t = e / Dt;
+    const int d = (int)(e - t * Dt);
+    const long long jf = t * g.Dy + d, jg = jf + Dt;
+    uint32_t w[4];
+    smp_words(smp_stream(e, g.seed, serial), 0u, w);
+    float z1, eps, z2, unused;
+    smp_normal2(w, z1, eps);
+    smp_normal2(w + 2, z2, unused);
+    float f = g.fmean[jf], lv = g.fmean[jg];
+    if (g.fvar) {
+        f = fmaf(sqrtf(fmaxf(g.fvar[jf], 0.f)), g.z_f ? g.z_f[jf] : z1, f);
+        lv = fmaf(sqrtf(fmaxf(g.fvar[jg], 0.f)), g.z_f ? g.z_f[jg] : z2, lv);
+    }
+    if (g.out_f) { g.out_f[jf] = f; g.out_f[jg] = lv; }
+    const float h = fminf(fmaxf(0.5f * lv, -60.f), 60.f);    // the exponent's clip of csrc/likelihood_hetero.hip
+    const float y = fmaf(expf(h), eps, f);
+    g.out_y[e] = (f != f || lv != lv) ? NAN : y;            // a NaN moment gives a NaN y
+}
+
 template <int TYPE>
 __global__ __launch_bounds__(256) void k_lik_sample(LikSampleArgs g) {
     // serial_dev: the low half is the serial, the high half this launch's arrival count.  Every workgroup reads the serial before it takes
     // its ticket, so before the last one advances it.
     unsigned long long serial = g.serial;
     if (g.serial_dev) serial = __hip_atomic_load(g.serial_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 0xffffffffULL;
-    const long long n = TYPE == IWVI_LIK_MULTICLASS ? g.T : g.T * g.Dy;
+    const long long n = TYPE == IWVI_LIK_MULTICLASS ? g.T : TYPE == IWVI_LIK_HETERO_GAUSSIAN ? g.T * (g.Dy / 2) : g.T * g.Dy;
     float p0 = g.lik.p0;
     if (TYPE != IWVI_LIK_ORDINAL && g.lik.p0_dev) p0 = *g.lik.p0_dev;
     for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
         if constexpr (TYPE == IWVI_LIK_MULTICLASS) smp_row_multiclass(g, e, serial);
+        else if constexpr (TYPE == IWVI_LIK_HETERO_GAUSSIAN) smp_row_hetero(g, e, serial);
         else smp_element<TYPE>(g, e, serial, p0);
     }
     if (g.serial_dev) {
@@ -238,6 +262,7 @@ extern "C" int iwvi_lik_sample_y(const iwvi_lik_desc* lik, const float* fmean, c
     int rc;
     if ((rc = take_lik(lik, g.lik, what)) != IWVI_OK) return rc;
     if (T < 0) { set_error("%s: T = %lld", what, (long long)T); return IWVI_ERR_ARG; }
+    if (g.lik.type == IWVI_LIK_HETERO_GAUSSIAN && (rc = hg_check_dim(Dy, what)) != IWVI_OK) return rc;
     if (Dy < 1 || Dy > IWVI_MAX_P) { set_error("%s: Dy = %d outside 1..%d", what, Dy, IWVI_MAX_P); return IWVI_ERR_ARG; }
     if (g.lik.type == IWVI_LIK_MULTICLASS && (rc = mc_check_classes(g.lik, Dy, what)) != IWVI_OK) return rc;
     if (!out_y) { set_error("%s: null out_y", what); return IWVI_ERR_ARG; }
@@ -256,6 +281,7 @@ extern "C" int iwvi_lik_sample_y(const iwvi_lik_desc* lik, const float* fmean, c
         case IWVI_LIK_EXPONENTIAL: return smp_launch<IWVI_LIK_EXPONENTIAL>(g, n, stream);
         case IWVI_LIK_GAMMA: return smp_launch<IWVI_LIK_GAMMA>(g, n, stream);
         case IWVI_LIK_BETA: return smp_launch<IWVI_LIK_BETA>(g, n, stream);
+        case IWVI_LIK_HETERO_GAUSSIAN: return smp_launch<IWVI_LIK_HETERO_GAUSSIAN>(g, (long long)T * (Dy / 2), stream);
         default: return smp_launch<IWVI_LIK_ORDINAL>(g, n, stream);      // (take_lik has refused every other value)
     }
 }

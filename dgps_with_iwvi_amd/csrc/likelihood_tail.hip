@@ -2,7 +2,7 @@
 // likelihood's methods as elementwise callables.  The reference passes any GPflow-1.x likelihood to its models (models.py:66,105,134);
 // the non-conjugate ones -- Bernoulli with the probit link, Student-t -- integrate by GPflow's ndiagquad: Gauss-Hermite, 20 points.
 // The entry points at the end of this file serve every type of include/iwvi_hip.h: Gaussian, Bernoulli and Student-t by the kernels here,
-// MultiClass by csrc/likelihood_multiclass.hip, Poisson / Exponential / Gamma (exp link, closed-form expectations) by csrc/likelihood_explink.hip,
+// MultiClass by csrc/likelihood_multiclass.hip, the heteroskedastic Gaussian by csrc/likelihood_hetero.hip, Poisson / Exponential / Gamma (exp link, closed-form expectations) by csrc/likelihood_explink.hip,
 // Beta / Ordinal (probit link, quadrature) by csrc/likelihood_bounded.hip.
 // The layer stack is untouched: these kernels read the final layer's moments (and the local regularisers) the layer launch left in HBM.
 #include "likelihood_common.h"   // the node tables GH_X / GH_W / GH_LOGW, LIK_V_FLOOR, LIK_JIT, Lik, the argument structs, lseg_*
@@ -322,7 +322,10 @@ int take_lik(const iwvi_lik_desc* d, Lik& L, const char* what, bool need_df2) {
             if (!(d->param[0] > 0.f)) { set_error("%s: Ordinal sigma (param[0]) must be positive, got %g", what, (double)d->param[0]); return IWVI_ERR_ARG; }
             return IWVI_OK;
         }
-        default:                                             // (7 is unassigned: include/iwvi_hip.h)
+        case IWVI_LIK_HETERO_GAUSSIAN:                       // no parameter: param[], lgc and param0_dev are ignored
+            L.p0 = 1.f; L.p1 = 0.f; L.p0_dev = nullptr;
+            return IWVI_OK;
+        default:                                             // (7 and 10 are unassigned: include/iwvi_hip.h)
             set_error("%s: unknown likelihood type %d", what, d->type); return IWVI_ERR_ARG;
     }
 }
@@ -341,6 +344,7 @@ extern "C" int iwvi_lik_elbo_reduce(const iwvi_lik_desc* lik, const float* fmean
     LikReduceArgs g{};
     int rc;
     if ((rc = take_lik(lik, g.lik, "iwvi_lik_elbo_reduce")) != IWVI_OK) return rc;
+    if (g.lik.type == IWVI_LIK_HETERO_GAUSSIAN && (rc = hg_check_dim(Dy, "iwvi_lik_elbo_reduce")) != IWVI_OK) return rc;
     if (!fmean || !fvar || !Y) { set_error("iwvi_lik_elbo_reduce: null input"); return IWVI_ERR_ARG; }
     if (B <= 0) { set_error("iwvi_lik_elbo_reduce: empty minibatch"); return IWVI_ERR_ARG; }
     if (K <= 0 || Dy <= 0) { set_error("iwvi_lik_elbo_reduce: bad K=%d or Dy=%d", K, Dy); return IWVI_ERR_ARG; }
@@ -369,6 +373,7 @@ extern "C" int iwvi_lik_elbo_reduce(const iwvi_lik_desc* lik, const float* fmean
         if ((rc = mc_check_classes(g.lik, Dy, "iwvi_lik_elbo_reduce")) != IWVI_OK) return rc;
         return mc_launch_elbo(g, stream);
     }
+    if (g.lik.type == IWVI_LIK_HETERO_GAUSSIAN) return hg_launch_elbo(g, stream);
     if (xl_type(g.lik.type)) return xl_launch_elbo(g, stream);
     if (bo_type(g.lik.type)) return bo_launch_elbo(g, stream);
     return seg_dispatch(K, [&](auto seg) {
@@ -387,6 +392,7 @@ extern "C" int iwvi_lik_elbo_backward(const iwvi_lik_desc* lik, const float* fme
     LikBwdArgs a{};
     int rc;
     if ((rc = take_lik(lik, a.lik, "iwvi_lik_elbo_backward")) != IWVI_OK) return rc;
+    if (a.lik.type == IWVI_LIK_HETERO_GAUSSIAN && (rc = hg_check_dim(Dy, "iwvi_lik_elbo_backward")) != IWVI_OK) return rc;
     if (!fmean || !fvar || !Y || !out_sums || !ws || Dy <= 0 || B <= 0 || K <= 0 || n_local < 0 || n_local > IWVI_MAX_KL ||
         n_glob < 0 || n_glob > IWVI_MAX_LAYERS) {
         set_error("iwvi_lik_elbo_backward: bad argument"); return IWVI_ERR_ARG;
@@ -409,6 +415,8 @@ extern "C" int iwvi_lik_elbo_backward(const iwvi_lik_desc* lik, const float* fme
     if (a.lik.type == IWVI_LIK_MULTICLASS) {
         if ((rc = mc_check_classes(a.lik, Dy, "iwvi_lik_elbo_backward")) != IWVI_OK) return rc;
         if ((rc = mc_launch_elbo_bwd(a, st)) != IWVI_OK) return rc;
+    } else if (a.lik.type == IWVI_LIK_HETERO_GAUSSIAN) {
+        if ((rc = hg_launch_elbo_bwd(a, st)) != IWVI_OK) return rc;
     } else if (xl_type(a.lik.type)) {
         if ((rc = xl_launch_elbo_bwd(a, st)) != IWVI_OK) return rc;
     } else if (bo_type(a.lik.type)) {
@@ -426,12 +434,15 @@ static int lik_elementwise(const char* what, const iwvi_lik_desc* lik, const flo
     Lik L{};
     int rc;
     if ((rc = take_lik(lik, L, what, MODE == 2)) != IWVI_OK) return rc;
+    if (L.type == IWVI_LIK_HETERO_GAUSSIAN && (rc = hg_check_dim(Dy, what)) != IWVI_OK) return rc;
     if (T < 0 || Dy <= 0 || row_div <= 0 || row_mod <= 0) { set_error("%s: bad size", what); return IWVI_ERR_ARG; }
     if (L.type == IWVI_LIK_MULTICLASS && (rc = mc_check_classes(L, Dy, what)) != IWVI_OK) return rc;
     if (T == 0) return IWVI_OK;
     if (!Fmu || !out || (MODE != 1 && !Fvar) || (MODE != 2 && !Y) || (MODE == 2 && !out2)) { set_error("%s: null pointer", what); return IWVI_ERR_ARG; }
     if (L.type == IWVI_LIK_MULTICLASS)
         return mc_launch_elem(what, MODE, L, Fmu, Fvar, Y, (long long)T, Dy, (long long)row_div, (long long)row_mod, out, out2, (hipStream_t)stream_);
+    if (L.type == IWVI_LIK_HETERO_GAUSSIAN)
+        return hg_launch_elem(what, MODE, Fmu, Fvar, Y, (long long)T, Dy, (long long)row_div, (long long)row_mod, out, out2, (hipStream_t)stream_);
     if (xl_type(L.type))
         return xl_launch_elem(what, MODE, L, Fmu, Fvar, Y, (long long)T, Dy, (long long)row_div, (long long)row_mod, out, out2, (hipStream_t)stream_);
     if (bo_type(L.type))
@@ -462,6 +473,20 @@ extern "C" int iwvi_lik_predict_mean_and_var(const iwvi_lik_desc* lik, const flo
         if (n < 0 || n % C != 0) { set_error("iwvi_lik_predict_mean_and_var: MultiClass takes n = T x %d elements, got %lld", C, (long long)n); return IWVI_ERR_ARG; }
         return lik_elementwise<2>("iwvi_lik_predict_mean_and_var", lik, Fmu, Fvar, nullptr, n / C, C, 1, 1, out_mean, out_var, stream_);
     }
+    if (lik && lik->type == IWVI_LIK_HETERO_GAUSSIAN) {       // n = T Dy elements of moments: rows of Dy = param[1] columns, outputs [T, Dy / 2]
+        const char* what = "iwvi_lik_predict_mean_and_var";
+        const float w = lik->param[1];
+        int rc;
+        if (!(w >= 2.f && w <= (float)IWVI_MAX_P) || w != (float)(int)w) {
+            set_error("%s: the heteroskedastic Gaussian takes the row width Dy (even, 2..%d) in param[1] here -- this entry has no Dy argument --, got %g",
+                      what, IWVI_MAX_P, (double)w);
+            return IWVI_ERR_ARG;
+        }
+        const int Dy = (int)w;
+        if ((rc = hg_check_dim(Dy, what)) != IWVI_OK) return rc;
+        if (n < 0 || n % Dy != 0) { set_error("%s: the heteroskedastic Gaussian takes n = T x %d elements, got %lld", what, Dy, (long long)n); return IWVI_ERR_ARG; }
+        return lik_elementwise<2>(what, lik, Fmu, Fvar, nullptr, n / Dy, Dy, 1, 1, out_mean, out_var, stream_);
+    }
     return lik_elementwise<2>("iwvi_lik_predict_mean_and_var", lik, Fmu, Fvar, nullptr, n, 1, 1, 1, out_mean, out_var, stream_);
 }
 
@@ -475,6 +500,7 @@ extern "C" int iwvi_lik_predict_mixture(const iwvi_lik_desc* lik, const float* f
     if ((rc = take_lik(lik, g.lik, what, out_mean != nullptr)) != IWVI_OK) return rc;
     if (N < 0) { set_error("%s: N = %lld", what, (long long)N); return IWVI_ERR_ARG; }
     if (S < 1) { set_error("%s: S = %d draws (at least 1)", what, S); return IWVI_ERR_ARG; }
+    if (g.lik.type == IWVI_LIK_HETERO_GAUSSIAN && (rc = hg_check_dim(Dy, what)) != IWVI_OK) return rc;
     if (Dy < 1 || Dy > IWVI_MAX_P) { set_error("%s: Dy = %d outside 1..%d", what, Dy, IWVI_MAX_P); return IWVI_ERR_ARG; }
     if (g.lik.type == IWVI_LIK_MULTICLASS && (rc = mc_check_classes(g.lik, Dy, what)) != IWVI_OK) return rc;
     if (stride_n < 0 || stride_s < 0) { set_error("%s: negative stride", what); return IWVI_ERR_ARG; }
@@ -487,6 +513,7 @@ extern "C" int iwvi_lik_predict_mixture(const iwvi_lik_desc* lik, const float* f
     g.N = N; g.S = S; g.Dy = Dy; g.stride_n = stride_n; g.stride_s = stride_s;
     g.logp = out_logp; g.mean = out_mean; g.var = out_var;
     if (g.lik.type == IWVI_LIK_MULTICLASS) return mc_launch_mix(g, stream);
+    if (g.lik.type == IWVI_LIK_HETERO_GAUSSIAN) return hg_launch_mix(g, stream);
     if (xl_type(g.lik.type)) return xl_launch_mix(g, stream);
     if (bo_type(g.lik.type)) return bo_launch_mix(g, stream);
     return seg_dispatch(S, [&](auto seg) {

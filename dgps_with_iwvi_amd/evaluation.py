@@ -199,12 +199,13 @@ def predictive_density_grid(model, X, levels, num_samples=10000, predict_batch_s
     with per batch of inputs one sampling launch (``predict_y_samples_fused``; layer by layer for a non-Gaussian likelihood) and one
     ``iwvi_kde_density_grid`` launch.  One output column.  ``predict_batch_size`` None: as many inputs per batch as the sampling launch's
     row budget allows, at least one, so a ``num_samples`` beyond that budget still runs."""
-    from .likelihoods import is_gaussian
+    from .likelihoods import is_gaussian, target_dim
     h = _check_bandwidth(bandwidth)
     S = int(num_samples)
     if S < (2 if h == 0.0 else 1):
         raise ValueError("num_samples=%d too small (Silverman's bandwidth needs 2)" % S)
-    if model._output_dim() != 1:
+    # (the TARGET's width: a HeteroskedasticGaussian over one target column has a final layer of two outputs)
+    if target_dim(getattr(model, "likelihood", None), model._output_dim()) != 1:
         raise ValueError("the density grid is for one output column, the model has %s" % (model._output_dim(),))
     dev = model.X.device
     X = torch.as_tensor(np.asarray(X, dtype=np.float32), device=dev) if not isinstance(X, torch.Tensor) else X.to(dev, settings.float_type)
@@ -215,7 +216,7 @@ def predictive_density_grid(model, X, levels, num_samples=10000, predict_batch_s
     if bs < 1:
         raise ValueError("predict_batch_size must be >= 1")
     out = torch.empty(N, levels.shape[-1], dtype=settings.float_type, device=dev)
-    fused = is_gaussian(model.likelihood)
+    fused = is_gaussian(getattr(model, "likelihood", None))
     for lo in range(0, N, bs):
         x = X[lo:lo + bs]
         smp = (model.predict_y_samples_fused(x, S, batch_size=bs) if fused else model.predict_y_samples(x, S))[:, :, 0]    # [S, n]

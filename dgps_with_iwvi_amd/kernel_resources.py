@@ -4,7 +4,7 @@ The layer kernel's hot variants sit at the 256-VGPR limit: a source change anywh
 scratch, and a variant that only the large configs take then regresses unnoticed (round 4: the five-sub-tile large-M variant went
 216 B into scratch, configs[3] 1.27 -> 1.43 ms, for four commits).  ``check()`` is run by ``__graft_entry__.build()`` and by
 tests/test_kernel_resources.py: it fails when a ``k_dgp_forward`` or ``k_bw_chain`` instantiation (the predictive and sampling variants of the
-forward included), ``k_sample_stats``, ``k_kde_grid`` or a likelihood-tail kernel (every ``k_lik_*``, ``k_mc_*``, ``k_xl_*``, ``k_bo_*``, the ``*_mix`` kernels of the predictive mixture and the sampling kernel ``k_lik_sample`` included) the SGHMC update ``k_sghmc_step``, a CVAE kernel (``k_cvae_*``) or a k-means kernel (``k_km_*``) uses scratch memory
+forward included), ``k_sample_stats``, ``k_kde_grid`` or a likelihood-tail kernel (every ``k_lik_*``, ``k_mc_*``, ``k_xl_*``, ``k_bo_*``, ``k_hg_*``, the ``*_mix`` kernels of the predictive mixture and the sampling kernel ``k_lik_sample`` included) the SGHMC update ``k_sghmc_step``, a CVAE kernel (``k_cvae_*``) or a k-means kernel (``k_km_*``) uses scratch memory
 (``.private_segment_fixed_size`` > 0) beyond what ``ALLOWED_SCRATCH`` lists, when a listed spill count grows, or when a kernel listed in ``MAX_VGPRS`` exceeds its VGPR ceiling.
 
   python -m dgps_with_iwvi_amd.kernel_resources [--write profiles/<tag>_kernel_resources.txt]
@@ -36,6 +36,7 @@ NO_SCRATCH = ("k_dgp_forward", "k_bw_chain", "k_sample_stats", "k_lik_elbo", "k_
               "k_mc_elbo", "k_mc_elbo_bwd", "k_mc_elem", "k_xl_elbo", "k_xl_elbo_bwd", "k_xl_elem",
               "k_lik_mix", "k_mc_mix", "k_xl_mix",
               "k_bo_elbo", "k_bo_elbo_bwd", "k_bo_elem", "k_bo_mix",
+              "k_hg_elbo", "k_hg_elbo_bwd", "k_hg_elem", "k_hg_mix",   # csrc/likelihood_hetero.hip: closed forms; the density's twenty nodes unrolled
               "k_lik_sample",          # csrc/likelihood_sample.hip: the type a template argument; rejection loops whose lanes leave at different rounds
               "k_sghmc_step",         # csrc/sghmc.hip: the sampler's update, replayed 10 000 times per evaluation (56 VGPRs today)
               # csrc/cvae.hip: a map's weights travel in registers (32 / 64 per lane) between LDS stagings; they must stay there
@@ -71,6 +72,8 @@ MAX_SPILLS = {
 # k_xl_elem 37-63, k_xl_mix 95; k_xl_elbo_bwd 65 when the ceiling was set, 54 today) rounded up to a multiple of 8, so a change that costs them
 # a wave of occupancy shows.
 # The bounded-target kernels (k_bo_*) likewise: k_bo_elbo 52-68, k_bo_elbo_bwd 68-117, k_bo_elem 34-50, k_bo_mix 68-88 (Ordinal - Beta).
+# The heteroskedastic-Gaussian kernels (k_hg_*) likewise, compiled counts rounded up to a multiple of 8: k_hg_elbo 56, k_hg_elbo_bwd 50,
+# k_hg_elem 34-63 (the log-space density), k_hg_mix 111-116 (that density inside the point loop with its float64 sums).
 # The sampling kernel (k_lik_sample<type>, iwvi_lik_sample_y) is at the family's 128: 16-32 VGPRs for every type but the Poisson, whose
 # float64 acceptance test takes 69 (165 with the library's float64 lgamma in it, which is why log k! is a table and a Stirling series there).
 # The bound-family kernels (csrc/bound_family.hip), compiled counts rounded up to a multiple of 8: k_bound_logw 74-94, k_bound_bwd 122,
@@ -80,6 +83,7 @@ MAX_VGPRS = {"k_lik_elbo": 128, "k_lik_elbo_bwd": 128, "k_lik_elem": 128, "k_lik
              "k_xl_elbo": 96, "k_xl_elbo_bwd": 72, "k_xl_elem": 64,
              "k_lik_mix": 128, "k_mc_mix": 128, "k_xl_mix": 96,
              "k_bo_elbo": 72, "k_bo_elbo_bwd": 120, "k_bo_elem": 56, "k_bo_mix": 88,
+             "k_hg_elbo": 56, "k_hg_elbo_bwd": 56, "k_hg_elem": 64, "k_hg_mix": 120,
              "k_lik_sample": 128,
              "k_sghmc_step": 64,
              "k_bound_logw": 96, "k_bound_bwd": 128, "k_bound_finish": 16}

@@ -16,6 +16,9 @@ scalars: (gradient name, value), or None).
 layer: ``Y`` is ONE column of class labels 0 .. C-1 while the layer has C outputs.  Nothing equates the two widths directly: ``target_dim``
 / ``output_dim`` below translate, and a likelihood says which it is by a ``num_classes`` attribute.
 
+``HeteroskedasticGaussian`` (``csrc/likelihood_hetero.hip``) is the other one: TWO outputs of the final layer per target column, the mean
+and the log noise variance (``outputs_per_target = 2``).  Closed-form expectations like the exp-link three; nothing is trained.
+
 ``Poisson``, ``Exponential`` and ``Gamma`` (exp link, GPflow's default; ``csrc/likelihood_explink.hip``) have closed-form variational
 expectations -- one ``exp`` per element, no quadrature --; ``Gamma.shape`` is the one trained scalar (``grad_name`` 'lik_shape').
 
@@ -32,14 +35,29 @@ from .kernels import DeviceScalarVariance
 
 
 def target_dim(likelihood, Dy):
-    """Columns of Y for a final layer of ``Dy`` outputs: 1 for a likelihood over class labels (``num_classes``), else ``Dy``."""
-    return 1 if getattr(likelihood, "num_classes", None) is not None else Dy
+    """Columns of Y for a final layer of ``Dy`` outputs: 1 for a likelihood over class labels (``num_classes``), ``Dy / outputs_per_target``
+    for one with several latent functions per target column (``HeteroskedasticGaussian``: 2), else ``Dy``."""
+    if getattr(likelihood, "num_classes", None) is not None:
+        return 1
+    per = getattr(likelihood, "outputs_per_target", 1)
+    return Dy if per == 1 or Dy is None else Dy // per
 
 
 def output_dim(likelihood, y_dim):
     """The other way round: outputs of the final layer (columns of its moments and of the heads) for targets of ``y_dim`` columns."""
     C = getattr(likelihood, "num_classes", None)
-    return y_dim if C is None else C
+    return y_dim * getattr(likelihood, "outputs_per_target", 1) if C is None else C
+
+
+def predictive_dim(likelihood, Dy):
+    """Columns of ``predict_mean_and_var`` (and of a predictive mixture's mean / var) for a final layer of ``Dy`` outputs: one per class
+    for ``MultiClass``, otherwise one per target column."""
+    return Dy if getattr(likelihood, "num_classes", None) is not None else target_dim(likelihood, Dy)
+
+
+def desc_target_dim(desc, Dy):
+    """``target_dim`` from a descriptor alone (``sample_y_launch``)."""
+    return 1 if desc.type == _abi.LIK_MULTICLASS else Dy // 2 if desc.type == _abi.LIK_HETERO_GAUSSIAN else Dy
 
 
 def _moments(Fmu, Fvar, Y, likelihood=None):
@@ -56,11 +74,11 @@ def _moments(Fmu, Fvar, Y, likelihood=None):
 
 def sample_y_launch(desc, Fmu, Fvar, z_f=None, return_f=False, seed=None, serial=None):
     """One ``iwvi_lik_sample_y`` launch on contiguous device moments [..., Dy] for the descriptor ``desc`` -> y [..., Dt] (Dt = 1 for the
-    MultiClass, else Dy), or (y, f) with ``return_f``."""
+    MultiClass, Dy / 2 for the heteroskedastic Gaussian, else Dy), or (y, f) with ``return_f``."""
     Fmu, Fvar, _, T, Dy = _moments(Fmu, Fvar, None)
     if z_f is not None:
         z_f = _abi.dev_tensor(torch.as_tensor(z_f, device=Fmu.device).expand_as(Fmu).contiguous(), "z_f")
-    Dt = 1 if desc.type == _abi.LIK_MULTICLASS else Dy
+    Dt = desc_target_dim(desc, Dy)
     out_y = torch.empty(*Fmu.shape[:-1], Dt, dtype=Fmu.dtype, device=Fmu.device) if Fmu.dim() else torch.empty_like(Fmu)
     out_f = torch.empty_like(Fmu) if return_f else None
     if Fmu.numel() == 0:                                             # (an empty tensor has no address to hand over: nothing to launch)
@@ -77,7 +95,8 @@ class _SampleY:
 
     def sample_y(self, Fmu, Fvar, z_f=None, return_f=False, seed=None, serial=None):
         """y ~ p(y | f), f = Fmu + sqrt(Fvar) z (``Fvar`` None: f = Fmu), elementwise on device moments [..., Dy] -> [..., Dy] (MultiClass:
-        [..., 1] labels).  ``z_f``: the standard normals of f, drawn when None; ``return_f``: also the f that was used.  The noise is the
+        [..., 1] labels; HeteroskedasticGaussian: [..., Dy / 2], with ``z_f`` / ``return_f`` [..., Dy] covering the mean and the log noise
+        variance).  ``z_f``: the standard normals of f, drawn when None; ``return_f``: also the f that was used.  The noise is the
         sub-stream (``seed``, ``serial``) per element: ``settings.seed`` and the next serial of ``settings.next_sample_serial`` by default,
         the same pair gives the same bits."""
         return sample_y_launch(self.lik_desc(), Fmu, Fvar, z_f=z_f, return_f=return_f, seed=seed, serial=serial)
@@ -329,6 +348,73 @@ class MultiClass(_SampleY):
             raise ValueError("MultiClass(%d): the moments need %d columns, got %d" % (self.num_classes, self.num_classes, C))
         m, v = torch.empty_like(Fmu), torch.empty_like(Fmu)
         _abi.check(_abi.lib().iwvi_lik_predict_mean_and_var(self.lik_desc(), _abi.ptr(Fmu), _abi.ptr(Fvar), Fmu.numel(), _abi.ptr(m), _abi.ptr(v),
+                                                            _abi.stream_ptr()))
+        return m, v
+
+
+class HeteroskedasticGaussian(_SampleY):
+    """A Gaussian whose noise variance is a second latent function of the input (GPflow 2's ``HeteroskedasticTFPConditional`` with the exp
+    link; ``csrc/likelihood_hetero.hip``).  For Dt target columns the final layer has 2 Dt outputs: columns 0 .. Dt-1 are the mean function
+    f, columns Dt .. 2 Dt-1 are g, the LOG NOISE VARIANCE of the same target column; ``Y`` and every result below are [..., Dt] against
+    moments [..., 2 Dt].  ``logp`` = -1/2 log 2 pi - g / 2 - (Y - f)^2 exp(-g) / 2; ``variational_expectations`` is the closed form
+    -1/2 log 2 pi - m_g / 2 - ((Y - m_f)^2 + v_f) exp(-m_g + v_g / 2) / 2; ``predict_mean_and_var`` = (m_f, v_f + exp(m_g + v_g / 2));
+    ``predict_density`` integrates N(Y; m_f, v_f + exp(g)) over g by the 20-point rule, in log space.  Every exponent is clipped to
+    [-60, 60].  No parameter, nothing is trained."""
+    outputs_per_target = 2
+
+    def __init__(self, name=None):
+        self.name = name
+
+    def lik_desc(self):
+        d = _abi.LikDesc()
+        d.type = _abi.LIK_HETERO_GAUSSIAN
+        return d
+
+    grad_name = None
+
+    def trained_scalar(self):
+        return None
+
+    def check_targets(self, Y):
+        """Any finite real (the models call this once on the host when they are built)."""
+        import numpy as np
+        Yh = _host_targets(Y)
+        _refuse_targets("HeteroskedasticGaussian", "finite", Yh, ~np.isfinite(Yh))
+
+    def check_output_dim(self, Dy):
+        """The final layer must have two outputs per target column (the models call this when they are built)."""
+        if Dy is None or int(Dy) != Dy or Dy < 2 or Dy % 2 or Dy > _abi.MAX_P:
+            raise ValueError("HeteroskedasticGaussian needs a final layer with an even number of outputs in 2..%d (the means, then the log "
+                             "noise variances), got %s" % (_abi.MAX_P, Dy))
+
+    def _rows(self, entry, Fmu, Fvar, Y):
+        Fmu, Fvar, Y, T, Dy = _moments(Fmu, Fvar, Y, self)
+        self.check_output_dim(Dy)
+        out = torch.empty(*Fmu.shape[:-1], Dy // 2, dtype=Fmu.dtype, device=Fmu.device)
+        if Fmu.numel() == 0:
+            return out
+        _abi.check(getattr(_abi.lib(), entry)(self.lik_desc(), _abi.ptr(Fmu), _abi.ptr(Fvar), _abi.ptr(Y), T, Dy, 1, max(T, 1), _abi.ptr(out),
+                                              _abi.stream_ptr()))
+        return out
+
+    def variational_expectations(self, Fmu, Fvar, Y):
+        return self._rows("iwvi_lik_var_exp", Fmu, Fvar, Y)
+
+    def logp(self, F, Y):
+        return self._rows("iwvi_lik_predict_density", F, None, Y)
+
+    def predict_density(self, Fmu, Fvar, Y):
+        return self._rows("iwvi_lik_predict_density", Fmu, Fvar, Y)
+
+    def predict_mean_and_var(self, Fmu, Fvar):
+        Fmu, Fvar, _, _, Dy = _moments(Fmu, Fvar, None)
+        self.check_output_dim(Dy)
+        m, v = (torch.empty(*Fmu.shape[:-1], Dy // 2, dtype=Fmu.dtype, device=Fmu.device) for _ in range(2))
+        if Fmu.numel() == 0:
+            return m, v
+        d = self.lik_desc()
+        d.param[1] = float(Dy)                                    # (the one entry without a Dy argument reads the row width here)
+        _abi.check(_abi.lib().iwvi_lik_predict_mean_and_var(d, _abi.ptr(Fmu), _abi.ptr(Fvar), Fmu.numel(), _abi.ptr(m), _abi.ptr(v),
                                                             _abi.stream_ptr()))
         return m, v
 

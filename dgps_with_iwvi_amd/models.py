@@ -12,7 +12,8 @@ to finish does the log-sum-exp over K, the scaled sum and subtracts the global K
 A likelihood other than the Gaussian (``likelihoods.Bernoulli`` / ``StudentT`` / ``MultiClass`` / ``Poisson`` / ``Exponential`` / ``Gamma`` / ``Beta`` / ``Ordinal``) takes THREE: the layer launch runs without its tail and leaves
 the final layer's moments and the local regularisers, ``iwvi_lik_elbo_reduce`` does the rest (Gauss-Hermite variational expectations -- closed
 forms for the exp-link three --, the log-sum-exp, the bound).  For a Gaussian nothing differs from the two-launch form.  ``MultiClass`` alone has targets narrower than the
-final layer -- Y is one column of class labels, the layer has one output per class --: ``likelihoods.target_dim`` / ``output_dim`` translate.
+final layer -- Y is one column of class labels, the layer has one output per class --: ``likelihoods.target_dim`` / ``output_dim`` translate;
+``HeteroskedasticGaussian`` has two outputs (mean, log noise variance) per target column and goes through the same two functions.
 ``predict_mixture`` evaluates a trained model of any likelihood the same way: the layer launch, then one ``iwvi_lik_predict_mixture`` launch gives
 the mean, variance and log density of the Monte Carlo predictive mixture over S draws (``predict_log_density`` of a non-Gaussian model is its density).
 
@@ -34,7 +35,7 @@ import torch
 
 from . import _abi, settings
 from .layers import GPLayer, LatentVariableLayer, RegularizerType
-from .likelihoods import is_gaussian, output_dim, target_dim
+from .likelihoods import is_gaussian, output_dim, predictive_dim, target_dim
 from .temp_workaround import draw_normal, precompute_states
 
 
@@ -154,7 +155,7 @@ class DGP_VI:
         if hasattr(likelihood, "check_targets"):                      # (a Bernoulli refuses labels other than 0 / 1 here, once, on the host)
             likelihood.check_targets(Y)
         self.layers = list(layers)
-        if hasattr(likelihood, "check_output_dim"):                   # (MultiClass: one output of the final layer per class)
+        if hasattr(likelihood, "check_output_dim"):                   # (MultiClass: one output per class; HeteroskedasticGaussian: an even number)
             likelihood.check_output_dim(self._output_dim() if self.layers else None)
         self.num_data = X.shape[0]                                    # models.py:18
         self.num_samples = num_samples
@@ -523,7 +524,7 @@ class DGP_VI:
                 want_ms=False, K_total=None, ms_out=None, elbo_out=None):
         """``iwvi_iw_elbo_reduce`` on explicit final-layer moments (the layer-by-layer path)."""
         dev = fmean.device
-        Dy = output_dim(self.likelihood, Y.shape[-1])                # (MultiClass: Y is one column of labels, the moments have C)
+        Dy = output_dim(self.likelihood, Y.shape[-1])                # (MultiClass: Y is one column of labels, the moments have C; hetero: 2 per column)
         fmean = _abi.dev_tensor(fmean.contiguous(), "final mean")
         fvar = _abi.dev_tensor(fvar.contiguous(), "final var")
         Y = _abi.dev_tensor(Y.contiguous(), "Y")
@@ -724,7 +725,8 @@ class DGP_VI:
             raise ValueError("predict_mixture: the Student-t variance needs df > 2 (df = %g); predict_log_density gives the density alone" % desc.param[1])
         res = {}
         if _moments:
-            res["mean"], res["var"] = (torch.empty(N, Dy, dtype=settings.float_type, device=dev) for _ in range(2))
+            Dm = predictive_dim(self.likelihood, Dy)                 # (HeteroskedasticGaussian: one column per TARGET, half the layer's width)
+            res["mean"], res["var"] = (torch.empty(N, Dm, dtype=settings.float_type, device=dev) for _ in range(2))
         if Y is not None:
             res["log_density"] = torch.empty(N, dtype=settings.float_type, device=dev)
         if N == 0:
@@ -802,7 +804,7 @@ class DGP_VI:
     def predict_y_draws(self, X, S, zs=None, z_f=None, batch_size=None, return_f=False, serial=None):
         """EXACT draws of the predictive targets [S, N, Dt] for any likelihood: y ~ p(y | f), f ~ N(m_s, v_s) over S draws through the inner
         layers (drawn as in ``predict_f_multisample``; ``zs``: one [S, N, dim] array or None per layer) -- counts for a Poisson, labels for
-        a Bernoulli / Ordinal / MultiClass (Dt = 1 there, else Dt = Dy), heavy tails for a Student-t --, where ``predict_y_samples`` stays
+        a Bernoulli / Ordinal / MultiClass (Dt = 1 there; Dt = Dy / 2 for a HeteroskedasticGaussian; else Dt = Dy), heavy tails for a Student-t --, where ``predict_y_samples`` stays
         the reference's moment-matched ``m + z sqrt(v)``.  Per batch of ``batch_size`` points: one precompute, the layer launch without a
         tail (the final layer's moments, rows n S + s) and ONE ``iwvi_lik_sample_y`` launch on them.  ``z_f`` [S, N, Dy]: the standard
         normals of f (drawn when None); ``return_f``: also the f that was used, [S, N, Dy].  Both results are transposed views of

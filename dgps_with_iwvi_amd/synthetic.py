@@ -82,6 +82,31 @@ def make_spec(L=2, M=128, B=1024, K=20, Dx=8, Dy=1, R=5, with_lv=False, seed=0, 
                 name="L%d_M%d_K%d_B%d%s" % (L, M, K, B, "_LV" if with_lv else ""))
 
 
+def hetero_noise_sd(X):
+    """The noise standard deviation of ``make_hetero_spec``'s targets at inputs X [n, Dx]: 0.05 on the far left of the first input
+    column, 0.65 on the far right (a logistic ramp), whatever the other columns hold."""
+    return 0.05 + 0.6 / (1.0 + np.exp(-3.0 * np.asarray(X, dtype=np.float64)[:, 0]))
+
+
+def make_hetero_spec(L=2, M=16, B=64, K=5, Dx=2, with_lv=False, seed=0, n_data=None, parity=False):
+    """A spec for ``likelihoods.HeteroskedasticGaussian``: ``make_spec`` with a final layer of Dy = 2 outputs (mean, log noise variance)
+    and ONE target column whose noise standard deviation depends on x, y = sin(2 x_0) + hetero_noise_sd(x) eps.  The encoder of a leading
+    latent-variable layer is narrowed to its [x, y] input of width Dx + 1.  ``build_model(spec, likelihood=HeteroskedasticGaussian())``
+    builds the model."""
+    spec = make_spec(L=L, M=M, B=B, K=K, Dx=Dx, Dy=2, with_lv=with_lv, seed=seed, n_data=n_data, parity=parity)
+    rng = np.random.default_rng([seed, 0x6865746f])
+    X = spec["X"]
+    spec["Y"] = _f32(np.sin(2.0 * X[:, :1]) + hetero_noise_sd(X)[:, None] * rng.standard_normal((X.shape[0], 1)))
+    spec["lik_var"] = 1.0                                          # (read by nothing here: the likelihood has no parameter)
+    if with_lv:
+        l0 = spec["layers"][0]
+        h = l0["dims"][1]
+        l0["dims"] = [Dx + 1] + list(l0["dims"][1:])
+        l0["enc_W"] = [_f32(rng.standard_normal((Dx + 1, h)) * (2.0 / (Dx + 1 + h)) ** 0.5)] + list(l0["enc_W"][1:])
+    spec["name"] += "_hetero"
+    return spec
+
+
 def make_noise(spec, seed=1, K=None, B=None):
     """One N(0,1) array per layer in the IW layout ([B,K,latent] for LV, [B,K,R] for GP layers)."""
     rng = np.random.default_rng(seed)

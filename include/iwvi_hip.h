@@ -810,10 +810,38 @@ int iwvi_kmeans(const float* X, int64_t N, int D, const float* Z_init, int M, in
  *                          accuracy at any distance from the bin.  A label outside 0 .. n is read as the nearest bin.
  *              IWVI_ERR_ARG (with iwvi_last_error) before any launch: BETA with param[0] <= 0 or NaN; ORDINAL with param[1] not an integer
  *              in 1..31, with param0_dev == NULL, or with param[0] <= 0 or NaN.
+ *
+ *   HETERO_GAUSSIAN   a Gaussian whose noise variance is a second latent function of the input (GPflow 2's heteroskedastic likelihood with the
+ *              exp link; csrc/likelihood_hetero.hip).  Its value is 11: 7 and 10 are UNASSIGNED and refused as unknown types.  For Dt target
+ *              columns the moments have Dy = 2 Dt columns per row: columns 0 .. Dt-1 are the mean function f, columns Dt .. 2 Dt-1 are g, the
+ *              LOG NOISE VARIANCE of the same target column.  Like MULTICLASS its targets are narrower than its moments: wherever an entry
+ *              point takes Dy, Y has Dy / 2 columns ([B, Dy/2]; [rows, Dy/2] for the elementwise entries), and every entry refuses a Dy that
+ *              is odd, below 2 or above IWVI_MAX_P.  No parameter: param[], lgc and param0_dev are ignored (one exception, below), nothing is
+ *              trained, out_sums[1] = 0.  Per target column, with (m_f, v_f) and (m_g, v_g) the moments of its two outputs:
+ *                logp(F, Y)              = -1/2 log 2pi - g/2 - (y - f)^2 exp(-g) / 2
+ *                variational expectation = -1/2 log 2pi - m_g/2 - ((y - m_f)^2 + v_f) r / 2,   r = exp(a),  a = -m_g + v_g/2     (closed form)
+ *                heads, q = (y - m_f)^2 + v_f:  dE/dm_f = (y - m_f) r,  dE/dv_f = -r/2,  dE/dm_g = -1/2 + q r / 2,  dE/dv_g = -q r / 4
+ *                predict_mean_and_var    = (m_f, v_f + exp(m_g + v_g/2))                                      (the exact moments)
+ *                predict_density         = log int N(y; m_f, v_f + exp(g)) N(g; m_g, v_g) dg by the 20-point rule above over g, in log
+ *                                          space: log sum_i exp(log N(y; m_f, v_f + exp(g_i)) + log w_i), g_i = m_g + sqrt(2 max(v_g, 1e-8)) x_i
+ *                                          (Fvar == NULL: logp(Fmu, Y))
+ *                mixture over S draws    mean: the average of m_f; variance: the average of v_f + exp(m_g + v_g/2) + m_f^2 minus the mean
+ *                                          squared; log density: logsumexp_s sum_d predict_density_s - log S
+ *                sample_y                f = m_f + sqrt(v_f) z_1,  g = m_g + sqrt(v_g) z_2,  y = f + exp(g/2) eps
+ *              THE CLIP: every exponent (a, -g, m_g + v_g/2, the nodes g_i, g/2) is clipped to [-60, 60] before exp, so float32 cannot
+ *              overflow.  The heads are the gradient of the value AS COMPUTED: through an active clip (|a| > 60) the derivative is zero --
+ *              the m_g / v_g parts through r vanish (dE/dm_g = -1/2, dE/dv_g = 0) while dE/dm_f and dE/dv_f keep the clipped r --, as for
+ *              MULTICLASS.  The outputs of iwvi_lik_var_exp, iwvi_lik_predict_density, iwvi_lik_predict_mean_and_var and the out_mean /
+ *              out_var of iwvi_lik_predict_mixture are [., Dy/2]; d_mean, d_var of iwvi_lik_elbo_backward, z_f and out_f of
+ *              iwvi_lik_sample_y are [., Dy] (z_f supplies z_1 in column d and z_2 in column Dy/2 + d); out_y of iwvi_lik_sample_y is
+ *              [T, Dy/2].  Targets: any finite real.
+ *              The exception: iwvi_lik_predict_mean_and_var has no Dy argument, so for this type it reads the row width Dy from param[1]
+ *              (as MULTICLASS's C), takes n = T Dy elements of moments and writes [T, Dy/2] twice.
  * ---------------------------------------------------------------------- */
 enum { IWVI_LIK_GAUSSIAN = 0, IWVI_LIK_BERNOULLI_PROBIT = 1, IWVI_LIK_STUDENT_T = 2, IWVI_LIK_MULTICLASS = 3,
        IWVI_LIK_POISSON = 4, IWVI_LIK_EXPONENTIAL = 5, IWVI_LIK_GAMMA = 6, /* 7: unassigned, refused as unknown */
-       IWVI_LIK_BETA = 8, IWVI_LIK_ORDINAL = 9 };
+       IWVI_LIK_BETA = 8, IWVI_LIK_ORDINAL = 9, /* 10: unassigned, refused as unknown */
+       IWVI_LIK_HETERO_GAUSSIAN = 11 };
 typedef struct iwvi_lik_desc {
     int32_t type;
     float param[2];
@@ -822,7 +850,8 @@ typedef struct iwvi_lik_desc {
 } iwvi_lik_desc;
 
 /* iwvi_iw_elbo_reduce_dev with a likelihood descriptor in place of lik_variance: the variational expectation of every (point, sample,
- * output) by the rule above, everything else -- strides, regularisers, ticket, optional outputs, ONE launch -- as documented there. */
+ * output) by the rule above, everything else -- strides, regularisers, ticket, optional outputs, ONE launch -- as documented there.
+ * HETERO_GAUSSIAN: Dy = 2 Dt is the width of the moments, Y is [B, Dy / 2]; the expectation is its closed form, summed over the Dt columns. */
 int iwvi_lik_elbo_reduce(const iwvi_lik_desc* lik, const float* fmean, const float* fvar, const float* Y,
                          int64_t B, int K, int Dy, int64_t stride_b, int64_t stride_k,
                          const float* const* kl_local_host, const int32_t* kl_dims_host, int n_kl,
@@ -832,7 +861,9 @@ int iwvi_lik_elbo_reduce(const iwvi_lik_desc* lik, const float* fmean, const flo
 
 /* iwvi_iw_elbo_backward_dev with a likelihood descriptor: out_w, d_mean, d_var, out_sums[0] and [2] as there, out_sums[1] =
  * d ELBO / d param[0] (0 for the Bernoulli; BETA: d / d scale; ORDINAL: d / d sigma, the head of param0_dev).  The heads use the reparameterised form of the rule, first derivatives only:
- *   dE/dmu = sum_i w_i g'(f_i),   dE/dv = sum_i w_i g'(f_i) x_i / sqrt(2 v)   with v floored at 1e-8. */
+ *   dE/dmu = sum_i w_i g'(f_i),   dE/dv = sum_i w_i g'(f_i) x_i / sqrt(2 v)   with v floored at 1e-8.
+ * HETERO_GAUSSIAN: Y is [B, Dy / 2], d_mean and d_var are [B K, Dy] (the closed-form heads of the table above, zero through an active clip),
+ * out_sums[1] = 0. */
 int iwvi_lik_elbo_backward(const iwvi_lik_desc* lik, const float* fmean, const float* fvar, const float* Y, int Dy,
                            const float* const* kl_local, const int32_t* kl_dims, int n_local,
                            int64_t B, int K, double scale, int mode_vi,
@@ -845,7 +876,9 @@ int iwvi_lik_elbo_backward(const iwvi_lik_desc* lik, const float* fmean, const f
  * iwvi_gaussian_var_exp.  iwvi_lik_predict_density: log of the predictive density (the Bernoulli's closed form at
  * p = inv_probit(Fmu / sqrt(1 + Fvar)), the Student-t's log-space quadrature of logp); Fvar == NULL: logp(Fmu, Y).
  * iwvi_lik_predict_mean_and_var (n elements): Bernoulli (p, p - p^2) at that p; Student-t (Fmu, E[s^2 nu/(nu - 2) + F^2] - Fmu^2) by the
- * rule, nu > 2 required; Gaussian (Fmu, Fvar + variance); the exp-link types, BETA and ORDINAL: the rule over the conditional moments. */
+ * rule, nu > 2 required; Gaussian (Fmu, Fvar + variance); the exp-link types, BETA and ORDINAL: the rule over the conditional moments.
+ * HETERO_GAUSSIAN: Fmu / Fvar are [T, Dy], Y's rows and out are [., Dy / 2] (one value per row and target column);
+ * iwvi_lik_predict_mean_and_var takes n = T Dy with Dy in param[1] and writes out_mean, out_var [T, Dy / 2]. */
 int iwvi_lik_var_exp(const iwvi_lik_desc* lik, const float* Fmu, const float* Fvar, const float* Y,
                      int64_t T, int Dy, int64_t row_div, int64_t row_mod, float* out, void* stream);
 int iwvi_lik_predict_density(const iwvi_lik_desc* lik, const float* Fmu, const float* Fvar, const float* Y,
@@ -866,10 +899,11 @@ int iwvi_lik_predict_mean_and_var(const iwvi_lik_desc* lik, const float* Fmu, co
  * log-sum-exp is shifted by the running float32 maximum and summed in float64 (a point whose every draw has density -inf gives -inf, not
  * NaN); sum_s E_s and sum_s (Var_s + E_s^2) accumulate in float64 and out_var is formed there and rounded once.  The exp-link types add a
  * point's target-only terms (sum_d c0(y_d)) once, outside the log-sum-exp.
- * Any output may be NULL, at least one must be given, out_mean and out_var go together.  All nine types are accepted -- the Gaussian's
+ * HETERO_GAUSSIAN: Dy = 2 Dt, Y is [N, Dy / 2], out_mean and out_var are [N, Dy / 2]; a draw's density is the sum over its Dt target columns.
+ * Any output may be NULL, at least one must be given, out_mean and out_var go together.  Every type is accepted -- the Gaussian's
  * out_logp is what iwvi_dgp_predict_density computes from the same moments: a cross-check.  A Student-t with df <= 2 is refused only when
  * the moments are asked for.  IWVI_ERR_ARG (with iwvi_last_error) before any launch for: a null or invalid descriptor, N < 0, S < 1, Dy
- * outside 1..IWVI_MAX_P, MULTICLASS with Dy != C, out_logp without Y or Y without out_logp, out_mean without out_var or the reverse, no
+ * outside 1..IWVI_MAX_P, MULTICLASS with Dy != C, HETERO_GAUSSIAN with an odd Dy, out_logp without Y or Y without out_logp, out_mean without out_var or the reverse, no
  * output at all.  N = 0: IWVI_OK, nothing is launched. */
 int iwvi_lik_predict_mixture(const iwvi_lik_desc* lik, const float* fmean, const float* fvar, const float* Y,
                              int64_t N, int S, int Dy, int64_t stride_n, int64_t stride_s,
@@ -879,7 +913,7 @@ int iwvi_lik_predict_mixture(const iwvi_lik_desc* lik, const float* fmean, const
  * csrc/likelihood_sample.hip).  fmean, fvar [T, Dy]: the final layer's moments, one row per (point, draw) in either layout -- the kernel is
  * elementwise over rows.  fvar == NULL: f = fmean.  z_f: optional [T, Dy] standard normals for f (tests); otherwise they are drawn.
  * out_f: optional [T, Dy], the f that was used (the exported noise: a test conditions on it).  out_y [T, Dt], Dt = Dy, except MULTICLASS:
- * Dy = C and Dt = 1 (one label column).  f = fmean + sqrt(max(fvar, 0)) z; links and jitters as in the table above:
+ * Dy = C and Dt = 1 (one label column), and HETERO_GAUSSIAN: Dt = Dy / 2 (z_f and out_f stay [T, Dy]).  f = fmean + sqrt(max(fvar, 0)) z; links and jitters as in the table above:
  *   GAUSSIAN     y = f + sqrt(variance) e
  *   BERNOULLI    y = 1 with probability ip(f) = Phi(f) (1 - 2e-3) + 1e-3, else 0
  *   STUDENT_T    y = f + s n / sqrt(g / (nu / 2)),  n ~ N(0, 1), g ~ Gamma(nu / 2, 1); any nu > 0
@@ -890,6 +924,8 @@ int iwvi_lik_predict_mixture(const iwvi_lik_desc* lik, const float* fmean, const
  *   GAMMA        y = exp(f) G, G ~ Gamma(a, 1) by Marsaglia-Tsang; a < 1: Gamma(a + 1) u^(1/a), formed in log space
  *   BETA         alpha = ip(f) s, beta = s - alpha, y = G_alpha / (G_alpha + G_beta)
  *   ORDINAL      bin j with probability P_j(f) / sum_k P_k(f) (the P_j sum to 0.998): inverse CDF over the n + 1 bins from one uniform
+ *   HETERO_GAUSSIAN  per target column d: f = column d, g = column Dy/2 + d of that formula, y = f + exp(clip(g / 2)) e; the element (and
+ *                sub-stream) is t Dy/2 + d; round 0 gives z_1 and e (words 0, 1) and z_2 (words 2, 3)
  * A NaN moment gives a NaN y.  param0_dev is honoured as everywhere: trained variance, scale, shape and sigma are read on the device.
  * EVERY LOOP IS CAPPED: a rejection sampler (Marsaglia-Tsang, PTRS) runs at most 32 rounds -- exhaustion probability below 0.14^32 = 5e-28
  * at their acceptance rates -- and then returns the conditional mean (f; a exp(f); ip(f); the rate, rounded); the Poisson inversion takes at
@@ -904,7 +940,7 @@ int iwvi_lik_predict_mixture(const iwvi_lik_desc* lik, const float* fmean, const
  * before its 2^32nd launch (the increment would carry into the arrival count).
  * ONE launch, no workspace, no host synchronisation: capturable in a hipGraph.  T = 0: IWVI_OK, nothing is launched.  IWVI_ERR_ARG (with
  * iwvi_last_error) before any launch: a null or invalid descriptor (the checks of iwvi_lik_predict_mixture), T < 0, Dy outside
- * 1..IWVI_MAX_P, MULTICLASS with Dy != C, a null out_y (or, with T > 0, a null fmean). */
+ * 1..IWVI_MAX_P, MULTICLASS with Dy != C, HETERO_GAUSSIAN with an odd Dy, a null out_y (or, with T > 0, a null fmean). */
 int iwvi_lik_sample_y(const iwvi_lik_desc* lik, const float* fmean, const float* fvar, int64_t T, int Dy, const float* z_f,
                       uint64_t seed, uint64_t serial, uint64_t* serial_dev, float* out_y, float* out_f, void* stream);
 
