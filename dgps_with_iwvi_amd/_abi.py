@@ -289,6 +289,9 @@ PROTOTYPES = {
                                          c_float, c_void_p, c_void_p, ctypes.c_uint64, c_void_p, c_void_p, c_void_p]),
     "iwvi_sample_stats": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "iwvi_sample_scores": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "iwvi_energy_score": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "iwvi_kde_density_grid": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int, c_double,
                                       c_void_p, c_void_p, c_void_p, c_void_p]),
     "iwvi_lik_elbo_reduce": (c_int, [ctypes.POINTER(LikDesc), c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_int64,

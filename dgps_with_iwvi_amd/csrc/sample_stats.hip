@@ -2,54 +2,16 @@
 // (experiments/run_conditional_density_estimation.py:148-169) -- KDE log density at y with Silverman's bandwidth, squared error of the
 // sample mean, Shapiro-Wilk W -- and quantiles, all from one ascending sort of the point's samples held in LDS.
 //
-//   sort    P = max(64, next power of two >= S) floats per point, padded with +inf; a bitonic network.  A group of TG threads owns a
-//           point; element i lives with thread i % TG, so every compare distance j < 64 pairs two lanes of ONE wave: those steps run on
-//           registers through __shfl_xor (the first six merge sizes entirely, on the way in from memory; later the last six steps of a
-//           merge), the distances j >= 64 go through LDS with one barrier per step.
-//   sums    float64 from the float32 values, the arithmetic of k_kde_loglik (csrc/lv_elbo.hip): W = b^2 / sum (x - mean)^2 cancels like
+//   sort    the bitonic network of csrc/sample_sort.h, shared with k_sample_scores (csrc/sample_scores.hip): P = max(64, next power of
+//           two >= S) floats per point, padded with +inf.
+//   sums   float64 from the float32 values, the arithmetic of k_kde_loglik (csrc/lv_elbo.hip): W = b^2 / sum (x - mean)^2 cancels like
 //           1 - W ~ 1e-3..1e-4 at the sizes in use, and the KDE's sum of S exponentials is what the reference's float64 estimate sums.
-//   groups  S <= 128: four points per 256-thread workgroup (one wave each); S <= 256: two; above that one point per workgroup, 1024
-//           threads from S > 2048.
+//   groups  ss_shape (csrc/sample_sort.h): four, two or one point per workgroup.
 #include <math.h>
 #include "iwvi_common.h"
+#include "sample_sort.h"
 
 namespace iwvi {
-
-constexpr int SS_MAX_S = 16384;                 // 64 KiB of sorted floats per workgroup
-constexpr int SS_RED = 16 * 3;                  // doubles in front of the samples: 3 partial sums per wave of the workgroup
-
-extern __shared__ __attribute__((aligned(16))) unsigned char ss_smem[];
-
-__device__ __forceinline__ double ss_wsum(double v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64); return v; }
-__device__ __forceinline__ double ss_wmin(double v) { for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64)); return v; }
-
-// sum (the first NV - NMIN entries) / minimum (the last NMIN) over the group's threads, left in every thread.  nwg = waves per group,
-// the same for every group of the workgroup, so the barriers are uniform.
-template <int NV, int NMIN>
-__device__ __forceinline__ void ss_group_reduce(double (&v)[NV], double* red, int gwave, int nwg, int lane) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = k < NV - NMIN ? ss_wsum(v[k]) : ss_wmin(v[k]);
-    if (nwg > 1) {
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < NV; ++k) red[gwave * 3 + k] = v[k];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            double s = red[k];
-            for (int w = 1; w < nwg; ++w) s = k < NV - NMIN ? s + red[w * 3 + k] : fmin(s, red[w * 3 + k]);
-            v[k] = s;
-        }
-        __syncthreads();                                          // (red is free for the next reduction)
-    }
-}
-
-// one compare-exchange step at distance j < 64 inside a wave: `up` = this element's merge sorts ascending
-__device__ __forceinline__ float ss_step(float v, int lane, int j, bool up) {
-    const float p = __shfl_xor(v, j, 64);
-    return (((lane & j) == 0) == up) ? fminf(v, p) : fmaxf(v, p);
-}
 
 __global__ __launch_bounds__(1024) void k_sample_stats(const float* __restrict__ samples, long long sstride, long long nstride,
                                                        const float* __restrict__ y, long long N, int S, int P, int TG,
@@ -66,9 +28,9 @@ __global__ __launch_bounds__(1024) void k_sample_stats(const float* __restrict__
     const float* src = samples + (valid ? n : 0) * nstride;
     const double yy = (valid && y) ? (double)y[n] : 0.0;
 
-    // ---- in: strided samples -> registers, merge sizes 2 .. 64 on the way (element i and i ^ j, j < 64, are lanes of this wave), -> LDS
+    // ---- in: strided samples -> the sort (csrc/sample_sort.h); the sums of the unsorted values are taken on the way
     double acc[3] = {0.0, 0.0, INFINITY};                          // sum, NaN count, min |y - x|
-    for (int i = gtid; i < P; i += TG) {
+    ss_sort_in(x, P, TG, gtid, lane, [&](int i) {
         float v = INFINITY;
         if (valid && i < S) {
             v = src[(long long)i * sstride];
@@ -76,36 +38,9 @@ __global__ __launch_bounds__(1024) void k_sample_stats(const float* __restrict__
             acc[1] += (v != v) ? 1.0 : 0.0;
             acc[2] = fmin(acc[2], fabs(yy - (double)v));
         }
-#pragma unroll
-        for (int k2 = 2; k2 <= 64; k2 <<= 1) {
-            const bool up = (i & k2) == 0;
-#pragma unroll
-            for (int j = k2 >> 1; j > 0; j >>= 1) v = ss_step(v, lane, j, up);
-        }
-        x[i] = v;
-    }
-    __syncthreads();
-    // ---- merge sizes 128 .. P: distances >= 64 through LDS (one barrier each), the last six in registers again
-    for (int k2 = 128; k2 <= P; k2 <<= 1) {
-        for (int j = k2 >> 1; j >= 64; j >>= 1) {
-            for (int q = gtid; q < (P >> 1); q += TG) {
-                const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1));
-                const float a = x[i], b = x[i + j];
-                const bool up = (i & k2) == 0;
-                x[i] = up ? fminf(a, b) : fmaxf(a, b);
-                x[i + j] = up ? fmaxf(a, b) : fminf(a, b);
-            }
-            __syncthreads();
-        }
-        for (int i = gtid; i < P; i += TG) {
-            float v = x[i];
-            const bool up = (i & k2) == 0;
-#pragma unroll
-            for (int j = 32; j > 0; j >>= 1) v = ss_step(v, lane, j, up);
-            x[i] = v;
-        }
-        __syncthreads();
-    }
+        return v;
+    });
+    ss_sort_merge(x, P, TG, gtid, lane);
 
     // ---- sums over the sorted samples (float64): mean -> (sum (x - mean)^2, the Shapiro-Wilk numerator) -> the KDE's sum of exponentials
     ss_group_reduce<3, 1>(acc, red, gwave, nwg, lane);
@@ -137,16 +72,8 @@ __global__ __launch_bounds__(1024) void k_sample_stats(const float* __restrict__
         if (stats) { stats[2 * n] = has_nan ? fnan : (float)mean; stats[2 * n + 1] = has_nan ? fnan : (float)sd; }
         if (outW) outW[n] = has_nan ? fnan : (ssq > 0.0 ? (float)(acc2[1] * acc2[1] / ssq) : 1.f);   // all samples equal: W = 1
     }
-    // ---- quantiles, NumPy's default rule: position p (S - 1), linear between the two neighbouring sorted values
-    for (int q = gtid; q < n_probs; q += TG) {
-        const double p = fmin(fmax(probs[q], 0.0), 1.0);       // (float64: 0.975 as a float32 moves the position by 4e-5 at S = 2000)
-        const double pos = p * (double)(S - 1);
-        int lo = (int)pos;
-        lo = lo < S - 1 ? lo : S - 1;
-        const int hi = lo + 1 < S ? lo + 1 : S - 1;
-        const double a = (double)x[lo], b = (double)x[hi], t = pos - (double)lo;
-        outQ[n * n_probs + q] = has_nan ? fnan : (float)(a == b ? a : a + (b - a) * t);
-    }
+    // ---- quantiles, NumPy's default rule (ss_quantile)
+    for (int q = gtid; q < n_probs; q += TG) outQ[n * n_probs + q] = has_nan ? fnan : (float)ss_quantile(x, S, probs[q]);
 }
 
 }  // namespace iwvi
@@ -163,13 +90,9 @@ extern "C" int iwvi_sample_stats(const float* samples, int64_t sample_stride, in
     if (!y && (out_logp || out_sqerr)) { set_error("iwvi_sample_stats: out_logp / out_sqerr need y"); return IWVI_ERR_ARG; }
     if (out_W && !sw_coef) { set_error("iwvi_sample_stats: out_W needs the %d Shapiro-Wilk coefficients of S=%d", S / 2, S); return IWVI_ERR_ARG; }
     if (N == 0) return IWVI_OK;
-    int P = 64;
-    while (P < S) P <<= 1;
-    const int threads = P >= 4096 ? 1024 : 256;
-    int TG = P / 2 < 64 ? 64 : P / 2;
-    if (TG > threads) TG = threads;
-    const int groups = threads / TG;
-    const size_t lds_bytes = SS_RED * sizeof(double) + (size_t)groups * P * sizeof(float);
+    const SsShape sh = ss_shape(S);
+    const int P = sh.P, threads = sh.threads, TG = sh.TG, groups = sh.groups;
+    const size_t lds_bytes = sh.lds_bytes;
     static size_t attr_set = 0;
     if (lds_bytes > attr_set) {
         hipError_t e = hipFuncSetAttribute((const void*)k_sample_stats, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);

@@ -18,6 +18,10 @@ Shapiro-Wilk W and any quantiles from it -- with one read-back at the end.
 ``m + z sqrt(v)`` samples means nothing --: the Monte Carlo log predictive density, and the error / accuracy of the predictive mixture's
 mean (``model.predict_mixture``: per batch the layer launch and one ``iwvi_lik_predict_mixture`` launch), with one read-back at the end.
 
+``evaluate_scores`` puts proper scoring rules on the exact draws of any likelihood and any number of target columns: per batch one
+``iwvi_sample_scores`` launch per column (CRPS, the counts of a PIT / rank histogram, quantiles and their pinball loss, from the one sort
+of ``iwvi_sample_stats``) and, for several columns, one ``iwvi_energy_score`` launch (the multivariate CRPS over all pairs of draws).
+
 ``evaluate_sghmc`` is the evaluation of an SGHMC model over its collected posterior samples: one fused y-sample per kept theta and test point."""
 import ctypes
 
@@ -422,7 +426,7 @@ def evaluate_draws(model, X_test, Y_test, num_predict_samples=2000, predict_batc
     ``test_rmse``, the draws' mean against Y; and for the continuous likelihoods (Gaussian, Student-t, Exponential, Gamma, Beta)
     ``test_loglik``, the reference's KDE test log-likelihood (run_conditional_density_estimation.py:148-165) from the same launch.
     One read-back at the end."""
-    from .likelihoods import Bernoulli, MultiClass, Ordinal, Poisson, target_dim
+    from .likelihoods import target_dim
     if not 0.0 < float(interval) < 1.0:
         raise ValueError("interval must lie in (0, 1), got %r" % (interval,))
     dev = model.X.device
@@ -434,7 +438,7 @@ def evaluate_draws(model, X_test, Y_test, num_predict_samples=2000, predict_batc
     if N == 0 or Y_test.numel() != N:
         raise ValueError("X_test has %d rows, Y_test must be [%d, 1], got %s" % (N, N, tuple(Y_test.shape)))
     Y_test = Y_test.reshape(N)
-    continuous = not isinstance(model.likelihood, (Bernoulli, MultiClass, Ordinal, Poisson))
+    continuous = not isinstance(model.likelihood, _discrete_likelihoods())
     probs = [0.5 * (1.0 - float(interval)), 0.5 * (1.0 + float(interval))]
     parts = []
     for lo in range(0, N, int(predict_batch_size)):
@@ -451,3 +455,177 @@ def evaluate_draws(model, X_test, Y_test, num_predict_samples=2000, predict_batc
         names.append("test_loglik")
     vals = torch.stack(stats).cpu().numpy()                                         # the one read-back
     return {k: float(v) for k, v in zip(names, vals)}
+
+
+# ---- proper scoring rules of predictive draws: CRPS, PIT, pinball loss, energy score ----------------------------------------------------
+def _discrete_likelihoods():
+    """The likelihoods whose targets are counts or labels (``evaluate_draws``: no KDE; ``evaluate_scores``: a randomized PIT)."""
+    from .likelihoods import Bernoulli, MultiClass, Ordinal, Poisson
+    return (Bernoulli, MultiClass, Ordinal, Poisson)
+
+
+def sample_scores(samples, y, quantiles=None):
+    """samples [S, N] (device, any strides), y [N] -> dict of device tensors through one ``iwvi_sample_scores`` launch (one sort per
+    point, the one of ``sample_stats``): ``crps`` and ``crps_fair`` [N], the CRPS of the draws' empirical distribution and its fair
+    (unbiased) version; ``below`` and ``equal`` [N] (int32), the number of draws below y and equal to y (``pit_values`` turns them into a
+    PIT); ``quantiles`` [N, len(quantiles)] (bit-equal to ``sample_stats``'s) and ``pinball`` [N, len(quantiles)], the quantile loss of
+    each, when asked for.  A point with a NaN draw or a NaN y: NaN, and -1 in both counts.  2 <= S <= 16384."""
+    probs = None if quantiles is None else _check_probs(quantiles)
+    if not isinstance(samples, torch.Tensor) or samples.dim() != 2:
+        raise ValueError("samples must be a [S, N] tensor")
+    S, N = samples.shape
+    if S < 2 or S > MAX_SAMPLES:
+        raise ValueError("S=%d out of range (2..%d)" % (S, MAX_SAMPLES))
+    if not isinstance(y, torch.Tensor) or y.numel() != N:
+        raise ValueError("y must be a tensor of %d entries, one per point of samples" % N)
+    if N > 0 and min(samples.stride()) <= 0:                             # (an expanded view: the kernel takes positive strides)
+        samples = samples.contiguous()
+    if not samples.is_cuda or samples.dtype != settings.float_type:
+        _abi.dev_tensor(samples.contiguous(), "samples")                 # (raises: no CPU fallback, float32 only)
+    dev = samples.device
+    y = _abi.dev_tensor(y.reshape(-1).contiguous(), "y")
+    crps = torch.empty(N, 2, dtype=settings.float_type, device=dev)
+    counts = torch.empty(N, 2, dtype=torch.int32, device=dev)
+    out = {"crps": crps[:, 0], "crps_fair": crps[:, 1], "below": counts[:, 0], "equal": counts[:, 1]}
+    pr = None
+    if probs is not None:
+        pr = torch.as_tensor(probs, dtype=torch.float64, device=dev)
+        out["quantiles"], out["pinball"] = (torch.empty(N, len(probs), dtype=settings.float_type, device=dev) for _ in range(2))
+    if N == 0:
+        return out
+    ss, sn = samples.stride()
+    _abi.check(_abi.lib().iwvi_sample_scores(ctypes.c_void_p(samples.data_ptr()), ss, sn, _abi.ptr(y), N, S, _abi.ptr(pr),
+                                            0 if probs is None else len(probs), _abi.ptr(crps), _abi.ptr(counts),
+                                            _abi.ptr(out.get("quantiles")), _abi.ptr(out.get("pinball")), _abi.stream_ptr()))
+    return out
+
+
+def energy_score(samples, Y):
+    """samples [S, N, D] (device, any positive strides -- the [N, S, D] view of ``predict_y_draws`` included), Y [N, D] -> dict of device
+    tensors through one ``iwvi_energy_score`` launch: ``energy`` and ``energy_fair`` [N], (1/S) sum_s |x_s - y| - B / S^2 and
+    - B / (S (S - 1)) with B = sum_{s<t} |x_s - x_t|: the multivariate CRPS (D = 1: the CRPS itself).  2 <= S <= 16384, 1 <= D <= 32."""
+    if not isinstance(samples, torch.Tensor) or samples.dim() != 3:
+        raise ValueError("samples must be a [S, N, D] tensor")
+    S, N, D = samples.shape
+    if S < 2 or S > MAX_SAMPLES:
+        raise ValueError("S=%d out of range (2..%d)" % (S, MAX_SAMPLES))
+    if D < 1 or D > _abi.MAX_P:
+        raise ValueError("D=%d out of range (1..%d)" % (D, _abi.MAX_P))
+    if not isinstance(Y, torch.Tensor) or tuple(Y.shape) != (N, D):
+        raise ValueError("Y must be a [N, D] = %s tensor, got %s" % ((N, D), tuple(Y.shape) if isinstance(Y, torch.Tensor) else type(Y).__name__))
+    if N > 0 and min(samples.stride()) <= 0:
+        samples = samples.contiguous()
+    if not samples.is_cuda or samples.dtype != settings.float_type:
+        _abi.dev_tensor(samples.contiguous(), "samples")                 # (raises: no CPU fallback, float32 only)
+    Y = _abi.dev_tensor(Y.contiguous(), "Y")
+    es = torch.empty(N, 2, dtype=settings.float_type, device=samples.device)
+    if N > 0:
+        ss, sn, sd = samples.stride()
+        _abi.check(_abi.lib().iwvi_energy_score(ctypes.c_void_p(samples.data_ptr()), ss, sn, sd, _abi.ptr(Y), N, S, D, _abi.ptr(es),
+                                               _abi.stream_ptr()))
+    return {"energy": es[:, 0], "energy_fair": es[:, 1]}
+
+
+def pit_values(below, equal, S, randomized=False, generator=None):
+    """The probability integral transform of each target among its S draws, from the counts of ``sample_scores``, float64 on the counts'
+    device: the mid-rank (below + equal / 2 + 1/2) / (S + 1) by default; ``randomized``: uniform in [below, below + equal + 1) / (S + 1)
+    (``torch.rand`` on that device, ``generator`` optional) -- what a discrete target, whose draws tie with it all the time, needs for a
+    flat histogram under a calibrated model.  A point the kernel marked invalid (counts -1) gets NaN."""
+    S = int(S)
+    if S < 1:
+        raise ValueError("S=%d: no draws" % S)
+    b, e = below.to(torch.float64), equal.to(torch.float64)
+    if b.shape != e.shape:
+        raise ValueError("below %s and equal %s differ in shape" % (tuple(b.shape), tuple(e.shape)))
+    if randomized:
+        u = torch.rand(b.shape, dtype=torch.float64, device=b.device, generator=generator)
+        pit = (b + u * (e + 1.0)) / (S + 1.0)
+    else:
+        pit = (b + 0.5 * e + 0.5) / (S + 1.0)
+    return torch.where(b < 0, torch.full_like(pit, float("nan")), pit)
+
+
+def _pit_summary(pit, bins):
+    """[bins + 1] float64 on pit's device: the histogram's counts over ``bins`` equal bins of [0, 1], then sup_u |ECDF(u) - u|."""
+    pit = pit.reshape(-1).to(torch.float64)
+    n = pit.numel()
+    idx = torch.clamp((pit * bins).to(torch.int64), 0, bins - 1)
+    counts = torch.zeros(bins, dtype=torch.float64, device=pit.device).scatter_add_(0, idx, torch.ones_like(pit))
+    p = pit.sort().values
+    i = torch.arange(1, n + 1, dtype=torch.float64, device=pit.device)
+    ks = torch.maximum(i / n - p, p - (i - 1.0) / n).max()
+    return torch.cat([counts, ks.reshape(1)])
+
+
+def pit_histogram(pit, bins=10):
+    """-> dict(counts [bins] (NumPy int64): the PIT / rank histogram over equal bins of [0, 1]; calibration_error: the Kolmogorov distance
+    sup_u |ECDF_PIT(u) - u| between the PIT values and the uniform distribution, 0 for a calibrated predictive).  Device ops, one read-back."""
+    bins = int(bins)
+    if bins < 1:
+        raise ValueError("bins must be >= 1")
+    if not isinstance(pit, torch.Tensor) or pit.numel() == 0:
+        raise ValueError("pit must be a non-empty tensor")
+    v = _pit_summary(pit, bins).cpu().numpy()
+    return {"counts": v[:bins].astype(np.int64), "calibration_error": float(v[bins])}
+
+
+def evaluate_scores(model, X_test, Y_test, num_predict_samples=2000, predict_batch_size=1000, quantiles=(0.05, 0.25, 0.5, 0.75, 0.95),
+                    pit_bins=10, randomized_pit=None):
+    """Proper scoring rules and calibration of the predictive distribution, for ANY likelihood and any number Dt >= 1 of target columns,
+    from the exact draws of ``model.predict_y_draws`` (``predict_y_samples`` for a ``cvae.CVAE``): per batch of ``predict_batch_size``
+    points one draw of ``num_predict_samples`` targets per point, one ``iwvi_sample_scores`` launch per target column and, for Dt > 1,
+    one ``iwvi_energy_score`` launch.  Means over the test points: ``test_crps``, ``test_crps_fair``; ``test_pinball`` (one per entry of
+    ``quantiles``); ``test_pit_hist`` (``pit_bins`` counts) and ``test_calibration_error`` (``pit_histogram``) -- each a list with one
+    entry per column when Dt > 1, which then also has ``test_energy_score`` / ``test_energy_score_fair``.  ``randomized_pit`` None: the
+    randomized PIT exactly for the discrete likelihoods (Bernoulli, MultiClass, Ordinal, Poisson), the mid-rank otherwise.
+    One read-back at the end."""
+    from .cvae import CVAE
+    from .likelihoods import target_dim
+    probs = _check_probs(quantiles)
+    if probs.size == 0:
+        raise ValueError("evaluate_scores needs at least one quantile")
+    S, bs, bins = int(num_predict_samples), int(predict_batch_size), int(pit_bins)
+    if S < 2 or S > MAX_SAMPLES:
+        raise ValueError("num_predict_samples=%d out of range (2..%d)" % (S, MAX_SAMPLES))
+    if bs < 1 or bins < 1:
+        raise ValueError("predict_batch_size and pit_bins must be >= 1")
+    dev = model.X.device
+    X_test = torch.as_tensor(np.asarray(X_test, dtype=np.float32), device=dev) if not isinstance(X_test, torch.Tensor) else X_test.to(dev, settings.float_type)
+    Y_test = torch.as_tensor(np.asarray(Y_test, dtype=np.float32), device=dev) if not isinstance(Y_test, torch.Tensor) else Y_test.to(dev, settings.float_type)
+    N = X_test.shape[0]
+    is_cvae = isinstance(model, CVAE)
+    Dt = model._output_dim() if is_cvae else target_dim(model.likelihood, model._output_dim())
+    if N == 0 or Y_test.dim() != 2 or tuple(Y_test.shape) != (N, Dt):
+        raise ValueError("X_test has %d rows, Y_test must be [%d, %d], got %s" % (N, N, Dt, tuple(Y_test.shape)))
+    if Dt > _abi.MAX_P:
+        raise ValueError("%d target columns: the energy score takes up to %d" % (Dt, _abi.MAX_P))
+    if randomized_pit is None:
+        randomized_pit = isinstance(model.likelihood, _discrete_likelihoods())
+    Y_test = Y_test.contiguous()
+    cols, energy = [[] for _ in range(Dt)], []
+    for lo in range(0, N, bs):
+        x, y = X_test[lo:lo + bs], Y_test[lo:lo + bs]
+        smp = model.predict_y_samples(x, S) if is_cvae else model.predict_y_draws(x, S)         # [S, n, Dt], a point's draws contiguous
+        for d in range(Dt):
+            cols[d].append(sample_scores(smp[:, :, d], y[:, d], quantiles=probs))
+        if Dt > 1:
+            energy.append(energy_score(smp, y))
+    stats = []
+    for d in range(Dt):
+        cat = {k: torch.cat([p[k] for p in cols[d]]) for k in cols[d][0]}
+        pit = pit_values(cat["below"], cat["equal"], S, randomized=bool(randomized_pit))
+        stats += [cat["crps"].double().mean().reshape(1), cat["crps_fair"].double().mean().reshape(1), cat["pinball"].double().mean(0),
+                  _pit_summary(pit, bins)]
+    if Dt > 1:
+        stats += [torch.cat([e[k] for e in energy]).double().mean().reshape(1) for k in ("energy", "energy_fair")]
+    vals = torch.cat(stats).cpu().numpy()                                           # the one read-back
+    nq, per = len(probs), 2 + len(probs) + bins + 1
+    by_col = []
+    for d in range(Dt):
+        v = vals[d * per:(d + 1) * per]
+        by_col.append(dict(test_crps=float(v[0]), test_crps_fair=float(v[1]), test_pinball=[float(t) for t in v[2:2 + nq]],
+                           test_pit_hist=[int(t) for t in v[2 + nq:2 + nq + bins]], test_calibration_error=float(v[per - 1])))
+    res = dict(by_col[0]) if Dt == 1 else {k: [c[k] for c in by_col] for k in by_col[0]}
+    if Dt > 1:
+        res["test_energy_score"], res["test_energy_score_fair"] = float(vals[Dt * per]), float(vals[Dt * per + 1])
+    return res

@@ -29,7 +29,7 @@ extern "C" {
 
 /* 19, with additive extensions: iwvi_dgp_predict_samples and iwvi_sample_stats, then the iwvi_lik_* entry points (likelihoods other than
  * the Gaussian; iwvi_lik_predict_mixture, their Monte Carlo predictive mixture, last), were added without a change to any existing entry point or struct, so the number did not move and a caller built against
- * 19 keeps working.  A C caller that wants the new symbols looks them up (dlsym), Python asks hasattr(lib, ...). */
+ * 19 keeps working; iwvi_sample_scores and iwvi_energy_score (proper scoring rules of predictive samples) likewise.  A C caller that wants the new symbols looks them up (dlsym), Python asks hasattr(lib, ...). */
 #define IWVI_ABI_VERSION 19
 
 enum {
@@ -690,6 +690,41 @@ int iwvi_dgp_predict_samples(const iwvi_layer_desc* layers_host, int n_layers, c
 int iwvi_sample_stats(const float* samples, int64_t sample_stride, int64_t point_stride, const float* y, int64_t N, int S,
                       const double* sw_coef, const double* probs, int n_probs, float* out_logp, float* out_sqerr,
                       float* out_mean_std, float* out_W, float* out_quantiles, void* stream);
+
+/* Univariate proper scoring rules of S samples per point in one launch (additive extension of ABI 19; csrc/sample_scores.hip), from the
+ * same ONE ascending sort x_(1) <= .. <= x_(S) as iwvi_sample_stats (csrc/sample_sort.h: one network, one grouping rule, one quantile rule).
+ * samples, strides, S and N as iwvi_sample_stats; y [N] is required.  With
+ *   A = (1/S) sum_s |x_s - y|,   G = sum_i (2i - S - 1) x_(i) = 1/2 sum_s sum_t |x_s - x_t|:
+ *   out_crps [N, 2]: A - G / S^2, the ensemble CRPS (the CRPS of the samples' empirical distribution), and A - G / (S (S - 1)), the fair
+ *     CRPS (unbiased for the CRPS of the distribution the samples were drawn from).  Valid for counts and labels as for reals.
+ *   out_counts [N, 2] (int32): #{s : x_s < y} and #{s : x_s == y}, exact.  A PIT value / rank is formed from them by the caller, who
+ *     decides what ties mean (mid-rank, or a uniform draw inside the tie for a discrete target).
+ *   out_quantiles [N, n_probs]: at probs [n_probs] (device, float64, clamped to [0, 1]), NumPy's default linear rule: the arithmetic of
+ *     iwvi_sample_stats, the same bits on the same input.  n_probs = 0: none.
+ *   out_pinball [N, n_probs]: max(tau (y - Q), (tau - 1) (y - Q)), tau = probs[q], Q the float64 quantile before it is rounded.
+ * Every sum is float64 formed from the float32 values, combined in a fixed order (no atomics: two calls give the same bits); each result
+ * is rounded to float32 once.  Every output may be NULL.  A point with a NaN sample or a NaN y gets NaN in its float outputs and -1 in
+ * both counts; other points are not affected.  N = 0: IWVI_OK without a launch.  IWVI_ERR_ARG before any HIP call for: S outside
+ * 2 .. 16384, N outside 0 .. 2^31 - 1, null samples or y, a non-positive stride, n_probs < 0, n_probs > 0 without probs or without
+ * either of out_quantiles / out_pinball. */
+int iwvi_sample_scores(const float* samples, int64_t sample_stride, int64_t point_stride, const float* y, int64_t N, int S,
+                       const double* probs, int n_probs, float* out_crps, int32_t* out_counts, float* out_quantiles,
+                       float* out_pinball, void* stream);
+
+/* The energy score, the multivariate CRPS, of S samples in D dimensions per point in one launch (additive extension of ABI 19;
+ * csrc/energy_score.hip).  samples: coordinate d of sample s of point n at samples[s*sample_stride + n*point_stride + d*dim_stride]
+ * (positive strides); Y [N, D] row-major.  With
+ *   A = (1/S) sum_s |x_s - y|,   B = sum_{s<t} |x_s - x_t|   (Euclidean norms):
+ *   out [N, 2]: A - B / S^2, the ensemble energy score, and A - B / (S (S - 1)), the fair one.  D = 1: the two CRPS of iwvi_sample_scores.
+ * A distance is sum_d (x_sd - x_td)^2 in float32 FROM THE DIFFERENCES, then one square root -- not |x_s|^2 + |x_t|^2 - 2 x_s . x_t, which
+ * loses every digit of the near pairs when the samples are tight against their offset.  The sums over pairs and samples are float64, in a
+ * fixed order (lane, wave, workgroup; no atomics: two calls give the same bits); each result is rounded to float32 once.  Only the pairs
+ * s < t are visited, one workgroup per point, the samples staged through LDS in tiles.
+ * 2 <= S <= 16384, 1 <= D <= IWVI_MAX_P.  A point with a NaN coordinate or a NaN target gets NaN in both outputs; other points are not
+ * affected.  N = 0: IWVI_OK without a launch.  IWVI_ERR_ARG before any HIP call for S, D or N (0 .. 2^31 - 1) out of range, a null
+ * pointer, a non-positive stride. */
+int iwvi_energy_score(const float* samples, int64_t sample_stride, int64_t point_stride, int64_t dim_stride, const float* Y,
+                      int64_t N, int S, int D, float* out, void* stream);
 
 /* Log density of each point's Gaussian kernel-density estimate on a GRID of levels, one launch (additive extension of ABI 19;
  * csrc/kde_grid.hip): the reference's conditional density picture (experiments/demo.py), 200 inputs x 10 000 samples x 200 levels.

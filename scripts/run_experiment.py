@@ -66,6 +66,8 @@ def run_cvae(ARGS, X, Y, Xs, Ys, dev):
     dt = time.perf_counter() - t0
     res = evaluation.evaluate(model, Xs, Ys, ARGS.num_predict_samples, ARGS.predict_batch_size, shapiro=True, on_device=ARGS.device_eval)
     res.update(test_loglik_before_training=before["test_loglik"], train_seconds=dt, ms_per_iteration=dt / max(ARGS.iterations, 1) * 1e3)
+    if ARGS.scores:
+        res.update(evaluation.evaluate_scores(model, Xs, Ys, ARGS.num_predict_samples, ARGS.predict_batch_size))
     res.update(ARGS.__dict__)
     print(res)
     return res
@@ -93,6 +95,9 @@ def main(argv=None):
     p.add_argument("--sghmc_spacing", type=int, default=5, help="--mode SGHMC: sample ops between two kept posterior samples")
     p.add_argument("--use_graph", type=int, default=1, help="replay the ops of a step from captured graphs")
     p.add_argument("--device_eval", action="store_true", help="evaluate on the device: fused y-samples + iwvi_sample_stats (evaluate(on_device=True))")
+    p.add_argument("--scores", action="store_true",
+                   help="add the proper scoring rules of the predictive draws (evaluate_scores: CRPS, pinball loss, PIT histogram and "
+                        "calibration error); not with --mode SGHMC")
     p.add_argument("--kmeans", choices=("host", "device"), default="host",
                    help="where the first layer's inducing inputs are clustered: SciPy's kmeans2 on the host, or iwvi_kmeans on the device")
     p.add_argument("--encoder_gradient", choices=("iwae", "dreg", "stl"), default="iwae",
@@ -124,6 +129,8 @@ def main(argv=None):
     dt = time.perf_counter() - t0
     res = evaluation.evaluate(model, Xs, Ys, ARGS.num_predict_samples, ARGS.predict_batch_size, shapiro=True, on_device=ARGS.device_eval)
     res.update(test_loglik_before_training=before["test_loglik"], train_seconds=dt, ms_per_iteration=dt / max(ARGS.iterations, 1) * 1e3)
+    if ARGS.scores:
+        res.update(evaluation.evaluate_scores(model, Xs, Ys, ARGS.num_predict_samples, ARGS.predict_batch_size))
     res.update(ARGS.__dict__)
     print(res)
     return res
