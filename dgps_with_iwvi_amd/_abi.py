@@ -132,6 +132,16 @@ class BoundDesc(ctypes.Structure):
     _fields_ = [("groups", ctypes.c_int32), ("tau", c_float), ("beta", c_float)]
 
 
+class PsisDesc(ctypes.Structure):
+    """struct iwvi_psis_desc (include/iwvi_hip.h): the inputs and outputs of iwvi_psis_summary."""
+    _fields_ = [("terms", c_void_p), ("n_terms", ctypes.c_int32), ("fmean", c_void_p), ("fvar", c_void_p), ("Y", c_void_p),
+                ("Dy", ctypes.c_int32), ("var_exp", ctypes.c_int32), ("lik_variance", c_float), ("lik_variance_dev", c_void_p),
+                ("kl_local", ctypes.POINTER(c_void_p)), ("kl_dims", ctypes.POINTER(ctypes.c_int32)), ("n_kl", ctypes.c_int32),
+                ("N", c_int64), ("S", ctypes.c_int32), ("stride_n", c_int64), ("stride_s", c_int64),
+                ("out_logw", c_void_p), ("out_raw", c_void_p), ("out_ess", c_void_p), ("out_khat", c_void_p), ("out_psis", c_void_p)]
+
+
+PSIS_MAX_S = 16384                                             # csrc/sample_sort.h: SS_MAX_S
 MOMENTS_MAX_TENSORS = 48
 LV_GRAD_IWAE, LV_GRAD_DREG, LV_GRAD_STL = 0, 1, 2              # IWVI_LV_GRAD_*
 LV_GRAD = {"iwae": LV_GRAD_IWAE, "dreg": LV_GRAD_DREG, "stl": LV_GRAD_STL}
@@ -309,6 +319,7 @@ PROTOTYPES = {
     "iwvi_lik_predict_mean_and_var": (c_int, [ctypes.POINTER(LikDesc), c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "iwvi_lik_predict_mixture": (c_int, [ctypes.POINTER(LikDesc), c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_int64,
                                          c_void_p, c_void_p, c_void_p, c_void_p]),
+    "iwvi_psis_summary": (c_int, [ctypes.POINTER(PsisDesc), c_void_p]),
     "iwvi_lik_sample_y": (c_int, [ctypes.POINTER(LikDesc), c_void_p, c_void_p, c_int64, c_int, c_void_p,
                                   ctypes.c_uint64, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "iwvi_unwhiten": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -22,6 +22,10 @@ mean (``model.predict_mixture``: per batch the layer launch and one ``iwvi_lik_p
 ``iwvi_sample_scores`` launch per column (CRPS, the counts of a PIT / rank histogram, quantiles and their pinball loss, from the one sort
 of ``iwvi_sample_stats``) and, for several columns, one ``iwvi_energy_score`` launch (the multivariate CRPS over all pairs of draws).
 
+``evaluate_importance`` is the held-out log density by importance sampling with the encoders as the proposal
+(``model.importance_log_density``: per batch the layer launch and one ``iwvi_psis_summary`` launch) with the diagnostics that say whether
+it can be trusted -- the Pareto-k of PSIS and the effective sample size --; ``psis_summary`` gives them for any [N, S] log-weights.
+
 ``evaluate_sghmc`` is the evaluation of an SGHMC model over its collected posterior samples: one fused y-sample per kept theta and test point."""
 import ctypes
 
@@ -629,3 +633,45 @@ def evaluate_scores(model, X_test, Y_test, num_predict_samples=2000, predict_bat
     if Dt > 1:
         res["test_energy_score"], res["test_energy_score_fair"] = float(vals[Dt * per]), float(vals[Dt * per + 1])
     return res
+
+
+def psis_summary(logw):
+    """Importance log-weights ``logw`` [N, S] (device float32, any strides -- the transposed [S, N] view or a slice included) -> dict of
+    device tensors [N] through one ``iwvi_psis_summary`` launch: ``log_mean`` = logsumexp_s - log S, ``log_mean_psis`` (the same with the
+    Pareto-smoothed tail), ``khat`` (the Pareto-k diagnostic: below 0.5 good, below 0.7 usable, from 0.7 on the weights cannot be trusted
+    at any practical S; +inf: no fit) and ``ess`` (Kish).  S <= 16384.  The training log-weights are one input:
+    ``psis_summary(model._logw().view(B, K))`` -- its ``ess`` is ``model.importance_ess()``, and its ``khat`` says what the effective
+    sample size cannot: whether the weights have a tail that one more draw could overturn."""
+    from . import psis
+    if not isinstance(logw, torch.Tensor) or logw.dim() != 2:
+        raise ValueError("logw must be a [N, S] tensor")
+    if logw.dtype != settings.float_type:
+        raise TypeError("logw must be %s, got %s" % (settings.float_type, logw.dtype))
+    if not logw.is_cuda:
+        raise _abi.IwviError("logw is on %s: iwvi_psis_summary is a gfx950 HIP kernel (there is no CPU fallback)" % logw.device)
+    N, S = logw.shape
+    sn, ss = logw.stride()
+    if sn < 0 or ss < 0:
+        raise ValueError("logw strides must not be negative")
+    r = psis.summarise(N, S, sn, ss, terms=logw, n_terms=1)
+    return {"log_mean": r["raw"], "log_mean_psis": r["psis"], "khat": r["khat"], "ess": r["ess"]}
+
+
+def evaluate_importance(model, X_test, Y_test, num_importance_samples=5000, predict_batch_size=None, proposal="encoder"):
+    """-> dict from ``model.importance_log_density(X_test, Y_test, num_importance_samples, proposal)``: ``test_loglik_is``, the mean
+    importance-sampled log density (taken in float64), ``test_loglik_psis``, the mean of its Pareto-smoothed form, and what says whether
+    either can be trusted: ``test_khat_median``, ``test_khat_max``, ``test_khat_bad_share`` (the share of points with khat > 0.7),
+    ``test_ess_median``, ``test_ess_min``.  One read-back at the end."""
+    dev = model.X.device
+    X_test = torch.as_tensor(np.asarray(X_test, dtype=np.float32), device=dev) if not isinstance(X_test, torch.Tensor) else X_test.to(dev, settings.float_type)
+    Y_test = torch.as_tensor(np.asarray(Y_test, dtype=np.float32), device=dev) if not isinstance(Y_test, torch.Tensor) else Y_test.to(dev, settings.float_type)
+    N = X_test.shape[0]
+    if N == 0 or Y_test.dim() != 2 or Y_test.shape[0] != N:
+        raise ValueError("X_test has %d rows, Y_test must be [%d, columns], got %s" % (N, N, tuple(Y_test.shape)))
+    r = model.importance_log_density(X_test, Y_test, num_importance_samples, proposal=proposal, batch_size=predict_batch_size)
+    kh, ess = r["khat"].double(), r["ess"].double()
+    stats = [r["log_density"].double().mean(), r["log_density_psis"].double().mean(), kh.median(), kh.max(), (kh > 0.7).double().mean(),
+             ess.median(), ess.min()]
+    names = ["test_loglik_is", "test_loglik_psis", "test_khat_median", "test_khat_max", "test_khat_bad_share", "test_ess_median", "test_ess_min"]
+    vals = torch.stack(stats).cpu().numpy()                          # the one read-back of the scalars
+    return {k: float(v) for k, v in zip(names, vals)}

@@ -4,7 +4,7 @@ The layer kernel's hot variants sit at the 256-VGPR limit: a source change anywh
 scratch, and a variant that only the large configs take then regresses unnoticed (round 4: the five-sub-tile large-M variant went
 216 B into scratch, configs[3] 1.27 -> 1.43 ms, for four commits).  ``check()`` is run by ``__graft_entry__.build()`` and by
 tests/test_kernel_resources.py: it fails when a ``k_dgp_forward`` or ``k_bw_chain`` instantiation (the predictive and sampling variants of the
-forward included), ``k_sample_stats``, ``k_sample_scores``, ``k_energy_score``, ``k_kde_grid`` or a likelihood-tail kernel (every ``k_lik_*``, ``k_mc_*``, ``k_xl_*``, ``k_bo_*``, ``k_hg_*``, the ``*_mix`` kernels of the predictive mixture and the sampling kernel ``k_lik_sample`` included) the SGHMC update ``k_sghmc_step``, a CVAE kernel (``k_cvae_*``) or a k-means kernel (``k_km_*``) uses scratch memory
+forward included), ``k_sample_stats``, ``k_sample_scores``, ``k_energy_score``, ``k_psis_summary``, ``k_kde_grid`` or a likelihood-tail kernel (every ``k_lik_*``, ``k_mc_*``, ``k_xl_*``, ``k_bo_*``, ``k_hg_*``, the ``*_mix`` kernels of the predictive mixture and the sampling kernel ``k_lik_sample`` included) the SGHMC update ``k_sghmc_step``, a CVAE kernel (``k_cvae_*``) or a k-means kernel (``k_km_*``) uses scratch memory
 (``.private_segment_fixed_size`` > 0) beyond what ``ALLOWED_SCRATCH`` lists, when a listed spill count grows, or when a kernel listed in ``MAX_VGPRS`` exceeds its VGPR ceiling.
 
   python -m dgps_with_iwvi_amd.kernel_resources [--write profiles/<tag>_kernel_resources.txt]
@@ -47,7 +47,9 @@ NO_SCRATCH = ("k_dgp_forward", "k_bw_chain", "k_sample_stats", "k_lik_elbo", "k_
               "k_bound_logw", "k_bound_bwd", "k_bound_finish",
               # csrc/sample_scores.hip: the sort of k_sample_stats (csrc/sample_sort.h) with other sums; csrc/energy_score.hip: a row sample
               # travels in up to 32 registers through the whole pair loop
-              "k_sample_scores", "k_energy_score")
+              "k_sample_scores", "k_energy_score",
+              # csrc/psis.hip: that sort again, then a float64 generalized-Pareto fit whose operands live in LDS, not in per-lane arrays
+              "k_psis_summary")
 # ... except these (demangled-name substring -> bytes of scratch it is known to use; lower it when a kernel improves)
 ALLOWED_SCRATCH = {
     # round 6 (profiles/r06_kernel_resources.txt): every BIG variant (some layer with M > 128: configs[3] / [4]) and every float64-route

@@ -16,6 +16,9 @@ final layer -- Y is one column of class labels, the layer has one output per cla
 ``HeteroskedasticGaussian`` has two outputs (mean, log noise variance) per target column and goes through the same two functions.
 ``predict_mixture`` evaluates a trained model of any likelihood the same way: the layer launch, then one ``iwvi_lik_predict_mixture`` launch gives
 the mean, variance and log density of the Monte Carlo predictive mixture over S draws (``predict_log_density`` of a non-Gaussian model is its density).
+``importance_log_density`` is the held-out log density with the encoders as the proposal instead of the prior: the layer launch with the
+sampled local regularisers, then one ``iwvi_psis_summary`` launch gives the importance-sampled estimate, its Pareto-smoothed form, the
+Pareto-k diagnostic and the effective sample size per point.
 
 Differences from the reference, all documented in DESIGN.md:
   * ``zs`` (one N(0,1) array or None per layer) injects the noise tf.random_normal draws in-graph; None
@@ -747,6 +750,104 @@ class DGP_VI:
                 _abi.ptr(res["mean"][lo:hi]) if _moments else None, _abi.ptr(res["var"][lo:hi]) if _moments else None, _abi.stream_ptr()))
         return res
 
+    def importance_log_density(self, X, Y, S, proposal="encoder", kind="predictive", zs=None, batch_size=None, return_logw=False):
+        """Importance-sampled held-out log density with its diagnostics -> dict of device tensors: ``log_density`` [N] =
+        log (1/S) sum_s w_ns, ``log_density_psis`` [N] (the same with the Pareto-smoothed tail), ``khat`` [N] (below 0.5 good, below 0.7
+        usable, from 0.7 on unreliable at any practical S; +inf: no fit), ``ess`` [N] (Kish) and, with ``return_logw``, ``logw`` [N, S].
+
+        ``proposal="encoder"``: every latent-variable layer draws w_s ~ q(w | x*, y*) from its encoder on the held-out rows and the draw is
+        weighted by p(w_s) / q(w_s | x*, y*): log w = log p(y* | f_s) - sum over those layers of [log q(w_s) - log p(w_s)].
+        ``proposal="prior"``: w_s ~ p(w), no weight -- ``predict_log_density``'s estimator plus diagnostics, and the route of a model
+        without a latent-variable layer.  Both estimate the same p(y* | x*).  ``kind="predictive"``: p(y* | f_s) is the likelihood's
+        predictive density at the final layer's moments; ``kind="bound"``: its variational expectation -- the per-point held-out
+        importance-weighted bound without the global KL.  ``zs``: one [S, N, dim] array or None per layer, as ``predict_log_density``.
+
+        Per batch of ``batch_size`` points (default ``_PREDICT_ROWS // S``): one precompute (with the encoders on the batch's [x, y] rows),
+        one layer launch (rows n S + s; the final layer's moments and every local regulariser, nothing else), for a likelihood other than
+        the Gaussian its elementwise density launch, and one ``iwvi_psis_summary`` launch.  The model's minibatch and its per-minibatch
+        caches are as they were afterwards; a call without ``zs`` draws noise, as every predictive call does."""
+        from . import psis as _psis
+        X, Y = _data(X), _data(Y)
+        S = int(S)
+        if proposal not in ("encoder", "prior"):
+            raise ValueError("proposal is 'encoder' or 'prior', not %r" % (proposal,))
+        if kind not in ("predictive", "bound"):
+            raise ValueError("kind is 'predictive' or 'bound', not %r" % (kind,))
+        if not 1 <= S <= _psis.MAX_S:
+            raise ValueError("importance_log_density: S must be in 1..%d (a point's draws are sorted in LDS), got %d" % (_psis.MAX_S, S))
+        lv = [i for i, l in enumerate(self.layers) if isinstance(l, LatentVariableLayer)]
+        enc = proposal == "encoder" and bool(lv)
+        if enc and len(lv) > _abi.MAX_KL:
+            raise ValueError("importance_log_density: %d latent-variable layers, the weight takes at most %d local regularisers (IWVI_MAX_KL)"
+                             % (len(lv), _abi.MAX_KL))
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("importance_log_density evaluates on one rank only (world size %d): run it outside the sharded group"
+                                      % dist.get_world_size())
+        if X.dim() != 2 or X.shape[1] != self._input_dim():
+            raise ValueError("X must be [N, %s], got %s" % (self._input_dim(), tuple(X.shape)))
+        Dy = self._output_dim()
+        if Dy is None:
+            raise ValueError("importance_log_density needs a GP layer as the last layer")
+        Yd = target_dim(self.likelihood, Dy)
+        N = X.shape[0]
+        if Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] != Yd:
+            raise ValueError("Y must be [%d, %s], got %s" % (N, Yd, tuple(Y.shape)))
+        zs = self._check_predict_noise("importance_log_density", S, N, zs)
+        bs = max(1, self._PREDICT_ROWS // S) if batch_size is None else int(batch_size)
+        if bs < 1:
+            raise ValueError("batch_size must be >= 1")
+        dev = X.device
+        names = {"raw": "log_density", "psis": "log_density_psis", "khat": "khat", "ess": "ess"}
+        res = {v: torch.empty(N, dtype=settings.float_type, device=dev) for v in names.values()}
+        if return_logw:
+            res["logw"] = torch.empty(N, S, dtype=settings.float_type, device=dev)
+        if N == 0:
+            return res
+        gauss = is_gaussian(self.likelihood)
+        last = len(self.layers) - 1
+        # the layer launch takes [x, y] rows and cached encoder outputs from the model's CURRENT minibatch: the held-out batch is bound as
+        # that minibatch for the call, with fresh cache buffers (the training ones are not written), and everything is put back
+        held = (self.X, self.Y, self._mb_serial, getattr(self, "_xy_cache", None), getattr(self, "_xy_key", None),
+                [(getattr(self.layers[i], "_enc_out", None), getattr(self.layers[i], "_enc_key", None)) for i in lv])
+        try:
+            if not enc:
+                self.precompute()
+            for lo in range(0, N, bs):
+                hi = min(N, lo + bs)
+                nb = hi - lo
+                xb, yb = _abi.dev_tensor(X[lo:hi].contiguous(), "X"), _abi.dev_tensor(Y[lo:hi].contiguous(), "Y")
+                zb = [None if z is None else _data(z)[:, lo:hi].transpose(0, 1).reshape(nb * S, -1) for z in zs]   # point-major rows n S + s
+                if enc:
+                    self.X, self.Y = xb, yb
+                    self._mb_serial += 1
+                    self._xy_cache = None
+                    for i in lv:
+                        self.layers[i]._enc_out = None
+                    self.precompute(with_encoders=True)
+                _, outs, _ = self._fused_forward(nb * S, S, nb, (nb * S,), zs=zb, sampled_kl=enc, want_layers=True, want_logw=False,
+                                                 use_encoder=enc, X=xb, outputs_for={last}, local_kls=enc)
+                fm, fv = outs[last]["mean"], outs[last]["var"]
+                kls = [outs[i]["kl_local"].reshape(nb * S, -1) for i in lv] if enc else []
+                out = {k: res[v][lo:hi] for k, v in names.items()}
+                if return_logw:
+                    out["logw"] = res["logw"][lo:hi]
+                if gauss:
+                    lik_host, lik_dev = self.likelihood.desc_variance()
+                    _psis.summarise(nb, S, S, 1, fmean=fm, fvar=fv, Y=yb, Dy=Dy, var_exp=kind == "bound", lik_variance=lik_host,
+                                    lik_variance_dev=lik_dev, kls=kls, out=out)
+                else:
+                    terms = torch.empty(nb * S, Yd, dtype=settings.float_type, device=dev)
+                    fn = _abi.lib().iwvi_lik_var_exp if kind == "bound" else _abi.lib().iwvi_lik_predict_density
+                    _abi.check(fn(self.likelihood.lik_desc(), _abi.ptr(fm), _abi.ptr(fv), _abi.ptr(yb), nb * S, Dy, S, nb, _abi.ptr(terms),
+                                  _abi.stream_ptr()))
+                    _psis.summarise(nb, S, S, 1, terms=terms, n_terms=Yd, kls=kls, out=out)
+        finally:
+            self.X, self.Y, self._mb_serial, self._xy_cache, self._xy_key, encs = held
+            for i, (eo, ek) in zip(lv, encs):
+                self.layers[i]._enc_out, self.layers[i]._enc_key = eo, ek
+        return res
+
     def _check_predict_noise(self, what, S, N, zs):
         """``zs`` of the fused predictive routes: one [S, N, dim] array or None per layer; no fed latent-variable placeholders."""
         zs = [None] * len(self.layers) if zs is None else list(zs)
@@ -946,7 +1047,9 @@ class DGP_IWVI(DGP_VI):
 
     def importance_ess(self, zs=None):
         """Kish's effective sample size of every point's K importance weights [B], in [1, K]: (sum_k w_k)^2 / sum_k w_k^2 with
-        w_k = exp(L_nk).  Over all K samples, whatever ``bound`` is (the default included).  Two launches and the reduction."""
+        w_k = exp(L_nk).  Over all K samples, whatever ``bound`` is (the default included).  Two launches and the reduction.
+        The ESS looks healthy on a heavy tail until the one huge weight shows up: ``evaluation.psis_summary(model._logw().view(B, K))`` gives
+        the same ESS together with the Pareto-k diagnostic, which says whether the weights can be trusted at all."""
         logw = self._logw(zs)
         if logw is None:
             raise NotImplementedError("importance_ess reads the layer launch's log-weights; the literal full_cov_over_samples path has none")

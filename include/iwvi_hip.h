@@ -29,7 +29,7 @@ extern "C" {
 
 /* 19, with additive extensions: iwvi_dgp_predict_samples and iwvi_sample_stats, then the iwvi_lik_* entry points (likelihoods other than
  * the Gaussian; iwvi_lik_predict_mixture, their Monte Carlo predictive mixture, last), were added without a change to any existing entry point or struct, so the number did not move and a caller built against
- * 19 keeps working; iwvi_sample_scores and iwvi_energy_score (proper scoring rules of predictive samples) likewise.  A C caller that wants the new symbols looks them up (dlsym), Python asks hasattr(lib, ...). */
+ * 19 keeps working; iwvi_sample_scores and iwvi_energy_score (proper scoring rules of predictive samples) and iwvi_psis_summary (importance-weight summaries with the Pareto-k diagnostic) likewise.  A C caller that wants the new symbols looks them up (dlsym), Python asks hasattr(lib, ...). */
 #define IWVI_ABI_VERSION 19
 
 enum {
@@ -943,6 +943,62 @@ int iwvi_lik_predict_mean_and_var(const iwvi_lik_desc* lik, const float* Fmu, co
 int iwvi_lik_predict_mixture(const iwvi_lik_desc* lik, const float* fmean, const float* fvar, const float* Y,
                              int64_t N, int S, int Dy, int64_t stride_n, int64_t stride_s,
                              float* out_logp, float* out_mean, float* out_var, void* stream);
+
+/* Importance-weight summaries of S draws per point in one launch (additive extension of ABI 19; csrc/psis.hip): the importance-sampled
+ * log density log (1/S) sum_s w_s, Kish's effective sample size, and Pareto-smoothed importance sampling with its diagnostic khat
+ * (Vehtari, Simpson, Gelman, Yao, Gabry, "Pareto smoothed importance sampling"; the generalized-Pareto fit of Zhang & Stephens 2009 with
+ * the PSIS prior).  khat < 0.5: good; 0.5 <= khat < 0.7: usable; khat >= 0.7: the estimate is not reliable at any practical S.
+ * Per point n over its S draws s, every per-row array read at row n*stride_n + s*stride_s (strides >= 0), the log-weight l_ns is
+ *   terms mode    (terms [rows, n_terms], 1 <= n_terms <= IWVI_MAX_P):   l = sum_j terms[row, j] - sum_i sum_c kl_local[i][row, c]
+ *                 n_terms = 1, n_kl = 0 summarises given log-weights [N, S] in any strides -- the training log-weights included; the
+ *                 columns of iwvi_lik_predict_density / iwvi_lik_var_exp are the terms of every likelihood but the Gaussian
+ *   moments mode  (terms == NULL; fmean, fvar [rows, Dy], Y [N, Dy], the Gaussian's variance lik_variance or, if given, *lik_variance_dev):
+ *                 var_exp = 0:  l = sum_d log N(y; m, v + s) - sum kl         (the predictive density of the draw)
+ *                 var_exp = 1:  l = sum_d [log N(y; m, s) - v / (2 s)] - sum kl   (the bound's own term)
+ * kl_local: n_kl <= IWVI_MAX_KL device arrays [rows, kl_dims[i]] (a host array of pointers, read during the call): each latent-variable
+ * layer's sampled log q(w) - log p(w).  Outputs, each [N] but out_logw [N, S] (point-major), any may be NULL, at least one is required:
+ *   out_logw  l_ns                                    out_raw   logsumexp_s l - log S
+ *   out_ess   (sum_s w)^2 / sum_s w^2, in [1, S], as iwvi_bound_logw_reduce
+ *   out_khat, out_psis:  x = sort(l - max l); M = ceil(min(S / 5, 3 sqrt S)); cutoff = max(x[S - M - 1], log 2^-126); the tail is the
+ *             n entries STRICTLY above the cutoff.  n <= 4 (S < 21, all weights equal, ..): khat = +inf and psis = raw.  Otherwise, on the
+ *             exceedances e = exp(tail) - exp(cutoff), ascending:  m = 30 + floor(sqrt n);  b_j = (1 - sqrt(m / (j - 1/2))) / (3 e[floor(n/4
+ *             + 1/2) - 1]) + 1 / e[n - 1];  k_j = mean log1p(-b_j e);  L_j = n (log(-b_j / k_j) - k_j - 1);  w = softmax(L), entries below
+ *             10 * 2^-52 dropped and the rest renormalised;  b = sum w_j b_j;  k = mean log1p(-b e);  sigma = -k / b;
+ *             khat = (n k + 5) / (n + 10).  The tail's i-th log-weight (i = 1 .. n) becomes min(log(sigma expm1(-khat log1p(-p_i)) / khat
+ *             + exp(cutoff)), 0), p_i = (i - 1/2) / n (-sigma log1p(-p_i) when |khat| < 2^-52), and out_psis is the log-mean of the
+ *             weights with that tail.  khat or sigma not finite: the tail stays as it is (psis = raw).
+ * A -inf log-weight is a zero weight; every draw at -inf: raw = psis = -inf, ess = 0, khat = +inf.  A NaN log-weight -- or a +inf one,
+ * which leaves the others no weight to be relative to -- gives NaN in the point's four summaries; other points are not affected.
+ * Arithmetic: float32 inside a draw; exp(l - max l) in float32, every sum in float64; everything from the exceedances on in float64; each
+ * result rounded to float32 once.  ONE launch, no workspace, no atomics, no ticket, no host synchronisation: two calls give the same bits,
+ * and the launch is capturable in a hipGraph.  One sort per point in LDS (csrc/sample_sort.h), four, two or one point per workgroup by S.
+ * IWVI_ERR_ARG (with iwvi_last_error) before any launch for: a null descriptor, N outside 0 .. 2^31 - 1, S outside 1 .. 16384, a negative
+ * stride, neither terms nor moments or both, n_terms or Dy outside 1..IWVI_MAX_P, n_kl outside 0..IWVI_MAX_KL, a NULL kl_local pointer,
+ * a kl_dims entry below 1, moments without Y, lik_variance <= 0 or NaN, no output at all.  N = 0: IWVI_OK, nothing is launched. */
+typedef struct iwvi_psis_desc {
+    const float* terms;
+    int32_t n_terms;
+    const float* fmean;
+    const float* fvar;
+    const float* Y;
+    int32_t Dy;
+    int32_t var_exp;
+    float lik_variance;
+    const float* lik_variance_dev;
+    const float* const* kl_local;
+    const int32_t* kl_dims;
+    int32_t n_kl;
+    int64_t N;
+    int32_t S;
+    int64_t stride_n;
+    int64_t stride_s;
+    float* out_logw;
+    float* out_raw;
+    float* out_ess;
+    float* out_khat;
+    float* out_psis;
+} iwvi_psis_desc;
+int iwvi_psis_summary(const iwvi_psis_desc* desc, void* stream);
 
 /* Exact draws of a predictive target, y ~ p(y | f) with f ~ N(fmean, fvar), for every likelihood above (additive extension of ABI 19;
  * csrc/likelihood_sample.hip).  fmean, fvar [T, Dy]: the final layer's moments, one row per (point, draw) in either layout -- the kernel is

@@ -98,6 +98,9 @@ def main(argv=None):
     p.add_argument("--scores", action="store_true",
                    help="add the proper scoring rules of the predictive draws (evaluate_scores: CRPS, pinball loss, PIT histogram and "
                         "calibration error); not with --mode SGHMC")
+    p.add_argument("--importance", type=int, nargs="?", const=5000, default=0, metavar="S",
+                   help="--mode IWAE / VI: add the importance-sampled held-out log density with S draws per point (default 5000) from the "
+                        "encoder proposal and from the prior, each with its Pareto-k and effective sample size (evaluate_importance)")
     p.add_argument("--kmeans", choices=("host", "device"), default="host",
                    help="where the first layer's inducing inputs are clustered: SciPy's kmeans2 on the host, or iwvi_kmeans on the device")
     p.add_argument("--encoder_gradient", choices=("iwae", "dreg", "stl"), default="iwae",
@@ -131,6 +134,10 @@ def main(argv=None):
     res.update(test_loglik_before_training=before["test_loglik"], train_seconds=dt, ms_per_iteration=dt / max(ARGS.iterations, 1) * 1e3)
     if ARGS.scores:
         res.update(evaluation.evaluate_scores(model, Xs, Ys, ARGS.num_predict_samples, ARGS.predict_batch_size))
+    if ARGS.importance:
+        for proposal in ("encoder", "prior"):
+            r = evaluation.evaluate_importance(model, Xs, Ys, ARGS.importance, proposal=proposal)
+            res.update({"%s_%s" % (k, proposal): v for k, v in r.items()})
     res.update(ARGS.__dict__)
     print(res)
     return res
