@@ -172,7 +172,11 @@ struct WindowCol<NB> { static __device__ __forceinline__ void run(double (&)[NB]
 __device__ __forceinline__ void diag_factor_window(double* blk, int p, int win, double* xT, double* rinv, int lane, unsigned long long* st = nullptr) {
     const int i = lane & 15, lb = lane >> 4;
     const bool ident = lb == 3, live = lb <= win;
-    double* rowp = ident ? xT + i * BLD : blk + boff(p + (live ? lb : 0), p) + i * BLD;
+    // the group's block offset: a select among the (scalar) offsets of the window's three blocks, not a per-lane boff(p + (live ? lb : 0), p)
+    int woff = boff(p, p);
+    woff = (lb == 1 && live) ? boff(p + 1, p) : woff;
+    woff = (lb == 2 && live) ? boff(p + 2, p) : woff;
+    double* rowp = ident ? xT + i * BLD : blk + woff + i * BLD;
     const double* drow = blk + boff(p, p) + i * BLD;            // row i of the diagonal block: a copy in every group
     double a[NB], dg[NB];
     int io = i;                                      // opaque copy: keeps the 16 identity-row constants from being hoisted out
@@ -274,7 +278,11 @@ __device__ __forceinline__ void blk_store(double* C, const f64x4& v, int lane) {
 template <bool PINV = false, class GEN, class POST, class TAIL, class PPACK = int>
 __device__ __forceinline__ void chol_blocks(double* blk, int nbk, double* rinv, double* xT, int tid, int nthreads, GEN gen, POST post, TAIL tail,
                                             unsigned long long* stamps = nullptr, int stamp_p = 1, double* tbuf = nullptr, PPACK pinv_pack = PPACK()) {
-    const int lane = tid & 63, wave = tid >> 6, nw = nthreads >> 6;
+    // The wave index as a SCALAR (v_readfirstlane): with tid >> 6 in a vector register every loop over "my blocks" -- step B, the catch-up,
+    // the Gram generation -- was a divergent loop: EXEC masks around each trip, block offsets by 64-bit vector multiplies.  In step B all of
+    // that sits between the barrier and the first LDS read of the hand-off, eight times per factorisation; as scalar code it is a dozen
+    // s_ instructions (M = 128: k_precompute 24.3 -> 23.3 us, profiles/factor_handoff_kernel_stats_*.csv).
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = nthreads >> 6;
     gen(0, nbk < 2 ? 1 : 2, wave, nw);
     __syncthreads();
     PRE_STAMP(7);
@@ -337,6 +345,7 @@ __device__ __forceinline__ void chol_blocks(double* blk, int nbk, double* rinv, 
             __syncthreads();
             if (p == stamp_p) PRE_STAMP(12);
             step_b(p, m, win);
+            if (p == stamp_p) PRE_STAMP(8);                  // wave 0's own products done; what follows is the wait for the slowest wave
             if (m > 0 || PINV) __syncthreads();
             if (p == stamp_p) PRE_STAMP(13);
         }

@@ -31,7 +31,8 @@ for n, col in zip(names, d.T):
     print("%-10s med %6.2f us" % (n, np.median(col)))
 print("total      med %6.2f us" % np.median((r[:, 6] - r[:, 0]) * 10e-3))
 r2 = np.stack(rows)[:, 0, :].astype(np.float64)
-for a, b, n in ((10, 11, "p=%d diagonal pass (w0)" % args.p), (10, 14, "   rows loaded"), (14, 15, "   16 columns"), (15, 11, "   stored"), (11, 12, "p=%d wait for the other waves" % args.p), (12, 13, "p=%d rows below" % args.p)):
+for a, b, n in ((10, 11, "p=%d diagonal pass (w0)" % args.p), (10, 14, "   rows loaded"), (14, 15, "   16 columns"), (15, 11, "   stored"), (11, 12, "p=%d wait for the other waves" % args.p), (12, 13, "p=%d rows below" % args.p),
+                (12, 8, "   products (w0's block)"), (8, 13, "   second barrier")):
     print("%-24s med %6.2f us" % (n, np.median((r2[:, b] - r2[:, a]) * 10e-3)))
 
 print("%-24s med %6.2f us" % ("start of chol -> this pass", np.median((r2[:, 10] - r2[:, 2]) * 10e-3)))
