@@ -131,9 +131,12 @@ def test_shapes_inside_the_variant_take_it_and_match_the_oracle(gpu_device, why,
         e_lean, lp_lean, lw_lean, v_lean = _evaluate(model, spec, force_general=False)
         e_gen, lp_gen, lw_gen, v_gen = _evaluate(model, spec, force_general=True)
         ref, lp_ref = _read_back_vs_oracle(model, spec, lw_lean)
+        v_back = _last_variant()                                 # (the read-back asks for per-layer outputs)
     finally:
         settings.fw_f32_stage2 = old
     assert v_lean & LEAN_BIT and (v_lean & 0xff) == 5 and bool(v_lean & S16_BIT) == (not f32), (why, hex(v_lean))
+    # the exact words (tests/forward_variant_cases.py names this test as the cover of the four LEAN / SHP instantiations)
+    assert v_lean == (5 | LEAN_BIT | (0 if f32 else S16_BIT)) and v_back == (5 | SHAPES_BIT | (0 if f32 else S16_BIT)), (why, hex(v_lean), hex(v_back))
     assert not (v_gen & (LEAN_BIT | SHAPES_BIT)), (why, hex(v_gen))
     np.testing.assert_array_equal(lw_lean, lw_gen)
     assert abs(e_lean - e_gen) <= 2e-7 * abs(e_gen), (e_lean, e_gen)
