@@ -415,5 +415,5 @@ def stream_ptr():
 def ptr_array(tensors):
     arr = (c_void_p * max(len(tensors), 1))()
     for i, t in enumerate(tensors):
-        arr[i] = t.data_ptr()
+        arr[i] = None if t is None else t.data_ptr()             # (None: a NULL entry, e.g. an encoder layer without a bias)
     return arr

@@ -36,6 +36,7 @@ struct PreEnc {
     float* sample_X; float* sample_kl; float* sample_z;
 };
 constexpr int PRE_MAX_ENC = 2;
+constexpr size_t PRE_LDS_MAX = 160 * 1024;                 // dynamic LDS of a workgroup: an encoder role of up to 7676 weights and biases fits
 struct PreArgs { PreLayer L[IWVI_MAX_LAYERS]; int n; int stop_after; int stamp_p; unsigned long long* stamps; PreEnc E[PRE_MAX_ENC]; int n_enc; };
 
 static unsigned long long* g_pre_stamps = nullptr;   // diagnostic; see iwvi_debug_set_pre_stamps
@@ -932,6 +933,11 @@ extern "C" int iwvi_model_precompute(const iwvi_gp_desc* layers, int n_layers, c
                 E.blk0 = enc_blocks; E.nblk = (int)((d.rows + ENC_ROWS - 1) / ENC_ROWS);
                 enc_blocks += E.nblk;
                 const size_t need = (w + 4 + 2 * (size_t)ENC_ROWS * 65) * sizeof(float);   // weights + two activation buffers
+                if (need > PRE_LDS_MAX) {                  // refused here, before any launch (the layer kernel takes such an encoder: iwvi_layer_desc.enc_W)
+                    set_error("iwvi_model_precompute: encoder %d needs %zu B of LDS (%zu weights and biases + two %d-row activation buffers), more than %zu B; "
+                              "evaluate it in the layer kernel", e, need, w, ENC_ROWS, PRE_LDS_MAX);
+                    return IWVI_ERR_UNSUPPORTED;
+                }
                 if (need > lds) lds = need;
             }
             a.n_enc = n_encs;

@@ -227,7 +227,12 @@ def _activation_code(activation_func):
 class Encoder:
     """MLP [input_dim, *network_dims, 2*latent_dim] with skip connections (reference :108-152), hidden activation
     ``activation_func`` (default tanh like the reference; also relu / sigmoid / softplus / identity, by name or as the torch
-    callable).  Evaluated inside ``iwvi_lv_layer_forward``; ``__call__`` runs that kernel in encoder-only mode."""
+    callable).  Evaluated inside ``iwvi_lv_layer_forward``; ``__call__`` runs that kernel in encoder-only mode.
+
+    ``bs`` may be None (no bias anywhere) or hold None entries (that layer has none): the FORWARD sites take such an encoder -- ``__call__``,
+    ``LatentVariableLayer.propagate`` / ``enc_desc`` / ``fused_desc``, ``torch_raw`` -- and the C-ABI's adjoint does.  The gradient, training
+    and checkpoint code of this package (backward.py, training.py, build_models.py) lists one bias per layer, as the reference's encoder
+    has, and does not take it."""
 
     def __init__(self, latent_dim, input_dim, network_dims, activation_func=None, name=None):
         # A built-in activation (tanh, relu, sigmoid, softplus, identity: by name or as the torch callable) runs inside the HIP kernels.
@@ -255,8 +260,20 @@ class Encoder:
 
     def to(self, device):
         self.Ws = [w.to(device) for w in self.Ws]
-        self.bs = [b.to(device) for b in self.bs]
+        self.bs = None if self.bs is None else [None if b is None else b.to(device) for b in self.bs]
         return self
+
+    # the precompute launch's encoder role (csrc/precompute.hip: role_encoder) keeps the weights, the biases and two 256-row activation
+    # buffers in LDS; an encoder beyond that is evaluated by the layer kernel instead, which holds the weights beside 16-sample tiles
+    PRECOMPUTE_LDS_MAX = 160 * 1024
+
+    def precompute_lds_bytes(self):
+        """Dynamic LDS the precompute launch needs for this encoder (``iwvi_model_precompute`` refuses more than 160 KiB)."""
+        w = sum(a * b + b for a, b in zip(self.layer_dims[:-1], self.layer_dims[1:]))
+        return (w + 4 + 2 * 256 * 65) * 4
+
+    def fits_precompute(self):
+        return self.precompute_lds_bytes() <= self.PRECOMPUTE_LDS_MAX
 
     _TORCH_ACTS = {_abi.ACT_TANH: torch.tanh, _abi.ACT_RELU: torch.relu, _abi.ACT_SIGMOID: torch.sigmoid,
                    _abi.ACT_SOFTPLUS: torch.nn.functional.softplus, _abi.ACT_IDENTITY: (lambda x: x)}
@@ -266,10 +283,11 @@ class Encoder:
         q_sqrt = softplus(raw - 3) (:149-150) is applied by the consumer.  ``Ws`` / ``bs``: stand-ins for the weights (autograd leaves)."""
         act = self.custom_act if self.custom_act is not None else self._TORCH_ACTS[self.act]
         Ws, bs = (self.Ws if Ws is None else Ws), (self.bs if bs is None else bs)
-        n = len(bs)
+        n = len(Ws)
+        bs = [None] * n if bs is None else bs                    # (a missing bias is zero, as in the kernels)
         for i, (W, b, din, dout) in enumerate(zip(Ws, bs, self.layer_dims[:-1], self.layer_dims[1:])):
             Z0 = Z
-            Z = Z @ W + b                                        # :141
+            Z = Z @ W if b is None else Z @ W + b                # :141
             if i < n - 1:
                 Z = act(Z)                                       # :143-144
             if dout == din:
@@ -280,9 +298,10 @@ class Encoder:
         if self.custom_act is not None:
             raise RuntimeError("an Encoder with a custom activation is evaluated by torch_raw(), not inside the kernels")
         Ws = [_abi.dev_tensor(w, "encoder W") for w in self.Ws]
-        bs = [_abi.dev_tensor(b, "encoder b") for b in self.bs]
+        # ``bs = None``: no bias anywhere (enc_b == NULL); an entry None: that layer has none (enc_b[l] == NULL)
+        bs = None if self.bs is None else [None if b is None else _abi.dev_tensor(b, "encoder b") for b in self.bs]
         dims = (ctypes.c_int32 * len(self.layer_dims))(*self.layer_dims)
-        return _abi.ptr_array(Ws), _abi.ptr_array(bs), dims, len(Ws), (Ws, bs)
+        return _abi.ptr_array(Ws), (None if bs is None else _abi.ptr_array(bs)), dims, len(Ws), (Ws, bs)
 
     def __call__(self, Z):
         """-> (q_mu, q_sqrt), each [..., latent_dim]."""
@@ -323,6 +342,14 @@ class LatentVariableLayer:
         self.encoder.to(device)
         return self
 
+    def precompute_refusal(self):
+        """None, or why this layer cannot be evaluated IN FULL inside the precompute launch (``DGP_VI.lv_in_precompute``)."""
+        enc = self.encoder
+        if enc.custom_act is not None or enc.fits_precompute():
+            return None
+        return ("lv_in_precompute: the encoder %s needs %d B of LDS in the precompute launch (more than %d B); "
+                "leave lv_in_precompute off: the layer kernel evaluates it" % (enc.layer_dims, enc.precompute_lds_bytes(), enc.PRECOMPUTE_LDS_MAX))
+
     def enc_desc(self, XY, sample=None):
         """``iwvi_enc_desc``: evaluate this layer's encoder for every row of XY [rows, XY_dim] inside the
         model's precompute launch; the result lands in ``self._enc_out`` [rows, 2*latent_dim].
@@ -341,6 +368,20 @@ class LatentVariableLayer:
                 raise NotImplementedError("the leading-LV-layer-in-the-precompute-launch route needs a built-in encoder activation")
             with torch.no_grad():
                 self._enc_out.copy_(self.encoder.torch_raw(XY))
+            return None, (XY,)
+        if not self.encoder.fits_precompute():
+            # beyond the LDS of the precompute launch's encoder role: the LAYER KERNEL evaluates the MLP (encoder-only mode), into the same
+            # output buffer.  That kernel exports (means, q_sqrt^2), so raw = softplus^-1(q_sqrt) + 3 is rebuilt from it as ``_propagate_fed``
+            # rebuilds it from a fed q_sqrt (float64, rounded once): raw moves by ~1e-7 of q_sqrt's relative rounding, and a q_sqrt below
+            # 1e-19, whose square is no float32, is held there.
+            if sample is not None:
+                raise ValueError(self.precompute_refusal())
+            with torch.no_grad():
+                mu, sg = self.encoder(XY)
+                sg64 = sg.double().clamp_min(1e-19)
+                raw = torch.where(sg64 > 20.0, sg64, torch.log(torch.expm1(sg64))) + 3.0
+                self._enc_out[:, :self.latent_dim].copy_(mu)
+                self._enc_out[:, self.latent_dim:].copy_(raw)
             return None, (XY,)
         Wp, bp, dims, n, k2 = self.encoder.abi_args()
         e = _abi.EncDesc()

@@ -178,6 +178,19 @@ class DGP_VI:
         self.keep_lv_noise = False
         self._dev_words = None
 
+    # -- lv_in_precompute: refused when it is switched on, not at the first evaluation, for an encoder the precompute launch cannot hold --
+    @property
+    def lv_in_precompute(self):
+        return self._lv_in_precompute
+
+    @lv_in_precompute.setter
+    def lv_in_precompute(self, on):
+        if on and self.layers and isinstance(self.layers[0], LatentVariableLayer):
+            why = self.layers[0].precompute_refusal()
+            if why:
+                raise ValueError(why)
+        self._lv_in_precompute = bool(on)
+
     # -- the estimator of the encoder gradient (configuration, not state: no checkpoint carries it) ------------
     # "iwae": the reparameterised gradient of the bound; "dreg" / "stl": the doubly reparameterised estimator and "sticking the landing"
     # (include/iwvi_hip.h: IWVI_LV_GRAD_*), which exist for the sampled regulariser of DGP_IWVI only

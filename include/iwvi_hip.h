@@ -132,7 +132,10 @@ int iwvi_gp_dense_inverse(const iwvi_gp_desc* layers_host, int n_layers, void* s
  * the minibatch: it does not depend on the factorisation, so it runs on otherwise idle CUs, off the critical
  * path of iwvi_dgp_forward (which then takes iwvi_layer_desc.enc_out instead of the weights).
  *   XY [rows, dims[0]];  enc_W[i] [dims[i], dims[i+1]], enc_b[i] [dims[i+1]] (host arrays of device pointers);
- *   out [rows, 2*latent_dim] = (means | raw), q_sqrt = softplus(raw - 3). */
+ *   out [rows, 2*latent_dim] = (means | raw), q_sqrt = softplus(raw - 3).
+ * An encoder role keeps its weights, biases and two 256-row activation buffers in LDS: (w + 4 + 2 * 256 * 65) floats for w weights and
+ * biases, so w <= 7676 (e.g. widths [64, 64, 64, 2] do not fit).  A larger encoder is refused with IWVI_ERR_UNSUPPORTED before
+ * anything is launched; iwvi_dgp_forward evaluates it from iwvi_layer_desc.enc_W. */
 typedef struct iwvi_enc_desc {
     const float* XY; int64_t rows;
     const float* const* enc_W; const float* const* enc_b; const int32_t* dims; int32_t n_enc, latent_dim;

@@ -1,4 +1,4 @@
-"""NumPy restatement of the library's stand-alone noise stream (``iwvi_fill_normal`` / ``iwvi_fill_normal_dev``, k_fill_normal in
+"""NumPy restatement of the library's noise streams: the layer stack's (``layer_normal`` below, draw_normal4) and the stand-alone one (``iwvi_fill_normal`` / ``iwvi_fill_normal_dev``, k_fill_normal in
 csrc/lv_elbo.hip; philox4x32_10 and box_muller4 in csrc/iwvi_common.h).  TEST INFRASTRUCTURE ONLY:
 tests/test_philox_reference_host.py pins this module on the CPU (Random123's known answers), tests/test_gpu_fill_normal.py compares the
 kernel with it.
@@ -62,3 +62,17 @@ def fill_normal(n, seed, offset, first=0, pairing=((0, 1), (2, 3))):
     """Elements first .. n-1 (first a multiple of 4) of iwvi_fill_normal(out, n, seed, offset), float64."""
     assert first % 4 == 0
     return box_muller(fill_words(n, seed, offset, first), pairing).reshape(-1)[:n - first]
+
+
+def layer_normal(seed, step, layer, t, dims, pairing=((0, 1), (2, 3))):
+    """The layer stack's own stream (draw_normal4 in csrc/iwvi_common.h): the draws of samples ``t`` (array of row indices) for the ``dims``
+    noise components of layer ``layer`` in evaluation ``step`` -> [len(t), dims] float64.  Components 4 q .. 4 q + 3 of sample t come from
+    the block of counter (lo32(t), hi32(t), 256 layer + q, lo32(step)) under the key (lo32(seed), hi32(seed) ^ hi32(step)); a last quad
+    that ``dims`` does not fill is drawn whole and cut."""
+    t = np.asarray(t, dtype=np.uint64).reshape(-1, 1)
+    q = np.arange((dims + 3) // 4, dtype=np.uint64).reshape(1, -1)
+    one = np.ones((t.shape[0], q.shape[1]), dtype=np.uint64)
+    counter = np.stack([(t & MASK32) * one, (t >> np.uint64(32)) * one, (np.uint64(256 * layer) + q) * one,
+                        np.uint64(step & 0xFFFFFFFF) * one], axis=-1)
+    key = np.array([seed & 0xFFFFFFFF, ((seed >> 32) ^ (step >> 32)) & 0xFFFFFFFF], dtype=np.uint64)
+    return box_muller(philox4x32_10(counter, key), pairing).reshape(t.shape[0], -1)[:, :dims]
